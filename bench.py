@@ -46,6 +46,14 @@ rank 0's NCCL_DEBUG=INFO log).  Every rank arms a watchdog (NK_BENCH_TIMEOUT_S, 
 stack of a hung rank and exits; the self-spawning launcher has an overall timeout and relays the last 2 KB of every
 rank's stderr when the job fails.
 
+`--dump-outputs DIR` (default workload) writes what the LAST timed step handed to its caller as DIR/<name>.npy, f32: the
+loss, the model's output, the parameters after that step's SGD update and the gradients the backward pass left on the
+intermediate nodes (the parameter gradients are consumed and re-zeroed inside the step).  An array of more than
+DUMP_SAMPLE elements is stored as a fixed seeded sample of its flattened elements (`dump_sample_index`), so the directory
+stays under DUMP_MAX_BYTES.  The dump is a function of the arguments alone: inputs and initial parameters are seeded, and
+the untimed steps (whose number follows the clock) run with a learning rate of 0, so the K timed steps always start
+from the initial parameters.  The JSON line lists what was written under `dumped_outputs`.
+
 Other workloads (parity-test configurations, not the headline): --workload matmul | conv | mha.
 """
 from __future__ import annotations
@@ -97,7 +105,16 @@ def parse():
     ap.add_argument("--dp-channels", type=int, default=16,
                     help="N > 1: cap RCCL at this many channels (NCCL_MAX_NCHANNELS, unless the caller set it) and tell the GEMMs "
                          "that many resident-block slots are busy while the exchange runs; 0: RCCL's own choice, GEMMs plan for an idle chip")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, output, updated parameters, intermediate "
+                         "gradients) as DIR/<name>.npy; same arguments, same inputs, from run to run (mlp workload)")
+    a = ap.parse_args()
+    if a.dump_outputs is not None:
+        if a.workload != "mlp":
+            ap.error("--dump-outputs is implemented for the default workload (--workload mlp)")
+        if a.steps < 1:
+            ap.error("--dump-outputs needs at least one timed step")
+    return a
 
 
 class Dist:
@@ -138,9 +155,11 @@ def device_sync(tdev):
     tdev.sync()
 
 
-def timed_steps(dist, tdev, cdev, step, steps, warmup, profile=True):
+def timed_steps(dist, tdev, cdev, step, steps, warmup, profile=True, before_timed=None):
     """W untimed + exactly K timed steps, barrier + sync on both sides; returns (host seconds for
     the K steps, max over ranks), device-event ms, and the GEMM/conv launch statistics.
+    `before_timed`: called once between the last untimed step and the timed region (host-side state only: the device
+    must not go idle there).
     `profile=False`: no HIP events around the individual launches (two event records per launch make a step of
     microsecond kernels host-bound: 1024^3 reads 94 us per fwd+bwd with them, 70 without)."""
     from neuronika_amd import capi
@@ -165,6 +184,8 @@ def timed_steps(dist, tdev, cdev, step, steps, warmup, profile=True):
         d = dist.max(time.perf_counter() - t1)
         per_step, elapsed, extra = d / n, elapsed + d, extra + n
     EXTRA_STATS["settle_steps"] = extra
+    if before_timed is not None:
+        before_timed()
     dist.barrier()
     if os.environ.get("NK_BENCH_NO_LAUNCH_EVENTS") == "1":   # measurement aid: what the per-launch event pairs cost the step
         profile = False
@@ -202,6 +223,39 @@ def timed_steps(dist, tdev, cdev, step, steps, warmup, profile=True):
 SETTLE_S = 0.15   # seconds of untimed load before the timed region (at least the W warm-up steps)
 LAUNCH_EVENTS_EVERY = 4   # timed steps whose MFMA launches carry HIP event pairs: every 4th (timed_steps)
 EXTRA_STATS = {}  # kernel classes only one workload has (the fused attention core of C5), from the last timed_steps()
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: upper bound of everything written
+DUMP_SAMPLE = 1 << 20       # elements kept of an array that has more
+DUMP_SEED = 0x6E6B          # seed of the sample ("nk")
+
+
+def dump_sample_index(size):
+    """The flat indices (ascending) --dump-outputs keeps of an array of `size` > DUMP_SAMPLE elements: a function of
+    `size` alone, so two runs (or two builds) store the same elements."""
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(size, DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: ndarray} as dirname/<name>.npy (f32 / f64, whole or the `dump_sample_index` sample); returns the
+    description that goes into the JSON line."""
+    os.makedirs(dirname, exist_ok=True)
+    index, described, total = {}, {}, 0
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr)
+        if arr.dtype not in (np.float32, np.float64):
+            arr = arr.astype(np.float64)
+        rec = {"shape": list(arr.shape), "dtype": arr.dtype.name, "sampled": arr.size > DUMP_SAMPLE}
+        if rec["sampled"]:
+            if arr.size not in index:
+                index[arr.size] = dump_sample_index(arr.size)
+            arr = arr.reshape(-1)[index[arr.size]]
+        rec["elements_written"] = int(arr.size)
+        total += arr.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"[bench] --dump-outputs: {name} would take the dump past {DUMP_MAX_BYTES} bytes")
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        described[name] = rec
+    return {"dir": dirname, "bytes": total, "of_timed_step": None, "arrays": described,
+            "sample": f"arrays of more than {DUMP_SAMPLE} elements: flat[sort(default_rng({DUMP_SEED}).choice(size, {DUMP_SAMPLE}, replace=False))]"}
 
 
 def read_traffic(kernel):
@@ -651,14 +705,17 @@ def run_mlp(a, dist):
     unfused = os.environ.get("NK_BENCH_UNFUSED_RELU") == "1"
     was = t.nn.set_relu_peephole(not unfused)
     try:
-        out = lins[2].forward(lins[1].forward(lins[0].forward(X).relu()).relu())
+        h1 = lins[0].forward(X).relu()
+        h2 = lins[1].forward(h1).relu()
+        out = lins[2].forward(h2)
     finally:
         t.nn.set_relu_peephole(was)
     loss = out.mse(T, t.Reduction.Mean)
     params = []
     for lin in lins:
         params += [lin.weight, lin.bias]
-    opt = t.optim.SGD(1e-3)
+    lr = 1e-3
+    opt = t.optim.SGD(lr)
     for p in params:
         opt.register(p)
     _log("graph built")
@@ -708,10 +765,30 @@ def run_mlp(a, dist):
         alone = allreduce_alone(dist, tdev, cdev, comm.raw(), sizes)
         _log(f"stand-alone all-reduce: {alone[0]['ms']} ms for {alone[0]['bytes']} B")
 
-    dt, ev_ms, gemm, _ = timed_steps(dist, tdev, cdev, step, a.steps, a.warmup)
+    before_timed = None
+    if a.dump_outputs is not None:
+        # The number of untimed steps follows the clock (timed_steps): with a learning rate of 0 they run the same kernels
+        # and leave the parameters bit for bit as initialised (w - g * 0), so the K timed steps start from the same state
+        # in every run and the dump below depends on the arguments only.
+        opt.set_lr(0.0)
+        before_timed = lambda: opt.set_lr(lr)
+    dt, ev_ms, gemm, _ = timed_steps(dist, tdev, cdev, step, a.steps, a.warmup, before_timed=before_timed)
     _log(f"timed loop done: {dt / a.steps * 1e3:.3f} ms/step")
     settle = EXTRA_STATS["settle_steps"]           # (the later timed_steps calls of this function overwrite it)
     loss_val = loss.item()
+    dumped = None
+    if a.dump_outputs is not None and dist.rank == 0:
+        # what timed step K left behind, read before anything else runs: the loss and the output it computed, the gradients
+        # its backward pass left on the intermediate nodes, the parameters after its SGD update (their gradients are zero
+        # again: the step ends with zero_grad)
+        arrays = {"loss": np.array([loss_val], np.float32), "output": out.data(), "output_grad": out.grad(),
+                  "hidden2_grad": h2.grad(), "hidden1_grad": h1.grad()}
+        for i, lin in enumerate(lins):
+            arrays[f"linear{i}_weight"] = lin.weight.data()
+            arrays[f"linear{i}_bias"] = lin.bias.data()
+        dumped = dump_outputs(a.dump_outputs, arrays)
+        dumped["of_timed_step"] = a.steps
+        _log(f"dumped {len(arrays)} arrays, {dumped['bytes']} bytes, to {a.dump_outputs}")
     n_exch = sync.exchanges_issued() if sync is not None else 0
     per_rank = dist.gather(ev_ms / a.steps)
     exposed, gemm_off = 0.0, None
@@ -763,6 +840,8 @@ def run_mlp(a, dist):
             "device_ms_per_step": round(ev_ms / a.steps, 4), "loss": loss_val,
             "gemm_share_of_step": round(gemm[1] / ev_ms, 4) if ev_ms > 0 else None,
         }
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         if sync is not None:
             res["dp_channels"] = {"nccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS"), "gemm_busy_slots": sync.busy_slots()}
             res["per_rank_device_ms_per_step"] = [round(v, 4) for v in per_rank]

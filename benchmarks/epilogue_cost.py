@@ -1,7 +1,7 @@
 """Fixed cost of a GEMM launch next to its k-loop: 4096 x 4096 x K for K = 32 ... 4096, beta = 0 and 1 (where the
 remaining 14 % of the 4096^3 launch go)."""
 import os, sys, json
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neuronika_amd import capi as c
 from benchmarks.microbench import timeit, rand
 dev = c.Device(0)

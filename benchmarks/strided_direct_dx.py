@@ -1,7 +1,7 @@
 """Round 6: the direct (<= 16 channels per group) input gradient of STRIDED convolutions - depthwise / grouped / few-channel layers -
 with whatever library NEURONIKA_HIP_LIB points at (run alternately against benchmarks/_ab/head.so: conv_direct_bwd_input_strided_kernel vs the general kernel)."""
 import os, sys, json
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from neuronika_amd import capi as c
 dev = c.Device(0)

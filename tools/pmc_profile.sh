@@ -6,8 +6,8 @@
 # then python tools/rocpd_pmc_summary.py OUTDIR/<target>/*/*_results.db
 set -u
 out=$1; shift
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-root=${GRAFT_REPO_ROOT:-/root/repo}
 declare -A G
 G[a]="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE"
 G[b]="SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_IFETCH SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT"

@@ -3,7 +3,7 @@
 # tools/rocpd_kernel_stats.py), micro-benchmarks.   bash tools/profile_round.sh OUTDIR TAG     (on the GPU box)
 set -u
 out=$1; tag=$2
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 mkdir -p "$root/$out"
 cd /tmp && export TMPDIR=/tmp
 for w in mlp matmul conv mha; do

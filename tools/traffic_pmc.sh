@@ -4,8 +4,8 @@
 # under its own timeout.      bash tools/traffic_pmc.sh OUTDIR        then      python tools/make_roofline_traffic.py OUTDIR
 set -u
 out=$1
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-root=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p "$root/$out"
 for tgt in gemm_once conv_step_once mha_step_once; do
   for c in FETCH_SIZE WRITE_SIZE; do
