@@ -774,11 +774,12 @@ struct HeadsAttentionFwd : Forward {
     Shared<bool> status;
     uint64_t seed;
     Shared<uint64_t> calls;  // each forward draws a fresh mask (the Philox offset advances), as AttnProbsFwd
+    bool causal = false;     // nk_attention_causal_*: query r attends to keys <= r (same draws, same offset advance)
     void forward() const override {
         const uint64_t sp = ((uint64_t)hg.S + 31) / 32 * 32;  // the draws are indexed in the padded (B*H, SP, SP) tensor (SP = S unless S is ragged)
         const uint64_t offset = (*calls) * (((uint64_t)hg.B * hg.H * sp * sp + 7) / 8);  // draws per forward, 8 per Philox call
         // scores / stats / mask are null in a graph without gradients: nothing is kept, no (B*H, S, S) tensor exists
-        check(nk_attention_fwd(D(q), q->ptr(), k->ptr(), v->ptr(), scores ? scores->ptr() : nullptr, stats ? stats->ptr() : nullptr,
+        check((causal ? nk_attention_causal_fwd : nk_attention_fwd)(D(q), q->ptr(), k->ptr(), v->ptr(), scores ? scores->ptr() : nullptr, stats ? stats->ptr() : nullptr,
                                mask ? reinterpret_cast<uint32_t*>(mask->ptr()) : nullptr, o->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
                                *status ? 1 : 0, seed, offset));
         ++(*calls);  // only a forward that was issued consumes its Philox range (a refused capture throws above)
@@ -792,6 +793,7 @@ struct HeadsAttentionBwd : Backward {
     float scale;
     double p;
     Shared<bool> status;
+    bool causal = false;
     void backward() const override {
         const HipArray& G = g->borrow();  // dO, flat layout
         nk_device* dev = D(q);
@@ -800,7 +802,7 @@ struct HeadsAttentionBwd : Backward {
         float* gk = first_write(dk, bk);
         float* gv = first_write(dv, bv);
         // dS and Pd are written by the fused kernel, dQ comes out of it; dK / dV are the two batched products on dS / Pd
-        check(nk_attention_bwd(dev, gq, gk, gv, ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
+        check((causal ? nk_attention_causal_bwd : nk_attention_bwd)(dev, gq, gk, gv, ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
                                reinterpret_cast<const uint32_t*>(mask->ptr()), q->ptr(), k->ptr(), v->ptr(), hg.B, hg.S, hg.H, hg.dh, scale,
                                p, *status ? 1 : 0, bq == 0.f ? 1 : 0, bk == 0.f ? 1 : 0, bv == 0.f ? 1 : 0));
     }
@@ -821,12 +823,13 @@ struct QkvAttentionFwd : Forward {
     Shared<bool> status;
     uint64_t seed;
     Shared<uint64_t> calls;
+    bool causal = false;
     void forward() const override {
         const int n = hg.B * hg.S, d = hg.d();
         check(nk_linear_fwd(D(x), x->ptr(), w->ptr(), b->ptr(), qkv->ptr(), n, d, 3 * d));
         const uint64_t sp = ((uint64_t)hg.S + 31) / 32 * 32;
         const uint64_t offset = (*calls) * (((uint64_t)hg.B * hg.H * sp * sp + 7) / 8);
-        check(nk_attention_qkv_fwd(D(x), qkv->ptr(), scores ? scores->ptr() : nullptr, stats ? stats->ptr() : nullptr,
+        check((causal ? nk_attention_qkv_causal_fwd : nk_attention_qkv_fwd)(D(x), qkv->ptr(), scores ? scores->ptr() : nullptr, stats ? stats->ptr() : nullptr,
                                    mask ? reinterpret_cast<uint32_t*>(mask->ptr()) : nullptr, o->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
                                    *status ? 1 : 0, seed, offset));
         ++(*calls);
@@ -841,6 +844,7 @@ struct QkvAttentionBwd : Backward {
     float scale;
     double p;
     Shared<bool> status;
+    bool causal = false;
     // the three views are written by ONE kernel: it may assign only when all three still wait for their zero fill
     static float packed_beta(const Shared<Gradient> (&v)[3]) {
         bool all = true;
@@ -856,7 +860,7 @@ struct QkvAttentionBwd : Backward {
         const HipArray& G = g->borrow();  // dO (B*S, d)
         nk_device* dev = D(x);
         const int n = hg.B * hg.S, d = hg.d();
-        check(nk_attention_qkv_bwd(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
+        check((causal ? nk_attention_qkv_causal_bwd : nk_attention_qkv_bwd)(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
                                    reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
                                    *status ? 1 : 0, 1));
         float beta;
@@ -1335,7 +1339,7 @@ VarDiff VarDiff::heads_context(const VarDiff& values, int B, int S, int H, int d
 }
 bool Var::attention_core_supported(int S, int dh, double p) { return nk_attention_supported(S, dh, p, 1) != 0; }
 static Var heads_attention_node(const Var& q, const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
-                                Shared<bool> status, bool keep) {
+                                Shared<bool> status, bool keep, bool causal) {
     if (!(p >= 0.0 && p <= 1.0)) panic("Wrong probability received: " + std::to_string(p) + ".");
     check_heads(q.shape(), {}, B, S, H, dh, false);
     check_heads(keys.shape(), {}, B, S, H, dh, false);
@@ -1353,19 +1357,19 @@ static Var heads_attention_node(const Var& q, const Var& keys, const Var& values
         op->mask = zeros_like(q.data, Shape{B * H, SP, SP / 32});
     }
     op->o = zeros_like(q.data, Shape{B * S, H * dh});
-    op->scale = scale; op->p = p; op->status = std::move(status);
+    op->scale = scale; op->p = p; op->status = std::move(status); op->causal = causal;
     op->seed = next_node_seed();
     op->calls = std::make_shared<uint64_t>(0);
     auto y = op->o;
     return Var::node(y, op, std::move(h));
 }
 Var Var::heads_attention(const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
-                         Shared<bool> status) const {
-    return heads_attention_node(*this, keys, values, B, S, H, dh, scale, p, std::move(status), false);
+                         Shared<bool> status, bool causal) const {
+    return heads_attention_node(*this, keys, values, B, S, H, dh, scale, p, std::move(status), false, causal);
 }
 VarDiff VarDiff::heads_attention(const VarDiff& keys, const VarDiff& values, int B, int S, int H, int dh, float scale, double p,
-                                 Shared<bool> status) const {
-    Var out = heads_attention_node(var, keys.var, values.var, B, S, H, dh, scale, p, status, true);
+                                 Shared<bool> status, bool causal) const {
+    Var out = heads_attention_node(var, keys.var, values.var, B, S, H, dh, scale, p, status, true, causal);
     auto fwd = std::dynamic_pointer_cast<HeadsAttentionFwd>(out.history.to_vec().back().op);
     History<BackwardEntry> h = history;
     h.merge(keys.history);
@@ -1376,7 +1380,7 @@ VarDiff VarDiff::heads_attention(const VarDiff& keys, const VarDiff& values, int
     bw->ds = zeros_like(fwd->scores, fwd->scores->shape());
     bw->dropped = zeros_like(fwd->scores, fwd->scores->shape());
     bw->dq = grad; bw->dk = keys.grad; bw->dv = values.grad; bw->g = g;
-    bw->scale = scale; bw->p = p; bw->status = status;
+    bw->scale = scale; bw->p = p; bw->status = status; bw->causal = causal;
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(h));
 }
 Var Var::bmm(const Var& rhs) const { return matmul_var(2, *this, rhs); }
@@ -2078,7 +2082,7 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     fw->stats = zeros_like(x.var.data, Shape{B * H, SP, 2});
     fw->mask = zeros_like(x.var.data, Shape{B * H, SP, SP / 32});
     fw->o = zeros_like(x.var.data, Shape{B * S, d});
-    fw->scale = scale; fw->p = m.drop.p; fw->status = m.drop.status;
+    fw->scale = scale; fw->p = m.drop.p; fw->status = m.drop.status; fw->causal = m.causal;
     fw->seed = next_node_seed();
     fw->calls = std::make_shared<uint64_t>(0);
     Var out = Var::node(fw->o, fw, std::move(hf));
@@ -2094,7 +2098,7 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     bw->dx = x.grad;
     const Linear* ls[3] = {&m.q, &m.k, &m.v};
     for (int i = 0; i < 3; ++i) { bw->gw[i] = ls[i]->weight.grad; bw->gb[i] = ls[i]->bias.grad; }
-    bw->g = g; bw->scale = scale; bw->p = m.drop.p; bw->status = m.drop.status;
+    bw->g = g; bw->scale = scale; bw->p = m.drop.p; bw->status = m.drop.status; bw->causal = m.causal;
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(hb));
 }
 VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
@@ -2113,24 +2117,34 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
         }
         return true;
     };
+    // Causal, where the fused core does not apply: the composition spelled out - one Addition node (broadcast over B*H) of a
+    // constant (S, S) leaf, 0 on and below the diagonal and -inf above, in front of the Softmax, whose -inf lanes come out exactly 0.
+    // Uploaded once per graph build; the fused `attention_probs` node has no mask operand and is not used.
+    auto causal_mask = [&](int n) {
+        std::vector<float> m((size_t)n * n, 0.f);
+        for (int r = 0; r < n; ++r)
+            for (int c = r + 1; c < n; ++c) m[(size_t)r * n + c] = -INFINITY;
+        return from_host(x.var.device(), Shape{n, n}, m.data());
+    };
     if (packed_qkv && wqkv_ && strided_heads && fused && fused_core && q.fused && k.fused && v.fused && Var::attention_core_supported(S, dh, drop.p) &&
         still_packed())
         return o.forward(qkv_attention_node(*this, wqkv_, bqkv_, gwqkv_, gbqkv_, x, batch, S, heads, dh, scale));
     if (strided_heads && dh % 4 == 0) {  // attention GEMMs address the heads inside the projection layout: no copies
         const VarDiff Qf = q.forward(x), Kf = k.forward(x), Vf = v.forward(x);
         if (fused && fused_core && Var::attention_core_supported(S, dh, drop.p))
-            return o.forward(Qf.heads_attention(Kf, Vf, batch, S, heads, dh, scale, drop.p, drop.status));
+            return o.forward(Qf.heads_attention(Kf, Vf, batch, S, heads, dh, scale, drop.p, drop.status, causal));
         const VarDiff scores = Qf.heads_scores(Kf, batch, S, heads, dh);
-        const VarDiff P = (fused && S % 4 == 0 && S <= 2048) ? scores.attention_probs(scale, drop.p, drop.status)
-                                                             : drop.forward((scores * scale).softmax(2));
+        const VarDiff P = causal ? drop.forward((scores * scale + causal_mask(S)).softmax(2))
+                          : (fused && S % 4 == 0 && S <= 2048) ? scores.attention_probs(scale, drop.p, drop.status)
+                                                               : drop.forward((scores * scale).softmax(2));
         return o.forward(P.heads_context(Vf, batch, S, heads, dh));
     }
     const VarDiff Q = q.forward(x).split_heads(batch, S, heads, dh);
     const VarDiff K = k.forward(x).split_heads(batch, S, heads, dh);
     const VarDiff V = v.forward(x).split_heads(batch, S, heads, dh);
-    const VarDiff P = (fused && S % 4 == 0 && S <= 2048)
-                          ? Q.bmm_t(K).attention_probs(scale, drop.p, drop.status)
-                          : drop.forward((Q.bmm_t(K) * scale).softmax(2));
+    const VarDiff P = causal ? drop.forward((Q.bmm_t(K) * scale + causal_mask(S)).softmax(2))
+                      : (fused && S % 4 == 0 && S <= 2048) ? Q.bmm_t(K).attention_probs(scale, drop.p, drop.status)
+                                                           : drop.forward((Q.bmm_t(K) * scale).softmax(2));
     const VarDiff O = P.bmm(V).merge_heads(batch, S, heads, dh);
     return o.forward(O);
 }

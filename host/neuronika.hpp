@@ -344,8 +344,9 @@ class Var {
     // the whole per-(sample, head) chain heads_scores -> attention_probs -> heads_context as ONE node on the fused
     // attention kernels (nk_attention_fwd): self = Q, all three operands (B*S, H*dh) -> (B*S, H*dh).  The score tile
     // stays on chip between the two products; see attention_core_supported() for the shapes it takes.
+    // causal: query r attends to keys <= r (nk_attention_causal_fwd; the composition gains one Addition node in front of the Softmax)
     Var heads_attention(const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
-                        Shared<bool> status) const;
+                        Shared<bool> status, bool causal = false) const;
     static bool attention_core_supported(int S, int dh, double p);
 };
 
@@ -439,7 +440,7 @@ class VarDiff {
     VarDiff heads_context(const VarDiff& values, int B, int S, int H, int dh) const;
     VarDiff attention_probs(float scale, double p, Shared<bool> status, bool store_probs = false) const;
     VarDiff heads_attention(const VarDiff& keys, const VarDiff& values, int B, int S, int H, int dh, float scale, double p,
-                            Shared<bool> status) const;
+                            Shared<bool> status, bool causal = false) const;
 };
 
 // `Add/Sub/Mul/Div` with NumPy broadcasting, all four differentiability combinations
@@ -632,6 +633,11 @@ struct MultiheadAttention {
     // as column blocks of the packed output (`nk_attention_qkv_*`).  q / k / v stay ordinary `Linear`s over those views
     // (optimizers, serde and the data-parallel exchange see three parameters as before).  false: three Linear nodes.
     bool packed_qkv = true;
+    // Causal self-attention: query r of a sample attends to keys <= r of that sample - P = dropout(softmax(scores * scale + M)),
+    // M[r][k] = 0 for k <= r and -inf above.  Read when forward() builds the graph, like the switches above, and honoured on every
+    // path: the fused core runs its causal kernels (which skip the key tiles above the diagonal); the node-by-node paths add M, a
+    // constant (S, S) leaf, on the broadcast Addition node.  Dropout draws keep their positions either way.
+    bool causal = false;
     MultiheadAttention(DevicePtr dev, int d_model, int heads, double p, uint64_t seed);
     // four Linear layers built elsewhere (e.g. deserialised): their weights are NOT packed, `packed_qkv` is off
     MultiheadAttention(Linear q, Linear k, Linear v, Linear o, int heads, double p);

@@ -77,8 +77,10 @@ PYBIND11_MODULE(_tape, m) {
         .def("mm", py::overload_cast<const VarDiff&>(&Var::mm, py::const_))
         .def("mm_t", py::overload_cast<const Var&>(&Var::mm_t, py::const_))
         .def("mm_t", py::overload_cast<const VarDiff&>(&Var::mm_t, py::const_))
-        .def("heads_attention", [](const Var& q, const Var& k, const Var& v, int B, int S, int H, int dh, float scale, double p, const Status& s) {
-            return q.heads_attention(k, v, B, S, H, dh, scale, p, s.flag); })
+        .def("heads_attention", [](const Var& q, const Var& k, const Var& v, int B, int S, int H, int dh, float scale, double p, const Status& s,
+                                   bool causal) { return q.heads_attention(k, v, B, S, H, dh, scale, p, s.flag, causal); },
+             py::arg("keys"), py::arg("values"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("dh"), py::arg("scale"), py::arg("p"),
+             py::arg("status"), py::arg("causal") = false)
         .def_static("attention_core_supported", &Var::attention_core_supported)
         .def("convolution", &Var::convolution)
         .def("__add__", [](const Var& a, const Var& b) { return a + b; })
@@ -138,8 +140,10 @@ PYBIND11_MODULE(_tape, m) {
         .def("mm", py::overload_cast<const VarDiff&>(&VarDiff::mm, py::const_))
         .def("mm_t", py::overload_cast<const Var&>(&VarDiff::mm_t, py::const_))
         .def("mm_t", py::overload_cast<const VarDiff&>(&VarDiff::mm_t, py::const_))
-        .def("heads_attention", [](const VarDiff& q, const VarDiff& k, const VarDiff& v, int B, int S, int H, int dh, float scale, double p, const Status& s) {
-            return q.heads_attention(k, v, B, S, H, dh, scale, p, s.flag); })
+        .def("heads_attention", [](const VarDiff& q, const VarDiff& k, const VarDiff& v, int B, int S, int H, int dh, float scale, double p,
+                                   const Status& s, bool causal) { return q.heads_attention(k, v, B, S, H, dh, scale, p, s.flag, causal); },
+             py::arg("keys"), py::arg("values"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("dh"), py::arg("scale"), py::arg("p"),
+             py::arg("status"), py::arg("causal") = false)
         .def("convolution", py::overload_cast<const Var&, const std::vector<int>&, const std::vector<int>&, int>(&VarDiff::convolution, py::const_))
         .def("convolution", py::overload_cast<const VarDiff&, const std::vector<int>&, const std::vector<int>&, int>(&VarDiff::convolution, py::const_))
         .def("__add__", [](const VarDiff& a, const Var& b) { return a + b; })
@@ -335,6 +339,7 @@ PYBIND11_MODULE(_tape, m) {
         .def_readwrite("strided_heads", &nn::MultiheadAttention::strided_heads)
         .def_readwrite("fused_core", &nn::MultiheadAttention::fused_core)
         .def_readwrite("packed_qkv", &nn::MultiheadAttention::packed_qkv)
+        .def_readwrite("causal", &nn::MultiheadAttention::causal)
         .def("forward", &nn::MultiheadAttention::forward);
 
     py::module_ optim = m.def_submodule("optim");

@@ -528,7 +528,8 @@ int nk_scale_softmax_dropout_bwd_from_scores(nk_device* dev, float* d_scores, co
  * Dropout mask: score (bh, r, k) takes draw (bh*SP + r)*SP + k of the layout documented at nk_dropout_fwd - for S % 32 == 0 the
  * Philox stream of nk_scale_softmax_dropout_fwd on the (B*H, S, S) tensor (same seed / offset -> same mask); one forward
  * consumes ceil(B*H*SP*SP / 8) calls.
- * nk_attention_supported: dh in {32, 64, 128}, S >= 1, not (train and p == 1); callers fall back to the node-by-node path. */
+ * nk_attention_supported: dh in {32, 64, 128}, S >= 1, not (train and p == 1) - the answer holds for the causal entry points
+ * below as well; callers fall back to the node-by-node path. */
 int nk_attention_supported(int S, int dh, double p, int train);
 /* forward: writes the raw scores (for the backward pass), the row statistics, the dropout draws (1 bit per score:
  * B*H*SP*SP/32 words laid out [b*H + h][SP/32 query tiles][SP/32 key tiles][32 queries of the tile], bit 16 j + e of a word =
@@ -556,6 +557,32 @@ int nk_attention_qkv_fwd(nk_device* dev, const float* QKV, float* scores, float*
 int nk_attention_qkv_bwd(nk_device* dev, float* dQKV, float* dS, float* dropped, const float* dO, const float* O, const float* scores,
                          const float* stats, const uint32_t* mask_bits, const float* QKV, int B, int S, int H, int dh, float scale,
                          double p, int train, int assign);
+/* Causal self-attention: query row r of a sample attends to the key rows k <= r of that sample.  As a composition it is the chain
+ * above with one Addition node (node/addition/mod.rs:39-50; AdditionBackward: the gradient passes through) in front of the Softmax:
+ *   P = dropout(softmax(Q_bh.K_bh^T * scale + M, axis 1)),  M (S, S) constant, M[r][k] = 0 for k <= r and -inf for k > r
+ * (Softmax of a lane with -inf entries is exactly 0 there, node/softmax/mod.rs:37-53; every row keeps its diagonal).  Same parameter
+ * lists, layouts, row statistics ((m2, 1 / sum) over the unmasked keys) and draw layout as the four entry points above: score
+ * (bh, r, k) takes draw (bh*SP + r)*SP + k whether masked or not and one forward consumes ceil(B*H*SP*SP / 8) calls, so a masked
+ * position's draw is simply unused and the mask agrees with the non-causal kernels' and nk_dropout_fwd's on every position.
+ * What differs is the scratch contract.  The kernels walk the key tiles on and below the diagonal only (a block of 128 queries
+ * 128 qb .. visits keys < 128 qb + 128): `scores`, `dS`, `dropped` and `mask_bits` keep their (B*H, SP, SP) allocation and layout, but
+ * the 32 x 32 tiles strictly above the diagonal are NOT WRITTEN AND NOT READ - they hold whatever the buffer held.  In a visited
+ * tile a masked position's score is -inf.  The backward writes zeros to dS and Pd above the diagonal INSIDE every 128 x 128 diagonal
+ * block, so both are defined (and exactly 0 at masked positions) on every 128 x 128 block that touches or lies below the diagonal and
+ * undefined strictly above; dK_bh (+)= dS_bh^T.Q_bh and dV_bh (+)= Pd_bh^T.dO_bh reduce, per strip of 128 keys, over the queries from
+ * the strip's first row on and never read an undefined block. */
+int nk_attention_causal_fwd(nk_device* dev, const float* Q, const float* K, const float* V, float* scores, float* stats,
+                            uint32_t* mask_bits, float* O, int B, int S, int H, int dh, float scale, double p, int train,
+                            uint64_t seed, uint64_t offset);
+int nk_attention_causal_bwd(nk_device* dev, float* dQ, float* dK, float* dV, float* dS, float* dropped, const float* dO,
+                            const float* O, const float* scores, const float* stats, const uint32_t* mask_bits, const float* Q,
+                            const float* K, const float* V, int B, int S, int H, int dh, float scale, double p, int train,
+                            int assign_dq, int assign_dk, int assign_dv);
+int nk_attention_qkv_causal_fwd(nk_device* dev, const float* QKV, float* scores, float* stats, uint32_t* mask_bits, float* O, int B,
+                                int S, int H, int dh, float scale, double p, int train, uint64_t seed, uint64_t offset);
+int nk_attention_qkv_causal_bwd(nk_device* dev, float* dQKV, float* dS, float* dropped, const float* dO, const float* O,
+                                const float* scores, const float* stats, const uint32_t* mask_bits, const float* QKV, int B, int S, int H,
+                                int dh, float scale, double p, int train, int assign);
 /* ------------------------------------------------------------------ dropout ------------ */
 /* Dropout::forward node/dropout/mod.rs:53-79.  train && 0<p<1: noise ~ Bernoulli(1-p) in
  * {0,1} is (re)drawn from Philox4x32-10(seed, offset) and written to `noise` (f32, like the

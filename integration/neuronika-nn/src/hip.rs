@@ -207,7 +207,7 @@ conv_layer!(Conv3d, GroupedConv3d, Ix5, Ix4, (usize, usize, usize),
 /// (`q_weight()` / `k_weight()` / `v_weight()` name the row blocks for initialisation from separate matrices) - one GEMM with
 /// N = 3 d forward and one with K = 3 d for the input gradient instead of three each - and the per-head chain is one node
 /// reading queries, keys and values in place as the column blocks of that projection (`HipVarDiff::packed_heads_attention`:
-/// `nk_attention_qkv_fwd` / `nk_attention_qkv_bwd`).  Head sizes the fused core does not cover
+/// `nk_attention_qkv_fwd` / `nk_attention_qkv_bwd`, or their `_causal_` counterparts when `causal` is set).  Head sizes the fused core does not cover
 /// (`ffi::nk_attention_supported`: dh in {32, 64, 128}) are rejected at construction.
 pub struct MultiheadAttention {
     pub qkv: Linear,
@@ -215,6 +215,9 @@ pub struct MultiheadAttention {
     pub d_model: usize,
     pub heads: usize,
     pub dropout: Dropout,
+    /// Causal self-attention: query `r` of a sample attends to the keys `<= r` of that sample (`P = dropout(softmax(scores * scale +
+    /// M))`, `M` = 0 on and below the diagonal, -inf above).  Read by `forward` when it builds the graph; `false` after `new`.
+    pub causal: bool,
 }
 
 impl MultiheadAttention {
@@ -223,7 +226,8 @@ impl MultiheadAttention {
         assert!(matches!(d_model / heads, 32 | 64 | 128), "MultiheadAttention: head size must be 32, 64 or 128");
         // each of the three row blocks is initialised as its own Linear(d_model, d_model): U(-k, k), k = 1 / sqrt(d_model) -
         // the fan-in of the packed layer is d_model too, so one draw over (3 d, d) follows the same law
-        Self { qkv: Linear::new(d_model, 3 * d_model, device), o: Linear::new(d_model, d_model, device), d_model, heads, dropout: Dropout::new(p) }
+        Self { qkv: Linear::new(d_model, 3 * d_model, device), o: Linear::new(d_model, d_model, device), d_model, heads, dropout: Dropout::new(p),
+               causal: false }
     }
 
     /// Row range of the packed weight (and element range of the packed bias) holding the query / key / value projection.
@@ -246,7 +250,11 @@ impl MultiheadAttention {
         let (seq, dh) = (rows / batch, self.d_model / self.heads);
         let scale = 1. / (dh as f32).sqrt();
         let packed = self.qkv.forward(input);
-        let context = packed.packed_heads_attention(batch, seq, self.heads, dh, scale, self.dropout.p, self.dropout.status.clone());
+        let context = if self.causal {
+            packed.packed_heads_attention_causal(batch, seq, self.heads, dh, scale, self.dropout.p, self.dropout.status.clone())
+        } else {
+            packed.packed_heads_attention(batch, seq, self.heads, dh, scale, self.dropout.p, self.dropout.status.clone())
+        };
         self.o.forward(context)
     }
 }

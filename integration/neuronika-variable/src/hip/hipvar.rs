@@ -797,6 +797,21 @@ impl HipVarDiff<Ix2> {
     #[allow(clippy::too_many_arguments)]
     pub fn packed_heads_attention(self, batch: usize, seq: usize, heads: usize, dh: usize, scale: f32, p: f64,
                                   status: Rc<Cell<bool>>) -> HipVarDiff<Ix2> {
+        self.packed_attention_node(batch, seq, heads, dh, scale, p, status, false)
+    }
+
+    /// `packed_heads_attention` for causal self-attention: query `r` of a sample attends to the keys `<= r` of that sample
+    /// (`nk_attention_qkv_causal_fwd` / `_bwd`: the kernels skip the key tiles above the diagonal; the score / dS / Pd tiles there
+    /// are neither written nor read).  Same dropout draws and offset advance as the full form.
+    #[allow(clippy::too_many_arguments)]
+    pub fn packed_heads_attention_causal(self, batch: usize, seq: usize, heads: usize, dh: usize, scale: f32, p: f64,
+                                         status: Rc<Cell<bool>>) -> HipVarDiff<Ix2> {
+        self.packed_attention_node(batch, seq, heads, dh, scale, p, status, true)
+    }
+
+    #[allow(clippy::too_many_arguments)]
+    fn packed_attention_node(self, batch: usize, seq: usize, heads: usize, dh: usize, scale: f32, p: f64, status: Rc<Cell<bool>>,
+                             causal: bool) -> HipVarDiff<Ix2> {
         let device = self.var.data.borrow().device().clone();
         let geometry = Heads { batch: batch as i32, seq: seq as i32, heads: heads as i32, dh: dh as i32 };
         let sp = (seq + 31) / 32 * 32;
@@ -804,11 +819,12 @@ impl HipVarDiff<Ix2> {
         let state = Rc::new(AttentionState { scores: big(sp), stats: big(2), mask_bits: big(sp / 32), calls: Cell::new(0) });
         let dim = ndarray::Dim([batch * seq, heads * dh]);
         let data = shared(dim, &device);
-        let fwd = PackedHeadsAttention::new(geometry, self.var.data.clone(), state.clone(), data.clone(), scale, p, status.clone(), next_seed());
+        let fwd = PackedHeadsAttention::new(geometry, self.var.data.clone(), state.clone(), data.clone(), scale, p, status.clone(), next_seed(),
+                                            causal);
         let var = HipVar::node(data.clone(), Rc::new(fwd), self.var.history);
         let grad = Rc::new(Gradient::hip_zeros(dim, device));
         let bwd = PackedHeadsAttentionBackward::new(geometry, self.var.data, data, state, big(sp), big(sp), self.grad, grad.clone(), scale, p,
-                                                    status);
+                                                    status, causal);
         let op: Rc<dyn Backward> = Rc::new(bwd);
         HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
     }

@@ -148,16 +148,17 @@ pub(crate) struct PackedHeadsAttention {
     p: f64,
     status: Rc<Cell<bool>>,
     seed: u64,
+    causal: bool, // query r attends to keys <= r: `nk_attention_qkv_causal_fwd` (same draws, same offset advance)
 }
 
 impl PackedHeadsAttention {
     #[allow(clippy::too_many_arguments)]
     pub(crate) fn new(geometry: Heads, packed: Shared<HipArray<Ix2>>, state: Rc<AttentionState>, data: Shared<HipArray<Ix2>>, scale: f32,
-                      p: f64, status: Rc<Cell<bool>>, seed: u64) -> Self {
+                      p: f64, status: Rc<Cell<bool>>, seed: u64, causal: bool) -> Self {
         if !(0. ..=1.).contains(&p) {
             panic!("Wrong probability received: {}.", p);
         }
-        Self { geometry, packed, state, data, scale, p, status, seed }
+        Self { geometry, packed, state, data, scale, p, status, seed, causal }
     }
 }
 
@@ -171,9 +172,15 @@ impl Forward for PackedHeadsAttention {
         let elems = (h.batch as u64) * (h.heads as u64) * sp * sp;
         let offset = self.state.calls.get() * ((elems + 7) / 8);
         ffi::check(unsafe {
-            ffi::nk_attention_qkv_fwd(qkv.device().as_raw(), qkv.as_ptr(), scores.as_mut_ptr(), stats.as_mut_ptr(), bits.as_mut_ptr() as *mut u32,
-                                      out.as_mut_ptr(), h.batch, h.seq, h.heads, h.dh, self.scale, self.p, self.status.get() as i32, self.seed,
-                                      offset)
+            if self.causal {
+                ffi::nk_attention_qkv_causal_fwd(qkv.device().as_raw(), qkv.as_ptr(), scores.as_mut_ptr(), stats.as_mut_ptr(),
+                                                 bits.as_mut_ptr() as *mut u32, out.as_mut_ptr(), h.batch, h.seq, h.heads, h.dh, self.scale, self.p,
+                                                 self.status.get() as i32, self.seed, offset)
+            } else {
+                ffi::nk_attention_qkv_fwd(qkv.device().as_raw(), qkv.as_ptr(), scores.as_mut_ptr(), stats.as_mut_ptr(), bits.as_mut_ptr() as *mut u32,
+                                          out.as_mut_ptr(), h.batch, h.seq, h.heads, h.dh, self.scale, self.p, self.status.get() as i32, self.seed,
+                                          offset)
+            }
         });
         self.state.calls.set(self.state.calls.get() + 1);
     }
@@ -193,14 +200,15 @@ pub(crate) struct PackedHeadsAttentionBackward {
     scale: f32,
     p: f64,
     status: Rc<Cell<bool>>,
+    causal: bool, // `nk_attention_qkv_causal_bwd`: dS / Pd are defined on and below the diagonal blocks only
 }
 
 impl PackedHeadsAttentionBackward {
     #[allow(clippy::too_many_arguments)]
     pub(crate) fn new(geometry: Heads, packed: Shared<HipArray<Ix2>>, output: Shared<HipArray<Ix2>>, state: Rc<AttentionState>,
                       d_scores: Shared<HipArray<Ix3>>, dropped: Shared<HipArray<Ix3>>, packed_gradient: Rc<Gradient<HipArray<Ix2>, Ix2>>,
-                      gradient: Rc<Gradient<HipArray<Ix2>, Ix2>>, scale: f32, p: f64, status: Rc<Cell<bool>>) -> Self {
-        Self { geometry, packed, output, state, d_scores, dropped, packed_gradient, gradient, scale, p, status }
+                      gradient: Rc<Gradient<HipArray<Ix2>, Ix2>>, scale: f32, p: f64, status: Rc<Cell<bool>>, causal: bool) -> Self {
+        Self { geometry, packed, output, state, d_scores, dropped, packed_gradient, gradient, scale, p, status, causal }
     }
 }
 
@@ -213,9 +221,15 @@ impl Backward for PackedHeadsAttentionBackward {
         let h = self.geometry;
         let mut dqkv = self.packed_gradient.borrow_mut();
         ffi::check(unsafe {
-            ffi::nk_attention_qkv_bwd(g.device().as_raw(), dqkv.as_mut_ptr(), ds.as_mut_ptr(), pd.as_mut_ptr(), g.as_ptr(), o.as_ptr(),
-                                      scores.as_ptr(), stats.as_ptr(), bits.as_ptr() as *const u32, qkv.as_ptr(), h.batch, h.seq, h.heads, h.dh,
-                                      self.scale, self.p, self.status.get() as i32, 0)
+            if self.causal {
+                ffi::nk_attention_qkv_causal_bwd(g.device().as_raw(), dqkv.as_mut_ptr(), ds.as_mut_ptr(), pd.as_mut_ptr(), g.as_ptr(), o.as_ptr(),
+                                                 scores.as_ptr(), stats.as_ptr(), bits.as_ptr() as *const u32, qkv.as_ptr(), h.batch, h.seq, h.heads,
+                                                 h.dh, self.scale, self.p, self.status.get() as i32, 0)
+            } else {
+                ffi::nk_attention_qkv_bwd(g.device().as_raw(), dqkv.as_mut_ptr(), ds.as_mut_ptr(), pd.as_mut_ptr(), g.as_ptr(), o.as_ptr(),
+                                          scores.as_ptr(), stats.as_ptr(), bits.as_ptr() as *const u32, qkv.as_ptr(), h.batch, h.seq, h.heads, h.dh,
+                                          self.scale, self.p, self.status.get() as i32, 0)
+            }
         });
     }
 

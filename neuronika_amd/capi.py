@@ -167,6 +167,11 @@ _SIGS = {
                          C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_attention_qkv_fwd": [VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_attention_qkv_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_int],
+    "nk_attention_causal_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
+    "nk_attention_causal_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double,
+                         C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_attention_qkv_causal_fwd": [VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
+    "nk_attention_qkv_causal_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_int],
     "nk_scale_softmax_dropout_fwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_scale_softmax_dropout_bwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_dropout_fwd": [VP, VP, VP, VP, C.c_size_t, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
@@ -746,31 +751,34 @@ def attention_padded(S):
     return (S + 31) // 32 * 32
 
 
-def attention_fwd(dev, Q, K, V, scores, stats, mask_bits, out, B, S, H, dh, scale, p, train=True, seed=0, offset=0):
+def attention_fwd(dev, Q, K, V, scores, stats, mask_bits, out, B, S, H, dh, scale, p, train=True, seed=0, offset=0, causal=False):
     """Fused attention core: scores (B*H,SP,SP), stats (B*H,SP,2), mask_bits (B*H,SP,SP/32 words held in an f32 array; None
     when dropout is inactive) and out (B*S,H*dh) are written, SP = S rounded up to a multiple of 32 (`attention_padded`).
-    scores = stats = None: inference (out only)."""
-    check(lib.nk_attention_fwd(dev.h, Q.p, K.p, V.p, scores.p if scores is not None else None, stats.p if stats is not None else None,
+    scores = stats = None: inference (out only).  causal: query r attends to keys <= r (nk_attention_causal_fwd; the 32 x 32
+    tiles of the scratch tensors strictly above the diagonal are neither written nor read)."""
+    check((lib.nk_attention_causal_fwd if causal else lib.nk_attention_fwd)(dev.h, Q.p, K.p, V.p, scores.p if scores is not None else None, stats.p if stats is not None else None,
                                mask_bits.p if mask_bits is not None else None, out.p,
                                B, S, H, dh, scale, float(p), int(train), seed, offset))
 
 
 def attention_bwd(dev, dQ, dK, dV, dS, dropped, dO, out, scores, stats, mask_bits, Q, K, V, B, S, H, dh, scale, p, train=True,
-                  assign=(False, False, False)):
-    """dS and dropped (B*H,SP,SP elements, scratch) are written; dQ / dK / dV (+)= the three input gradients per (sample, head)."""
-    check(lib.nk_attention_bwd(dev.h, dQ.p, dK.p, dV.p, dS.p, dropped.p, dO.p, out.p, scores.p, stats.p,
+                  assign=(False, False, False), causal=False):
+    """dS and dropped (B*H,SP,SP elements, scratch) are written; dQ / dK / dV (+)= the three input gradients per (sample, head).
+    causal: dS / dropped are defined on the 128 x 128 blocks that touch or lie below the diagonal only."""
+    check((lib.nk_attention_causal_bwd if causal else lib.nk_attention_bwd)(dev.h, dQ.p, dK.p, dV.p, dS.p, dropped.p, dO.p, out.p, scores.p, stats.p,
                                mask_bits.p if mask_bits is not None else None, Q.p, K.p, V.p, B, S, H, dh, scale, float(p),
                                int(train), int(assign[0]), int(assign[1]), int(assign[2])))
 
 
-def attention_qkv_fwd(dev, QKV, scores, stats, mask_bits, out, B, S, H, dh, scale, p, train=True, seed=0, offset=0):
+def attention_qkv_fwd(dev, QKV, scores, stats, mask_bits, out, B, S, H, dh, scale, p, train=True, seed=0, offset=0, causal=False):
     """attention_fwd with Q, K, V as the three column blocks of ONE (B*S, 3*H*dh) array."""
-    check(lib.nk_attention_qkv_fwd(dev.h, QKV.p, scores.p if scores is not None else None, stats.p if stats is not None else None,
+    check((lib.nk_attention_qkv_causal_fwd if causal else lib.nk_attention_qkv_fwd)(dev.h, QKV.p, scores.p if scores is not None else None, stats.p if stats is not None else None,
                                    mask_bits.p if mask_bits is not None else None, out.p, B, S, H, dh, scale, float(p), int(train), seed, offset))
 
 
-def attention_qkv_bwd(dev, dQKV, dS, dropped, dO, out, scores, stats, mask_bits, QKV, B, S, H, dh, scale, p, train=True, assign=False):
-    check(lib.nk_attention_qkv_bwd(dev.h, dQKV.p, dS.p, dropped.p, dO.p, out.p, scores.p, stats.p,
+def attention_qkv_bwd(dev, dQKV, dS, dropped, dO, out, scores, stats, mask_bits, QKV, B, S, H, dh, scale, p, train=True, assign=False,
+                      causal=False):
+    check((lib.nk_attention_qkv_causal_bwd if causal else lib.nk_attention_qkv_bwd)(dev.h, dQKV.p, dS.p, dropped.p, dO.p, out.p, scores.p, stats.p,
                                    mask_bits.p if mask_bits is not None else None, QKV.p, B, S, H, dh, scale, float(p), int(train), int(assign)))
 
 

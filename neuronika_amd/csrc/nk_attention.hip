@@ -72,6 +72,7 @@ struct AttnArgs {
     float scale, keep, dscale;
     float c1;          // scale * log2(e): exponents are taken in base 2
     unsigned keep_lt;  // a draw v is kept iff v < keep_lt = floor((1 - p) * 2^32)  (nk_common.h: the Bernoulli construction)
+    int rev;           // causal: a head's query blocks in descending order (longest walk first); sits in the 4 bytes of padding in front of `seed`
     unsigned long long seed, offset;
     int assign;        // backward: dQ = (1) or += (0)
     int SP;            // S rounded up to a multiple of 32: row count and row stride of the (B*H, SP, SP) scratch tensors (scores, dS, Pd,
@@ -118,7 +119,18 @@ __device__ __forceinline__ void tile_flush(const float* scrw, float* g /* &T[row
 // -inf in the forward (probability exactly 0; the stored -inf makes the backward's recomputed probability, dS and Pd exactly 0 too),
 // padded queries compute a copy of row S - 1 that is never stored outside the scratch.  The dropout draws of score (bh, r, k) are
 // indexed in the PADDED tensor ((bh * SP + r) * SP + k), which keeps a lane's 16 keys on two whole Philox calls.
-template <bool BWD, bool MASKED, bool FULL, int OCC, bool KEEP = true, int DH = 64, bool RAGGED = false>
+// CAUSAL: query r attends to keys k <= r (the composition with one Addition node in front of the Softmax: scores + M, M[r][k] = 0 for
+// k <= r and -inf above; Softmax gives exactly 0 there).  Query block qb (rows 128 qb ..) stages key tiles 0 .. min(ntile, 4 qb + 4) - 1
+// and nothing beyond; its wave w (rows 32 (4 qb + w) ..) computes tiles kt <= dk = 4 qb + w.  Tiles kt < 4 qb are whole for all four
+// waves and run the loop body as it is (the MAIN part: no predicate, see FULL); the last (at most) four tiles are the TAIL part, the
+// same body under a per-wave predicate: tile dk is the wave's diagonal tile, where key 32 dk + 16 h + e is masked for query
+// 32 dk + q when 16 h + e > q - the forward stores -inf as its score, exactly as RAGGED does for padded keys, so the backward's
+// recomputed probability, dS and Pd are exactly 0 there without a second test; for kt > dk the wave takes part in the staging and
+// the barrier, draws nothing, and (backward) writes ZERO tiles of dS and Pd, so that both are defined on every 128 x 128 block that
+// touches or lies below the diagonal (what the dK / dV products read).  Score, dS, Pd and mask-word tiles above that are neither
+// written nor read.  Dropout draws keep their positions in the padded tensor (a masked position's draw is unused).  The blocks of a
+// head are handed out longest first (p.rev): they differ in length by nqb x and the short ones fill the end of the grid.
+template <bool BWD, bool MASKED, bool FULL, int OCC, bool KEEP = true, int DH = 64, bool RAGGED = false, bool CAUSAL = false>
 __global__ __launch_bounds__(A_NT, OCC) void attention_kernel(const AttnArgs p) {
     static_assert(!(RAGGED && FULL), "ragged sequence lengths take the guarded instantiation");
     constexpr int X1_LD = x1_ld(DH), X2_LD = x2_ld(DH);
@@ -133,12 +145,14 @@ __global__ __launch_bounds__(A_NT, OCC) void attention_kernel(const AttnArgs p) 
     // blocks of one (sample, head) are consecutive in the sequence and one XCD takes a contiguous chunk of it: the 512 KB
     // of K and V a head's blocks share stay in that XCD's L2
     const int seq = nkmma::xcd_chunk(blockIdx.x, gridDim.x);
-    const int bh = seq / p.nqb, qb = seq % p.nqb;
+    const int bh = seq / p.nqb, qb = CAUSAL && p.rev ? p.nqb - 1 - seq % p.nqb : seq % p.nqb;
     const long long samp = (long long)(bh / p.H) * p.S, hoff = (long long)(bh % p.H) * DH;
     const long long flat0 = samp * p.ldx + hoff;   // (sample, head) origin in x1 / x2; bq, ctx and out have their own row strides
     const int q0 = qb * A_QB + w * 32;
     const bool on = FULL ? true : q0 < p.S;  // wave-uniform: the wave has at least one query
     const int SP = RAGGED ? p.SP : p.S;
+    const int nt = CAUSAL ? min(p.ntile, 4 * qb + 4) : p.ntile;   // key tiles this block walks
+    const int dk = 4 * qb + w;                                    // causal: this wave's diagonal tile (< ntile whenever `on`)
     const float* x1 = p.x1 + flat0;
     const float* x2 = p.x2 + flat0;
 
@@ -253,154 +267,17 @@ __global__ __launch_bounds__(A_NT, OCC) void attention_kernel(const AttnArgs p) 
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     __syncthreads();
 
-    for (int kt = 0; kt < p.ntile; ++kt) {
-        const int cur = kt & 1;
-        const bool more = kt + 1 < p.ntile;
-        if (more) A_STAGE_LOAD(kt + 1);
-        if (on) {
-            float sv[16];
-            unsigned mybits = 0;
-            if (BWD) {  // score tile (put into the scratch at the end of the previous iteration) -> lane layout; fetch the next one
-                if (MASKED) mybits = mkn >> (16 * h);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float4 t = *reinterpret_cast<const float4*>(&scrw[q * SCR_LD + 16 * h + 4 * c]);
-                    sv[4 * c] = t.x; sv[4 * c + 1] = t.y; sv[4 * c + 2] = t.z; sv[4 * c + 3] = t.w;
-                }
-                if (more) A_SCORES_LOAD(kt + 1);
-            }
-            // ---- pass 1: C[key][query] = X1 . Bq^T  (forward: scores; backward: dPd) -------------------------------
-            f32x16 acc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-            {
-                const float* a1 = &x1s[cur][q * X1_LD + 4 * h];
-#pragma unroll
-                for (int j = 0; j < DH / 8; ++j) {
-                    const float4 a = *reinterpret_cast<const float4*>(a1 + 8 * j);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bq[j].x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bq[j].y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bq[j].z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, bq[j].w, acc, 0, 0, 0);
-                }
-            }
-            // Bernoulli(1 - p) draws of this lane's 16 keys.  Forward: 2 Philox calls (8 consecutive keys each, the draw
-            // layout of nk_common.h / nk_dropout_fwd / nk_scale_softmax_dropout_fwd), packed to one bit per score for the
-            // backward pass - the Philox rounds were ~2000 of the ~6500 issue cycles of a masked tile with one word per
-            // score (v_mad_u64_u32 is quarter rate) and are paid once, not twice; the backward mask is the forward's by
-            // construction (the reference shares the noise buffer the same way, node/dropout/mod.rs:113-128).
-            bool kp[16];          // forward: the compare results stay lane masks in SGPR pairs (the masked forward is at its VGPR limit)
-            int km[16];           // backward: 0 / -1 per key as AND operands (one v_bfe_i32 + one v_and per use instead of bit test + compare + select)
-            if (MASKED && !BWD) {
-                unsigned bits = 0;
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const unsigned long long ctr = ctr0 + (unsigned long long)(kt * 4 + c);
-                    const uint4 r = philox4x32_10(make_uint4((unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0u), key);
-                    const unsigned wv[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const bool k0 = wv[k] < p.keep_lt, k1 = nk_rot16(wv[k]) < p.keep_lt;
-                        kp[8 * c + 2 * k] = k0;
-                        kp[8 * c + 2 * k + 1] = k1;
-                        bits |= (k0 ? 1u : 0u) << (8 * c + 2 * k);
-                        bits |= (k1 ? 1u : 0u) << (8 * c + 2 * k + 1);
-                    }
-                }
-                const unsigned other = (unsigned)__shfl_xor((int)bits, 32, 64);
-                if (KEEP && h == 0) mwave[kt * 32] = bits | (other << 16);
-            }
-            if (MASKED && BWD) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) km[e] = __builtin_amdgcn_sbfe((int)mybits, e, 1);   // v_bfe_i32: 0 / -1
-            }
-            float bv[16];  // B operand of pass 2
-            if (!BWD) {
-                float raw[16];
-#pragma unroll
-                for (int e = 0; e < 16; ++e) raw[e] = acc[e];
-                if (RAGGED && kt == p.ntile - 1) {  // keys beyond S: probability exactly 0, here and (through the stored score) in the backward
-                    const int nvalid = p.S - 32 * kt - 16 * h;
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) raw[e] = e < nvalid ? raw[e] : -INFINITY;
-                }
-                if (KEEP) tile_write(scrw, raw, lane);
-                // Online softmax in the base-2 exponent domain: exp(s*scale - m) = exp2(s*c1 - m2), c1 = scale*log2(e), one fma
-                // and one v_exp_f32 per element.  f32 MFMA and VALU instructions do NOT overlap on a SIMD (measured,
-                // benchmarks/native/mfma_valu_overlap.hip: both run on the f32 lanes), so every VALU instruction here is
-                // paid in full on top of the 64 MFMAs of the tile.
-                float rmax = raw[0];
-#pragma unroll
-                for (int e = 1; e < 16; ++e) rmax = fmaxf(rmax, raw[e]);   // scale > 0: max of the scaled = scaled max
-                rmax = fmaxf(rmax, __shfl_xor(rmax, 32, 64));
-                const float tm2 = rmax * p.c1;
-                // The running max only has to bound the exponents, not equal the true max: it moves when a tile exceeds it by
-                // more than 2^6 (terms stay <= 64, sums <= 2^16), i.e. after the first tile practically never, and the rescale
-                // of the 32 accumulator registers is skipped (wave-uniform test).  Softmax is invariant to the shift, and the
-                // backward pass recomputes the probabilities with the stored (shift, 1 / sum) pair.
-                if (__any(tm2 > m_run + 6.f)) {
-                    const float m_new = fmaxf(m_run, tm2);
-                    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-                    l_run *= alpha;
-                    m_run = m_new;
-#pragma unroll
-                    for (int d = 0; d < ND; ++d)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) oacc[d][e] *= alpha;
-                }
-                float ps = 0.f;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { sv[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(raw[e], p.c1, -m_run)); ps += sv[e]; }
-                ps += __shfl_xor(ps, 32, 64);
-                l_run += ps;
-                // Dropout: the 1 / (1 - p) factor is applied once, with the normalisation, in the epilogue
-#pragma unroll
-                for (int e = 0; e < 16; ++e) bv[e] = MASKED ? (kp[e] ? sv[e] : 0.f) : sv[e];
-            } else {
-                float pd[16];
-                const float inv_s = l_run * p.scale;                      // P * scale = e * (1/sum * scale)
-                const float inv_d = MASKED ? l_run * p.dscale : l_run;    // Pd = e * (1/sum * 1/(1-p)) where kept
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float ev = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[e], p.c1, -m_run));  // exp(s*scale - shift), as the forward
-                    const float gv = MASKED ? __int_as_float(__float_as_int(acc[e]) & km[e]) : acc[e];  // DropoutBackward: g * noise
-                    bv[e] = (ev * inv_s) * (gv - dot);                           // SoftmaxBackward, MultiplicationBackwardLeft
-                    pd[e] = MASKED ? __int_as_float(__float_as_int(ev * inv_d) & km[e]) : ev * inv_d;    // Dropout forward (for dV = Pd^T . dO)
-                }
-                tile_write(scrw, bv, lane);   // (the score tile was read out of this region at the top of the iteration)
-                tile_write(scrb, pd, lane);
-            }
-            // ---- pass 2: out^T[dh][query] += X2^T . C ----------------------------------------------------------------
-            {
-                // column tile d of the output reads dh column 32 d + q of the key rows 16 h + e, stored rotated by 32 h
-                const float* const a2b = &x2s[cur][(16 * h) * X2_LD];
-                const int c0 = (q + 32 * h) & (DH - 1), c1 = (q + 32 + 32 * h) & (DH - 1), c2 = (q + 64 + 32 * h) & (DH - 1),
-                          c3 = (q + 96 + 32 * h) & (DH - 1);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    oacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2b[e * X2_LD + c0], bv[e], oacc[0], 0, 0, 0);
-                    if constexpr (ND > 1) oacc[ND > 1 ? 1 : 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2b[e * X2_LD + c1], bv[e], oacc[ND > 1 ? 1 : 0], 0, 0, 0);
-                    if constexpr (ND > 2) {
-                        oacc[ND > 2 ? 2 : 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2b[e * X2_LD + c2], bv[e], oacc[ND > 2 ? 2 : 0], 0, 0, 0);
-                        oacc[ND > 2 ? 3 : 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2b[e * X2_LD + c3], bv[e], oacc[ND > 2 ? 3 : 0], 0, 0, 0);
-                    }
-                }
-                (void)c1; (void)c2; (void)c3;
-            }
-            // ---- the tiles written to the scratch before pass 2 go to HBM now (machine scheduler pinned: hoisting the
-            //      ds_reads above the MFMAs would put the LDS round trip back on the critical path) ---------------------
-            __builtin_amdgcn_sched_barrier(0);
-            wave_lds_handover();
-            if (!BWD) {
-                if (KEEP) tile_flush(scrw, p.scores + rowbase + kt * 32, SP, lane);
-            } else {
-                tile_flush(scrw, p.ds + rowbase + kt * 32, SP, lane);
-                tile_flush(scrb, p.dropped + rowbase + kt * 32, SP, lane);
-                if (more) { wave_lds_handover(); A_SCORES_TO_LDS(); }   // next tile's scores (loaded during this iteration)
-            }
+    for (int kt = 0; kt < (CAUSAL ? 4 * qb : nt); ++kt) {   // causal: the tiles left of the block's diagonal square (4 qb < nt)
+#define NK_ATT_TAIL false
+#include "nk_attention_tile.h"
+#undef NK_ATT_TAIL
+    }
+    if constexpr (CAUSAL) {
+        for (int kt = 4 * qb; kt < nt; ++kt) {
+#define NK_ATT_TAIL true
+#include "nk_attention_tile.h"
+#undef NK_ATT_TAIL
         }
-        if (more) A_STAGE_STORE(cur ^ 1);
-        __syncthreads();
     }
 #undef A_STAGE_LOAD
 #undef A_STAGE_STORE
@@ -452,11 +329,12 @@ int attention_check(int B, int S, int H, int dh, double p, int train, float scal
     return NK_OK;
 }
 
-template <bool BWD, int DH>
+template <bool BWD, int DH, bool CAUSAL>
 int attention_launch_dh(nk_device* dev, AttnArgs& a, int B, int S, int H, double p, int train, uint64_t seed, uint64_t offset, float scale) {
     a.S = S; a.H = H; a.nqb = (S + A_QB - 1) / A_QB; a.SP = (S + 31) / 32 * 32; a.ntile = a.SP / 32;
     a.scale = scale; a.c1 = scale * 1.44269504088896341f; a.keep = (float)(1.0 - p); a.dscale = 1.f / (1.f - (float)p);  // as nk_scale_softmax_dropout_fwd
     a.seed = seed; a.offset = offset;
+    a.rev = 1;   // (a kernel argument, not a template parameter: the ascending order is one word away for a sweep)
     a.keep_lt = nk_keep_threshold(1.0 - p);   // Bernoulli::new(1. - p), node/dropout/mod.rs:46
     const bool masked = train && p != 0.0;
     if (!BWD && masked)   // (the backward reads the forward's stored bits: nothing of its own to freeze)
@@ -471,13 +349,14 @@ int attention_launch_dh(nk_device* dev, AttnArgs& a, int B, int S, int H, double
     // DH = 32: the DH = 64 budgets.
     constexpr int OCC_F = DH == 128 ? 1 : 3, OCC_B = DH == 128 ? 1 : 2;   // forward / backward blocks per CU
     constexpr int OCC_DEFAULT = BWD ? OCC_B : OCC_F;
-    const bool occ2 = !BWD && DH != 128 && dev->tune_attn_occ == 2;   // (nk_dev_tune, NK_TUNE_ATTENTION_OCC: sweeps only)
+    // (the causal kernels have no two-block variant: the knob is a sweep tool and every instantiation is compile time)
+    const bool occ2 = !CAUSAL && !BWD && DH != 128 && dev->tune_attn_occ == 2;   // (nk_dev_tune, NK_TUNE_ATTENTION_OCC: sweeps only)
 #define NK_ATT(M, F, R)                                                                                                    \
     do {                                                                                                                   \
         /* inference forward: KEEP = false (spelled `BWD`, false on the only path that reaches this line) */             \
-        if (!BWD && !a.scores) hipLaunchKernelGGL((attention_kernel<BWD, M, F, OCC_DEFAULT, BWD, DH, R>), grid, block, 0, dev->compute, a); \
-        else if (occ2) hipLaunchKernelGGL((attention_kernel<BWD, M, F, (DH == 128 ? 1 : 2), true, DH, R>), grid, block, 0, dev->compute, a); \
-        else hipLaunchKernelGGL((attention_kernel<BWD, M, F, OCC_DEFAULT, true, DH, R>), grid, block, 0, dev->compute, a);    \
+        if (!BWD && !a.scores) hipLaunchKernelGGL((attention_kernel<BWD, M, F, OCC_DEFAULT, BWD, DH, R, CAUSAL>), grid, block, 0, dev->compute, a); \
+        else if (occ2) hipLaunchKernelGGL((attention_kernel<BWD, M, F, (DH == 128 || CAUSAL ? OCC_DEFAULT : 2), true, DH, R, CAUSAL>), grid, block, 0, dev->compute, a); \
+        else hipLaunchKernelGGL((attention_kernel<BWD, M, F, OCC_DEFAULT, true, DH, R, CAUSAL>), grid, block, 0, dev->compute, a);    \
     } while (0)
     if (ragged) { if (masked) NK_ATT(true, false, true); else NK_ATT(false, false, true); }
     else if (masked && full) NK_ATT(true, true, false);
@@ -489,11 +368,21 @@ int attention_launch_dh(nk_device* dev, AttnArgs& a, int B, int S, int H, double
     return NK_OK;
 }
 
+template <bool BWD, bool CAUSAL>
+int attention_launch_c(nk_device* dev, AttnArgs& a, int B, int S, int H, int dh, double p, int train, uint64_t seed, uint64_t offset, float scale) {
+    if (dh == 32) return attention_launch_dh<BWD, 32, CAUSAL>(dev, a, B, S, H, p, train, seed, offset, scale);
+    if (dh == 128) return attention_launch_dh<BWD, 128, CAUSAL>(dev, a, B, S, H, p, train, seed, offset, scale);
+    return attention_launch_dh<BWD, 64, CAUSAL>(dev, a, B, S, H, p, train, seed, offset, scale);
+}
 template <bool BWD>
-int attention_launch(nk_device* dev, AttnArgs& a, int B, int S, int H, int dh, double p, int train, uint64_t seed, uint64_t offset, float scale) {
-    if (dh == 32) return attention_launch_dh<BWD, 32>(dev, a, B, S, H, p, train, seed, offset, scale);
-    if (dh == 128) return attention_launch_dh<BWD, 128>(dev, a, B, S, H, p, train, seed, offset, scale);
-    return attention_launch_dh<BWD, 64>(dev, a, B, S, H, p, train, seed, offset, scale);
+int attention_launch(nk_device* dev, AttnArgs& a, bool causal, int B, int S, int H, int dh, double p, int train, uint64_t seed, uint64_t offset,
+                     float scale) {
+    return causal ? attention_launch_c<BWD, true>(dev, a, B, S, H, dh, p, train, seed, offset, scale)
+                  : attention_launch_c<BWD, false>(dev, a, B, S, H, dh, p, train, seed, offset, scale);
+}
+// algorithmic flops of one direction's two products: all S*S (query, key) pairs, or the S*(S+1)/2 on and below the diagonal
+double attention_flops(bool causal, int B, int S, int H, int dh) {
+    return causal ? 2.0 * B * H * dh * (double)S * (S + 1) : 4.0 * B * H * (double)S * S * dh;
 }
 
 }  // namespace
@@ -504,7 +393,7 @@ int nk_attention_supported(int S, int dh, double p, int train) {
     return (dh == 32 || dh == 64 || dh == 128) && S > 0 && !(train && 1.0 - p == 0.0);
 }
 
-static int attention_fwd_impl(nk_device* dev, const float* Q, const float* K, const float* V, int ld_qkv, float* scores, float* stats,
+static int attention_fwd_impl(nk_device* dev, bool causal, const float* Q, const float* K, const float* V, int ld_qkv, float* scores, float* stats,
                               uint32_t* mask_bits, float* O, int B, int S, int H, int dh, float scale, double p, int train, uint64_t seed,
                               uint64_t offset) {
     NK_USE(dev);
@@ -514,27 +403,41 @@ static int attention_fwd_impl(nk_device* dev, const float* Q, const float* K, co
     NK_CHECK(!scores || mask_bits || !(train && p != 0.0), "nk_attention_fwd: dropout is active, the mask_bits buffer is needed");
     NK_CHECK(al16(Q) && al16(K) && al16(V) && al16(scores) && al16(O) && al16(stats), "nk_attention_fwd needs 16-byte aligned buffers");
     NK_CHECK((long long)B * S * ld_qkv < (1ll << 31), "attention: the packed projection layout exceeds 2^31 elements");
-    nk_prof_start(dev, NK_KERNEL_ATTENTION, 4.0 * B * H * (double)S * S * dh);
+    nk_prof_start(dev, NK_KERNEL_ATTENTION, attention_flops(causal, B, S, H, dh));
     AttnArgs a{};
     a.x1 = K; a.x2 = V; a.bq = Q; a.out = O; a.scores = scores; a.stats = stats; a.maskbits = mask_bits;
     a.ldx = ld_qkv; a.ldq = ld_qkv; a.ldc = H * dh; a.ldo = H * dh;
-    const int rc = attention_launch<false>(dev, a, B, S, H, dh, p, train, seed, offset, scale);
+    const int rc = attention_launch<false>(dev, a, causal, B, S, H, dh, p, train, seed, offset, scale);
     nk_prof_stop(dev);
     return rc;
 }
 int nk_attention_fwd(nk_device* dev, const float* Q, const float* K, const float* V, float* scores, float* stats,
                      uint32_t* mask_bits, float* O, int B, int S, int H, int dh, float scale, double p, int train, uint64_t seed,
                      uint64_t offset) {
-    return attention_fwd_impl(dev, Q, K, V, H * dh, scores, stats, mask_bits, O, B, S, H, dh, scale, p, train, seed, offset);
+    return attention_fwd_impl(dev, false, Q, K, V, H * dh, scores, stats, mask_bits, O, B, S, H, dh, scale, p, train, seed, offset);
+}
+int nk_attention_causal_fwd(nk_device* dev, const float* Q, const float* K, const float* V, float* scores, float* stats,
+                            uint32_t* mask_bits, float* O, int B, int S, int H, int dh, float scale, double p, int train, uint64_t seed,
+                            uint64_t offset) {
+    return attention_fwd_impl(dev, true, Q, K, V, H * dh, scores, stats, mask_bits, O, B, S, H, dh, scale, p, train, seed, offset);
+}
+static int attention_qkv_fwd_impl(nk_device* dev, bool causal, const float* QKV, float* scores, float* stats, uint32_t* mask_bits, float* O,
+                                  int B, int S, int H, int dh, float scale, double p, int train, uint64_t seed, uint64_t offset) {
+    NK_CHECK(QKV != nullptr, "null pointer in nk_attention_qkv_fwd");
+    const int d = H * dh;
+    return attention_fwd_impl(dev, causal, QKV, QKV + d, QKV + 2 * d, 3 * d, scores, stats, mask_bits, O, B, S, H, dh, scale, p, train, seed,
+                              offset);
 }
 int nk_attention_qkv_fwd(nk_device* dev, const float* QKV, float* scores, float* stats, uint32_t* mask_bits, float* O, int B, int S,
                          int H, int dh, float scale, double p, int train, uint64_t seed, uint64_t offset) {
-    NK_CHECK(QKV != nullptr, "null pointer in nk_attention_qkv_fwd");
-    const int d = H * dh;
-    return attention_fwd_impl(dev, QKV, QKV + d, QKV + 2 * d, 3 * d, scores, stats, mask_bits, O, B, S, H, dh, scale, p, train, seed, offset);
+    return attention_qkv_fwd_impl(dev, false, QKV, scores, stats, mask_bits, O, B, S, H, dh, scale, p, train, seed, offset);
+}
+int nk_attention_qkv_causal_fwd(nk_device* dev, const float* QKV, float* scores, float* stats, uint32_t* mask_bits, float* O, int B, int S,
+                                int H, int dh, float scale, double p, int train, uint64_t seed, uint64_t offset) {
+    return attention_qkv_fwd_impl(dev, true, QKV, scores, stats, mask_bits, O, B, S, H, dh, scale, p, train, seed, offset);
 }
 
-static int attention_bwd_impl(nk_device* dev, float* dQ, float* dK, float* dV, float* dS, float* dropped, const float* dO, const float* O,
+static int attention_bwd_impl(nk_device* dev, bool causal, float* dQ, float* dK, float* dV, float* dS, float* dropped, const float* dO, const float* O,
                               const float* scores, const float* stats, const uint32_t* mask_bits, const float* Q, const float* K,
                               const float* V, int ld_qkv, int B, int S, int H, int dh, float scale, double p, int train, int assign_dq,
                               int assign_dk, int assign_dv) {
@@ -546,12 +449,12 @@ static int attention_bwd_impl(nk_device* dev, float* dQ, float* dK, float* dV, f
                  al16(Q) && al16(K) && al16(V),
              "nk_attention_bwd needs 16-byte aligned buffers");
     NK_CHECK((long long)B * S * ld_qkv < (1ll << 31), "attention: the packed projection layout exceeds 2^31 elements");
-    nk_prof_start(dev, NK_KERNEL_ATTENTION, 4.0 * B * H * (double)S * S * dh);
+    nk_prof_start(dev, NK_KERNEL_ATTENTION, attention_flops(causal, B, S, H, dh));
     AttnArgs a{};
     a.x1 = V; a.x2 = K; a.bq = dO; a.ctx = O; a.out = dQ; a.scores = const_cast<float*>(scores); a.ds = dS; a.dropped = dropped;
     a.stats = const_cast<float*>(stats); a.maskbits = const_cast<uint32_t*>(mask_bits); a.assign = assign_dq ? 1 : 0;
     a.ldx = ld_qkv; a.ldq = H * dh; a.ldc = H * dh; a.ldo = ld_qkv;
-    int rc = attention_launch<true>(dev, a, B, S, H, dh, p, train, 0, 0, scale);
+    int rc = attention_launch<true>(dev, a, causal, B, S, H, dh, p, train, 0, 0, scale);
     nk_prof_stop(dev);
     if (rc) return rc;
     // dK_bh (+)= dS_bh^T . Q_bh and dV_bh (+)= Pd_bh^T . dO_bh: reductions over the queries, i.e. across the blocks above.
@@ -559,6 +462,21 @@ static int attention_bwd_impl(nk_device* dev, float* dQ, float* dK, float* dV, f
     // 128 x 32 tiles are single 16 KB runs for these products - was built and measured: kernel and products unchanged.)
     const int d = H * dh, SP = (S + 31) / 32 * 32;  // row stride of the scratch tensors (== S unless S is ragged)
     const long long so = (long long)S * d, sq = (long long)S * ld_qkv, po = (long long)H * SP * SP, pi = (long long)SP * SP;
+    // Causal: dS and Pd are defined on the 128 x 128 blocks that touch or lie below the diagonal and UNDEFINED above (the kernel never
+    // visits those tiles; garbage times zero is NaN), so the key strip [128 j, 128 j + 128) reduces over the queries >= 128 j only: one
+    // pair of products per strip with A, B and C advanced to (128 j, 128 j) and K = S - 128 j.  S / 128 launches of B*H (pairs of)
+    // blocks; the chained-launch rule for reductions longer than 2048 products is nk_sgemm's own and applies per strip.
+    if (causal) {
+        for (int j0 = 0; j0 < S; j0 += A_QB) {
+            const int m = S - j0 < A_QB ? S - j0 : A_QB, k = S - j0;
+            const long long da = (long long)j0 * SP + j0, dq = (long long)j0 * ld_qkv, dd = (long long)j0 * d;
+            rc = nk_sgemm_pair_batched(dev, B, H, 1, 0, m, dh, k, dS + da, SP, po, pi, Q + dq, ld_qkv, sq, dh, assign_dk ? 0.f : 1.f, dK + dq,
+                                       ld_qkv, sq, dh, 1, 0, m, dh, k, dropped + da, SP, po, pi, dO + dd, d, so, dh, assign_dv ? 0.f : 1.f,
+                                       dV + dq, ld_qkv, sq, dh);
+            if (rc) return rc;
+        }
+        return NK_OK;
+    }
     // (one launch for both when nk_sgemm_pair's rule says so: the two grids share their last wave of resident blocks)
     return nk_sgemm_pair_batched(dev, B, H, 1, 0, S, dh, S, dS, SP, po, pi, Q, ld_qkv, sq, dh, assign_dk ? 0.f : 1.f, dK, ld_qkv, sq, dh,
                                  1, 0, S, dh, S, dropped, SP, po, pi, dO, d, so, dh, assign_dv ? 0.f : 1.f, dV, ld_qkv, sq, dh);
@@ -567,16 +485,33 @@ int nk_attention_bwd(nk_device* dev, float* dQ, float* dK, float* dV, float* dS,
                      const float* scores, const float* stats, const uint32_t* mask_bits, const float* Q, const float* K,
                      const float* V, int B, int S, int H, int dh, float scale, double p, int train, int assign_dq, int assign_dk,
                      int assign_dv) {
-    return attention_bwd_impl(dev, dQ, dK, dV, dS, dropped, dO, O, scores, stats, mask_bits, Q, K, V, H * dh, B, S, H, dh, scale, p, train,
+    return attention_bwd_impl(dev, false, dQ, dK, dV, dS, dropped, dO, O, scores, stats, mask_bits, Q, K, V, H * dh, B, S, H, dh, scale, p, train,
                               assign_dq, assign_dk, assign_dv);
+}
+int nk_attention_causal_bwd(nk_device* dev, float* dQ, float* dK, float* dV, float* dS, float* dropped, const float* dO, const float* O,
+                            const float* scores, const float* stats, const uint32_t* mask_bits, const float* Q, const float* K,
+                            const float* V, int B, int S, int H, int dh, float scale, double p, int train, int assign_dq, int assign_dk,
+                            int assign_dv) {
+    return attention_bwd_impl(dev, true, dQ, dK, dV, dS, dropped, dO, O, scores, stats, mask_bits, Q, K, V, H * dh, B, S, H, dh, scale, p, train,
+                              assign_dq, assign_dk, assign_dv);
+}
+static int attention_qkv_bwd_impl(nk_device* dev, bool causal, float* dQKV, float* dS, float* dropped, const float* dO, const float* O,
+                                  const float* scores, const float* stats, const uint32_t* mask_bits, const float* QKV, int B, int S, int H,
+                                  int dh, float scale, double p, int train, int assign) {
+    NK_CHECK(dQKV && QKV, "null pointer in nk_attention_qkv_bwd");
+    const int d = H * dh;
+    return attention_bwd_impl(dev, causal, dQKV, dQKV + d, dQKV + 2 * d, dS, dropped, dO, O, scores, stats, mask_bits, QKV, QKV + d, QKV + 2 * d,
+                              3 * d, B, S, H, dh, scale, p, train, assign, assign, assign);
 }
 int nk_attention_qkv_bwd(nk_device* dev, float* dQKV, float* dS, float* dropped, const float* dO, const float* O, const float* scores,
                          const float* stats, const uint32_t* mask_bits, const float* QKV, int B, int S, int H, int dh, float scale,
                          double p, int train, int assign) {
-    NK_CHECK(dQKV && QKV, "null pointer in nk_attention_qkv_bwd");
-    const int d = H * dh;
-    return attention_bwd_impl(dev, dQKV, dQKV + d, dQKV + 2 * d, dS, dropped, dO, O, scores, stats, mask_bits, QKV, QKV + d, QKV + 2 * d, 3 * d,
-                              B, S, H, dh, scale, p, train, assign, assign, assign);
+    return attention_qkv_bwd_impl(dev, false, dQKV, dS, dropped, dO, O, scores, stats, mask_bits, QKV, B, S, H, dh, scale, p, train, assign);
+}
+int nk_attention_qkv_causal_bwd(nk_device* dev, float* dQKV, float* dS, float* dropped, const float* dO, const float* O, const float* scores,
+                                const float* stats, const uint32_t* mask_bits, const float* QKV, int B, int S, int H, int dh, float scale,
+                                double p, int train, int assign) {
+    return attention_qkv_bwd_impl(dev, true, dQKV, dS, dropped, dO, O, scores, stats, mask_bits, QKV, B, S, H, dh, scale, p, train, assign);
 }
 
 }  // extern "C"
