@@ -995,6 +995,105 @@ BackwardEntry entry(Shared<Op> op, Shared<Gradient> grad) {
     return BackwardEntry{std::move(op), std::move(grad)};
 }
 
+// Layer normalisation over the trailing dimensions (ours; the reference has no such node): x read as (rows, dim).  The forward
+// node owns `stats` = per-row {mean, rstd}, which the backward node reads; the no-gradient form keeps none.
+struct LayerNormFwd : Forward {
+    Shared<HipArray> x, gamma, beta, y, stats;  // gamma / beta null: no affine part; stats null: nothing kept for a backward pass
+    long long rows;
+    int dim;
+    double eps;
+    void forward() const override {
+        check(nk_layer_norm_fwd(D(x), x->ptr(), gamma ? gamma->ptr() : nullptr, beta ? beta->ptr() : nullptr, y->ptr(),
+                                stats ? stats->ptr() : nullptr, rows, dim, eps));
+    }
+};
+// ONE backward entry for up to three gradients: dgamma and dbeta leave one pass over (g, x, stats) together, dx its own.  Each
+// target is written only if that operand is differentiable, each through its own first-writer-assigns state.
+struct LayerNormBwd : Backward {
+    Shared<Gradient> dx, dgamma, dbeta, g;  // any of the three targets may be null
+    Shared<HipArray> x, gamma, stats;
+    long long rows;
+    int dim;
+    void backward() const override {
+        const HipArray& G = g->borrow();
+        nk_device* dev = D(x);
+        bool ag = false, ab = false;
+        float* pg = dgamma ? dgamma->borrow_first_write(ag).ptr() : nullptr;
+        float* pb = dbeta ? dbeta->borrow_first_write(ab).ptr() : nullptr;
+        auto params = [&](float* a, float* b, bool assign) {
+            check((assign ? nk_layer_norm_bwd_params_assign : nk_layer_norm_bwd_params)(dev, a, b, G.ptr(), x->ptr(), stats->ptr(), rows, dim));
+        };
+        if (pg && pb && ag != ab) {  // one gradient already written in this pass (a shared parameter), the other not
+            params(pg, nullptr, ag);
+            params(nullptr, pb, ab);
+        } else if (pg || pb) {
+            params(pg, pb, pg ? ag : ab);
+        }
+        if (dx) {
+            bool assign = false;
+            HipArray& d = dx->borrow_first_write(assign);
+            check((assign ? nk_layer_norm_bwd_assign : nk_layer_norm_bwd)(dev, d.ptr(), G.ptr(), x->ptr(), gamma ? gamma->ptr() : nullptr,
+                                                                          stats->ptr(), rows, dim));
+        }
+    }
+    void targets(std::vector<const Gradient*>& out) const override {
+        if (dgamma) out.push_back(dgamma.get());
+        if (dbeta) out.push_back(dbeta.get());
+        if (dx) out.push_back(dx.get());
+    }
+};
+
+// the normalised extent: `ns` must be the trailing dimensions of `xs`
+int layer_norm_dim(const Shape& xs, const Shape& ns) {
+    if (ns.empty() || ns.size() > xs.size() || !std::equal(ns.rbegin(), ns.rend(), xs.rbegin()))
+        panic("layer_norm: normalized_shape must equal the trailing dimensions of the input");
+    const size_t d = numel(ns);
+    if (d == 0 || d > (size_t)1 << 30) panic("layer_norm: the normalised extent must be in 1 .. 2^30");
+    return (int)d;
+}
+Shared<LayerNormFwd> layer_norm_fwd_node(const Var& x, const Var* gamma, const Var* beta, const Shape& ns, double eps, bool keep_stats) {
+    if (gamma && gamma->shape() != ns) panic("layer_norm: gamma must have the normalised shape");
+    if (beta && beta->shape() != ns) panic("layer_norm: beta must have the normalised shape");
+    if (!(eps >= 0.0) || !std::isfinite(eps)) panic("layer_norm: eps must be finite and not negative");
+    auto n = std::make_shared<LayerNormFwd>();
+    n->dim = layer_norm_dim(x.shape(), ns);
+    n->rows = (long long)(x.data->len() / (size_t)n->dim);
+    if (keep_stats && n->rows > (1ll << 30)) panic("layer_norm: too many rows");
+    n->x = x.data; n->gamma = gamma ? gamma->data : nullptr; n->beta = beta ? beta->data : nullptr;
+    n->y = zeros_like(x.data, x.shape());
+    if (keep_stats) n->stats = zeros_like(x.data, Shape{(int)n->rows, 2});
+    n->eps = eps;
+    return n;
+}
+Var layer_norm_var(const Var& x, const Var* gamma, const Var* beta, const Shape& ns, double eps) {
+    History<ForwardEntry> h = x.history;
+    if (gamma) h.merge(gamma->history);
+    if (beta) h.merge(beta->history);
+    auto n = layer_norm_fwd_node(x, gamma, beta, ns, eps, false);
+    auto y = n->y;
+    return Var::node(y, n, std::move(h));
+}
+// x, gamma, beta with their gradients and tapes where differentiable (null otherwise); at least one gradient is not null
+VarDiff layer_norm_diff(const Var& x, const Shared<Gradient>& dx, const History<BackwardEntry>* hx, const Var* gamma,
+                        const Shared<Gradient>& dgamma, const History<BackwardEntry>* hg, const Var* beta,
+                        const Shared<Gradient>& dbeta, const History<BackwardEntry>* hb, const Shape& ns, double eps) {
+    History<ForwardEntry> fh = x.history;
+    if (gamma) fh.merge(gamma->history);
+    if (beta) fh.merge(beta->history);
+    auto n = layer_norm_fwd_node(x, gamma, beta, ns, eps, true);
+    auto y = n->y;
+    Var var = Var::node(y, n, std::move(fh));
+    History<BackwardEntry> h;
+    if (hx) h = *hx;
+    if (hg) h.merge(*hg);
+    if (hb) h.merge(*hb);
+    auto grad = std::make_shared<Gradient>(var.device(), var.shape());
+    auto bw = std::make_shared<LayerNormBwd>();
+    bw->dx = dx; bw->dgamma = dgamma; bw->dbeta = dbeta; bw->g = grad;
+    bw->x = x.data; bw->gamma = n->gamma; bw->stats = n->stats; bw->rows = n->rows; bw->dim = n->dim;
+    return VarDiff::node(std::move(var), grad, entry(bw, grad), std::move(h));
+}
+
 Shape mm_shape(const Shape& a, const Shape& b, int kind) {  // utils.rs:46-55 `DotDim`
     if (kind == 4) {
         if (a.size() != 2 || b.size() != 1) panic("mv: matrix and vector expected");
@@ -1166,6 +1265,11 @@ Var Var::unsqueeze(int axis) const {
 Var Var::softmax(int axis) const { check_axis(shape(), axis); return unary_var(Unary::Softmax, axis, *this, shape()); }
 Var Var::log_softmax(int axis) const { check_axis(shape(), axis); return unary_var(Unary::LogSoftmax, axis, *this, shape()); }
 Var Var::t() const { return unary_var(Unary::Transpose, 0, *this, Shape(shape().rbegin(), shape().rend())); }
+Var Var::layer_norm(const Var& gamma, const Var& beta, double eps) const { return layer_norm_var(*this, &gamma, &beta, gamma.shape(), eps); }
+Var Var::layer_norm(const Shape& normalized_shape, double eps) const { return layer_norm_var(*this, nullptr, nullptr, normalized_shape, eps); }
+VarDiff Var::layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps) const {
+    return layer_norm_diff(*this, nullptr, nullptr, &gamma.var, gamma.grad, &gamma.history, &beta.var, beta.grad, &beta.history, gamma.shape(), eps);
+}
 Var Var::dropout(double p, Shared<bool> status) const {
     if (!(p >= 0.0 && p <= 1.0)) panic("Wrong probability received: " + std::to_string(p) + ".");
     auto op = std::make_shared<DropoutFwd>();
@@ -1572,6 +1676,15 @@ VarDiff VarDiff::unsqueeze(int axis) const {
 VarDiff VarDiff::softmax(int axis) const { check_axis(shape(), axis); return unary_diff(Unary::Softmax, axis, *this, shape()); }
 VarDiff VarDiff::log_softmax(int axis) const { check_axis(shape(), axis); return unary_diff(Unary::LogSoftmax, axis, *this, shape()); }
 VarDiff VarDiff::t() const { return unary_diff(Unary::Transpose, 0, *this, Shape(shape().rbegin(), shape().rend())); }
+VarDiff VarDiff::layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps) const {
+    return layer_norm_diff(var, grad, &history, &gamma.var, gamma.grad, &gamma.history, &beta.var, beta.grad, &beta.history, gamma.shape(), eps);
+}
+VarDiff VarDiff::layer_norm(const Var& gamma, const Var& beta, double eps) const {
+    return layer_norm_diff(var, grad, &history, &gamma, nullptr, nullptr, &beta, nullptr, nullptr, gamma.shape(), eps);
+}
+VarDiff VarDiff::layer_norm(const Shape& normalized_shape, double eps) const {
+    return layer_norm_diff(var, grad, &history, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, normalized_shape, eps);
+}
 VarDiff VarDiff::dropout(double p, Shared<bool> status) const {
     Var v = var.dropout(p, status);
     // the forward node owns the noise buffer; share it with the backward node (var.rs:375-393)
@@ -1893,6 +2006,25 @@ void xavier_normal(const VarDiff& p, float gain, uint64_t seed) {
 Linear::Linear(DevicePtr dev, int in_features, int out_features, uint64_t seed)
     : weight(uniform_param(dev, {out_features, in_features}, 1.f / std::sqrt((float)in_features), seed)),
       bias(uniform_param(dev, {out_features}, 1.f / std::sqrt((float)in_features), seed + 1)) {}
+LayerNorm::LayerNorm(DevicePtr dev, Shape normalized_shape, double eps, bool elementwise_affine)
+    : normalized_shape(std::move(normalized_shape)), eps(eps), elementwise_affine(elementwise_affine) {
+    if (this->normalized_shape.empty() || numel(this->normalized_shape) == 0) panic("LayerNorm: normalized_shape must not be empty");
+    if (elementwise_affine) {
+        weight = ones(dev, this->normalized_shape).requires_grad();
+        bias = zeros(dev, this->normalized_shape).requires_grad();
+    }
+}
+LayerNorm::LayerNorm(VarDiff w, VarDiff b, double eps) : weight(std::move(w)), bias(std::move(b)), normalized_shape(weight.shape()), eps(eps) {
+    if (bias.shape() != normalized_shape) panic("LayerNorm: weight and bias must have the same shape");
+}
+VarDiff LayerNorm::forward(const Var& input) const {
+    if (!elementwise_affine) panic("LayerNorm without affine parameters on a Var input has nothing to differentiate: use Var::layer_norm(normalized_shape, eps)");
+    return input.layer_norm(weight, bias, eps);
+}
+VarDiff LayerNorm::forward(const VarDiff& input) const {
+    return elementwise_affine ? input.layer_norm(weight, bias, eps) : input.layer_norm(normalized_shape, eps);
+}
+
 static VarDiff linear_node(const Linear& l, const Var& x, const Shared<Gradient>& dx, const History<BackwardEntry>* hx, bool relu = false) {
     const Shape& xs = x.shape();
     const Shape& ws = l.weight.shape();
@@ -2302,6 +2434,15 @@ nn::Linear linear_from_json(DevicePtr dev, const Json& j) {
     return nn::Linear(vardiff_from_json(dev, j.at("weight")), vardiff_from_json(dev, j.at("bias")));
 }
 nn::Linear linear_from_json(DevicePtr dev, const std::string& text) { return linear_from_json(std::move(dev), parse(text)); }
+
+std::string to_json(const nn::LayerNorm& l) {
+    if (!l.elementwise_affine) panic("serde: a LayerNorm without affine parameters has nothing to serialise");
+    return "{\"weight\":" + to_json(l.weight) + ",\"bias\":" + to_json(l.bias) + "}";
+}
+nn::LayerNorm layer_norm_from_json(DevicePtr dev, const Json& j, double eps) {
+    return nn::LayerNorm(vardiff_from_json(dev, j.at("weight")), vardiff_from_json(dev, j.at("bias")), eps);
+}
+nn::LayerNorm layer_norm_from_json(DevicePtr dev, const std::string& text, double eps) { return layer_norm_from_json(std::move(dev), parse(text), eps); }
 
 }  // namespace serde
 

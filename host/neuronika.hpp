@@ -300,6 +300,12 @@ class Var {
     Var softmax(int axis) const;                      // var.rs:318
     Var log_softmax(int axis) const;                  // var.rs:338
     Var t() const;                                    // var.rs:347
+    // Layer normalisation over the trailing dimensions (ours: the reference has none; semantics in neuronika_hip.h).  The
+    // normalised shape is gamma's (beta's must equal it), or `normalized_shape` without affine parameters.  The Var forms keep
+    // no statistics; with differentiable parameters the result is differentiable in them alone.
+    Var layer_norm(const Var& gamma, const Var& beta, double eps = 1e-5) const;
+    Var layer_norm(const Shape& normalized_shape, double eps = 1e-5) const;
+    VarDiff layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps = 1e-5) const;
     Var dropout(double p, Shared<bool> status) const; // var.rs:375
     std::vector<Var> chunks(const Shape& chunk_size) const;             // var.rs:401
     Var cat(const std::vector<Var>& variables, int axis) const;         // var.rs:564
@@ -406,6 +412,10 @@ class VarDiff {
     VarDiff softmax(int axis) const;
     VarDiff log_softmax(int axis) const;
     VarDiff t() const;
+    // one forward and ONE backward entry; gradients flow to self and, independently, to gamma and beta where differentiable
+    VarDiff layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps = 1e-5) const;
+    VarDiff layer_norm(const Var& gamma, const Var& beta, double eps = 1e-5) const;
+    VarDiff layer_norm(const Shape& normalized_shape, double eps = 1e-5) const;
     VarDiff dropout(double p, Shared<bool> status) const;
     std::vector<VarDiff> chunks(const Shape& chunk_size) const;
     VarDiff cat(const std::vector<VarDiff>& vars, int axis) const;
@@ -526,6 +536,21 @@ struct LinearOrigin {
 // Graph-build peephole `forward(x).relu()` -> the Linear+ReLU node (on by default, per thread; off: the ReLU node over the
 // Linear's output, as the tests that pit the two graphs against each other bit for bit need it).  Returns the old setting.
 bool set_relu_peephole(bool on);
+
+// Layer normalisation over the trailing `normalized_shape` of the input (ours: the reference has no normalisation layer):
+// y = (x - mean) / sqrt(var + eps) * weight + bias per row, biased variance.  weight = ones, bias = zeros, both of
+// `normalized_shape`, ordinary leaves for the optimizers; without `elementwise_affine` there are no parameters (weight and bias
+// stay empty) and y = xhat.
+struct LayerNorm {
+    VarDiff weight, bias;
+    Shape normalized_shape;
+    double eps = 1e-5;
+    bool elementwise_affine = true;
+    LayerNorm(DevicePtr dev, Shape normalized_shape, double eps = 1e-5, bool elementwise_affine = true);
+    LayerNorm(VarDiff weight, VarDiff bias, double eps = 1e-5);  // parameters built elsewhere (e.g. deserialised)
+    VarDiff forward(const Var& input) const;  // differentiable in the parameters: needs elementwise_affine
+    VarDiff forward(const VarDiff& input) const;
+};
 
 // `LSTMCell` neuronika-nn/src/lib.rs:453-541.  Weights (4H,in)/(4H,H), biases (4H), U(-k,k), k = 1/sqrt(H).
 // `forward` keeps the reference's exact composition: state = (cell_state, hidden); gate chunks 0..3 get
@@ -678,6 +703,9 @@ VarDiff vardiff_from_json(DevicePtr dev, const std::string& text);
 std::string to_json(const nn::Linear& l);
 nn::Linear linear_from_json(DevicePtr dev, const Json& j);
 nn::Linear linear_from_json(DevicePtr dev, const std::string& text);
+std::string to_json(const nn::LayerNorm& l);  // {"weight":..., "bias":...}; eps is not part of the wire format
+nn::LayerNorm layer_norm_from_json(DevicePtr dev, const Json& j, double eps = 1e-5);
+nn::LayerNorm layer_norm_from_json(DevicePtr dev, const std::string& text, double eps = 1e-5);
 
 }  // namespace serde
 

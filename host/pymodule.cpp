@@ -66,6 +66,9 @@ PYBIND11_MODULE(_tape, m) {
         .def("softplus", &Var::softplus).def("sigmoid", &Var::sigmoid).def("tanh", &Var::tanh).def("ln", &Var::ln)
         .def("exp", &Var::exp).def("unsqueeze", &Var::unsqueeze)
         .def("softmax", &Var::softmax).def("log_softmax", &Var::log_softmax).def("t", &Var::t)
+        .def("layer_norm", py::overload_cast<const Var&, const Var&, double>(&Var::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
+        .def("layer_norm", py::overload_cast<const VarDiff&, const VarDiff&, double>(&Var::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
+        .def("layer_norm", py::overload_cast<const Shape&, double>(&Var::layer_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-5)
         .def("dropout", [](const Var& v, double p, const Status& s) { return v.dropout(p, s.flag); }).def("chunks", &Var::chunks).def("cat", &Var::cat)
         .def("mse", &Var::mse).def("mae", &Var::mae).def("bce", &Var::bce).def("bce_with_logits", &Var::bce_with_logits)
         .def("kldiv", &Var::kldiv).def("nll", &Var::nll).def("stack", &Var::stack)
@@ -129,6 +132,9 @@ PYBIND11_MODULE(_tape, m) {
         .def("softplus", &VarDiff::softplus).def("sigmoid", &VarDiff::sigmoid).def("tanh", &VarDiff::tanh).def("ln", &VarDiff::ln)
         .def("exp", &VarDiff::exp).def("unsqueeze", &VarDiff::unsqueeze)
         .def("softmax", &VarDiff::softmax).def("log_softmax", &VarDiff::log_softmax).def("t", &VarDiff::t)
+        .def("layer_norm", py::overload_cast<const VarDiff&, const VarDiff&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
+        .def("layer_norm", py::overload_cast<const Var&, const Var&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
+        .def("layer_norm", py::overload_cast<const Shape&, double>(&VarDiff::layer_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-5)
         .def("dropout", [](const VarDiff& v, double p, const Status& s) { return v.dropout(p, s.flag); }).def("chunks", &VarDiff::chunks).def("cat", &VarDiff::cat)
         .def("mse", &VarDiff::mse).def("mae", &VarDiff::mae).def("bce", &VarDiff::bce).def("bce_with_logits", &VarDiff::bce_with_logits)
         .def("kldiv", &VarDiff::kldiv).def("nll", &VarDiff::nll).def("stack", &VarDiff::stack)
@@ -248,6 +254,9 @@ PYBIND11_MODULE(_tape, m) {
     sd.def("var_from_json", py::overload_cast<DevicePtr, const std::string&>(&serde::var_from_json));
     sd.def("vardiff_from_json", py::overload_cast<DevicePtr, const std::string&>(&serde::vardiff_from_json));
     sd.def("linear_from_json", py::overload_cast<DevicePtr, const std::string&>(&serde::linear_from_json));
+    sd.def("to_json", py::overload_cast<const nn::LayerNorm&>(&serde::to_json));
+    sd.def("layer_norm_from_json", py::overload_cast<DevicePtr, const std::string&, double>(&serde::layer_norm_from_json), py::arg("dev"), py::arg("text"),
+           py::arg("eps") = 1e-5);
 
     py::module_ nn = m.def_submodule("nn");
     nn.def("set_relu_peephole", &nn::set_relu_peephole, py::arg("on"));
@@ -261,6 +270,18 @@ PYBIND11_MODULE(_tape, m) {
         .def("forward", py::overload_cast<const VarDiff&>(&nn::Linear::forward, py::const_))
         .def("forward_relu", py::overload_cast<const Var&>(&nn::Linear::forward_relu, py::const_))
         .def("forward_relu", py::overload_cast<const VarDiff&>(&nn::Linear::forward_relu, py::const_));
+    py::class_<nn::LayerNorm>(nn, "LayerNorm")
+        .def(py::init<DevicePtr, Shape, double, bool>(), py::arg("dev"), py::arg("normalized_shape"), py::arg("eps") = 1e-5,
+             py::arg("elementwise_affine") = true)
+        .def(py::init<VarDiff, VarDiff, double>(), py::arg("weight"), py::arg("bias"), py::arg("eps") = 1e-5)
+        // without affine parameters there is no weight and no bias: None
+        .def_property_readonly("weight", [](const nn::LayerNorm& l) { return l.elementwise_affine ? py::cast(l.weight) : py::object(py::none()); })
+        .def_property_readonly("bias", [](const nn::LayerNorm& l) { return l.elementwise_affine ? py::cast(l.bias) : py::object(py::none()); })
+        .def_readonly("normalized_shape", &nn::LayerNorm::normalized_shape)
+        .def_readwrite("eps", &nn::LayerNorm::eps)
+        .def_readonly("elementwise_affine", &nn::LayerNorm::elementwise_affine)
+        .def("forward", py::overload_cast<const Var&>(&nn::LayerNorm::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::LayerNorm::forward, py::const_));
     {
         py::module_ im = nn.def_submodule("init");
         im.def("calculate_gain", &nn::init::calculate_gain);

@@ -514,6 +514,34 @@ int nk_scale_softmax_dropout_bwd_from_scores(nk_device* dev, float* d_scores, co
                                              int L, float scale, double p, int train, uint64_t seed,
                                              uint64_t offset, int assign);
 
+/* ------------------------------------------------------------------ layer normalisation */
+/* LayerNorm over the trailing extent of a contiguous row-major tensor, read as (rows, D) with D the product of the
+ * normalised dimensions.  The reference has no such layer; the semantics are fixed here.  Per row, all in f32:
+ *   mean = sum(x) / D ;  var = sum((x - mean)^2) / D   (biased; a second pass over the centred values, not E[x^2] - mean^2)
+ *   rstd = 1 / sqrt(var + eps) ;  xhat = (x - mean) * rstd ;  y = xhat * gamma + beta     (gamma, beta of D elements)
+ * fwd overwrites y and, when `stats` is not NULL, writes stats[rows][2] = {mean, rstd}.  `gamma`, `beta` and `stats` may each be
+ * NULL (y = xhat * 1 + 0; nothing kept for a backward pass).  Every D in 1 .. 2^30 and every rows >= 0 is accepted; rows == 0
+ * returns NK_OK and writes nothing (in every entry point below, the _assign twins included).  D % 4 == 0 with 16-byte aligned
+ * pointers and D <= 16384 takes the kernels that keep the row in registers.  D = 1 gives y = beta; a constant row has var = 0
+ * and stays finite through eps; non-finite inputs propagate as the arithmetic produces them, inside their own row only.
+ * bwd, with gh = g * gamma (or g when gamma is NULL) and xhat recomputed from x and stats:
+ *   dx     += rstd * (gh - mean_D(gh) - xhat * mean_D(gh * xhat))
+ *   dgamma += sum over rows of g * xhat ;  dbeta += sum over rows of g        (either output may be NULL, not both)
+ * The parameter gradients are summed without atomics (per-row-block partial sums in the device workspace, then a fixed-order
+ * final sum whose order depends on (rows, D) alone): every result repeats bit for bit.  Nothing here synchronises or allocates
+ * beyond the workspace, so the calls can be captured into a graph.  The `_assign` twins write what their `+=` twin would leave in
+ * an all-zero destination, without reading it (see "first-write variants"). */
+int nk_layer_norm_fwd(nk_device* dev, const float* x, const float* gamma, const float* beta, float* y, float* stats,
+                      long long rows, int D, double eps);
+int nk_layer_norm_bwd(nk_device* dev, float* dx, const float* g, const float* x, const float* gamma, const float* stats,
+                      long long rows, int D);
+int nk_layer_norm_bwd_assign(nk_device* dev, float* dx, const float* g, const float* x, const float* gamma,
+                             const float* stats, long long rows, int D);
+int nk_layer_norm_bwd_params(nk_device* dev, float* dgamma, float* dbeta, const float* g, const float* x,
+                             const float* stats, long long rows, int D);
+int nk_layer_norm_bwd_params_assign(nk_device* dev, float* dgamma, float* dbeta, const float* g, const float* x,
+                                    const float* stats, long long rows, int D);
+
 /* ------------------------------------------------------------------ fused attention core ---
  * The composed multi-head attention's per-(sample, head) chain in one kernel per direction (SURVEY.md 8a note; the
  * composition is MatrixMatrixMulT node/matrix_matrix_mul_t/mod.rs:31-41, Multiplication node/multiplication/mod.rs:39-50,

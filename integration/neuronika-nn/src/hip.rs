@@ -77,6 +77,30 @@ impl Linear {
     }
 }
 
+/// Layer normalisation over the trailing dimensions `normalized_shape` of the input (the reference has no normalisation layer;
+/// semantics in `include/neuronika_hip.h`): `y = (x - mean) / sqrt(var + eps) * weight + bias` per row, biased variance.
+/// `weight` starts as ones, `bias` as zeros, both of `normalized_shape` (dimension `E`).
+pub struct LayerNorm<E: Dimension> {
+    pub weight: HipVarDiff<E>,
+    pub bias: HipVarDiff<E>,
+    pub eps: f64,
+}
+
+impl<E: Dimension + 'static> LayerNorm<E> {
+    pub fn new(normalized_shape: E, eps: f64, device: &Device) -> Self {
+        Self {
+            weight: HipVarDiff::parameter(&Array::ones(normalized_shape.clone()), device.clone()),
+            bias: HipVarDiff::parameter(&Array::zeros(normalized_shape), device.clone()),
+            eps,
+        }
+    }
+
+    /// ONE forward node (`nk_layer_norm_fwd`) and ONE backward entry (`nk_layer_norm_bwd`, `nk_layer_norm_bwd_params`).
+    pub fn forward<D: Dimension + 'static>(&self, input: HipVarDiff<D>) -> HipVarDiff<D> {
+        input.layer_norm(self.weight.clone(), self.bias.clone(), self.eps)
+    }
+}
+
 /// `ModelStatus`-style switch shared with the dropout nodes (`neuronika-nn/src/lib.rs:84-137`, `node/dropout/mod.rs:27`).
 pub struct Dropout {
     pub p: f64,

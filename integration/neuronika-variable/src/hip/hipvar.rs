@@ -18,7 +18,7 @@ use super::{
         AttentionState, BinaryOp, BinaryOperation, BinaryOperationBackwardLeft, BinaryOperationBackwardRight, Chunk, ChunkBackward,
         Convolution, ConvolutionBackwardInput, ConvolutionBackwardKernel, ConvolutionBackwardKernelBias, ConvolutionBackwardPadded, ConvolutionBias,
         ConvolutionBiasPadded, Dropout,
-        DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
+        DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, LayerNorm, LayerNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
         ReLUBackward, ReluMask, Softmax, SoftmaxBackward,
@@ -187,6 +187,26 @@ where
         let data = shared(self.data.borrow().dimension(), &self.device());
         let op = Softmax::new(self.data, data.clone(), axis);
         HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    /// Layer normalisation over the trailing dimensions, which must equal `gamma`'s shape (`beta`'s equals it): ours, the
+    /// reference has no normalisation node.  `stats` = the per-row `{mean, rstd}` buffer a backward node will read, `None` for
+    /// the no-gradient form (`layer_norm`).
+    pub(crate) fn layer_norm_with_stats<E: 'static + Dimension>(mut self, gamma: HipVar<E>, beta: HipVar<E>, eps: f64,
+                                                                 stats: Option<Shared<HipArray<Ix2>>>) -> HipVar<D> {
+        let (xs, ns) = (self.data.borrow().shape_c(), gamma.data.borrow().shape_c());
+        assert!(!ns.is_empty() && ns.len() <= xs.len() && xs[xs.len() - ns.len()..] == ns[..], "layer_norm: gamma must have the shape of the input's trailing dimensions");
+        assert!(beta.data.borrow().shape_c() == ns, "layer_norm: beta must have gamma's shape");
+        assert!(eps >= 0.0 && eps.is_finite(), "layer_norm: eps must be finite and not negative");
+        self.history.merge(gamma.history);
+        self.history.merge(beta.history);
+        let data = shared(self.data.borrow().dimension(), &self.device());
+        let op = LayerNorm::new(self.data, gamma.data, beta.data, data.clone(), stats, eps);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    pub fn layer_norm<E: 'static + Dimension>(self, gamma: HipVar<E>, beta: HipVar<E>, eps: f64) -> HipVar<D> {
+        self.layer_norm_with_stats(gamma, beta, eps, None)
     }
 
     /// `Var::log_softmax` (`var.rs:332-344`).
@@ -543,6 +563,21 @@ where
         let var = self.var.softmax(axis);
         let op = SoftmaxBackward::new(self.grad.clone(), var.data.clone(), grad.clone(), axis);
         HipVarDiff::node(var, grad.clone(), (Rc::new(op), grad), self.history)
+    }
+
+    /// Layer normalisation with differentiable parameters: ONE forward node and ONE backward entry writing the gradients of
+    /// `self`, `gamma` and `beta` (`LayerNormBackward`).
+    pub fn layer_norm<E: 'static + Dimension>(mut self, gamma: HipVarDiff<E>, beta: HipVarDiff<E>, eps: f64) -> HipVarDiff<D> {
+        self.history.merge(gamma.history);
+        self.history.merge(beta.history);
+        let (input_data, gamma_data) = (self.var.data.clone(), gamma.var.data.clone());
+        let rows = input_data.borrow().len() / gamma_data.borrow().len().max(1);
+        let stats = shared(Ix2(rows, 2), &self.var.device());
+        let grad = self.new_grad(self.grad.shape());
+        let var = self.var.layer_norm_with_stats(gamma.var, beta.var, eps, Some(stats.clone()));
+        let op: Rc<dyn Backward> = Rc::new(LayerNormBackward::new(input_data, gamma_data, stats, Some(self.grad.clone()), gamma.grad.clone(),
+                                                                   beta.grad.clone(), grad.clone()));
+        HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
     }
 
     /// `VarDiff::log_softmax` (`vardiff.rs:381-387`).

@@ -3,7 +3,7 @@
 //! reference's ndarray nodes (`node/*/mod.rs`), so graph construction code is unchanged.  Written here: the nodes of
 //! the BASELINE configurations (MatMul / MatMulT, Convolution, broadcast binaries, ReLU, Softmax, Dropout, Sum,
 //! SquaredError, the fused attention core of the composed MHA) and their glue (LogSoftmax, Mean, Pad in all four modes, Chunk,
-//! MultiConcatenate, Transpose, the SGD / Adam steps).  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
+//! MultiConcatenate, Transpose, the SGD / Adam steps) and the layer normalisation the reference lacks.  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
 mod attention;
 mod binary_op;
 mod convolution;
@@ -11,6 +11,7 @@ mod layout;
 mod linear;
 mod matrix_matrix_mul;
 mod matrix_matrix_mul_t;
+mod normalization;
 mod optim;
 mod pointwise;
 mod reduction;
@@ -22,6 +23,7 @@ pub(crate) use layout::*;
 pub(crate) use linear::*;
 pub(crate) use matrix_matrix_mul::*;
 pub(crate) use matrix_matrix_mul_t::*;
+pub(crate) use normalization::*;
 pub(crate) use optim::*;
 pub(crate) use pointwise::*;
 pub(crate) use reduction::*;

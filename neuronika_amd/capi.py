@@ -161,6 +161,11 @@ _SIGS = {
     "nk_softmax_bwd": [VP, VP, VP, VP, c_intp, C.c_int, C.c_int],
     "nk_log_softmax_fwd": [VP, VP, VP, c_intp, C.c_int, C.c_int],
     "nk_log_softmax_bwd": [VP, VP, VP, VP, c_intp, C.c_int, C.c_int],
+    "nk_layer_norm_fwd": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_double],
+    "nk_layer_norm_bwd": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
+    "nk_layer_norm_bwd_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
+    "nk_layer_norm_bwd_params": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
+    "nk_layer_norm_bwd_params_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
     "nk_attention_supported": [C.c_int, C.c_int, C.c_double, C.c_int],
     "nk_attention_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_attention_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double,
@@ -714,6 +719,21 @@ def log_softmax_fwd(dev, x, y, axis):
 
 def log_softmax_bwd(dev, dx, g, y, axis, assign=False):
     check((lib.nk_log_softmax_bwd_assign if assign else lib.nk_log_softmax_bwd)(dev.h, dx.p, g.p, y.p, y.shape_c(), y.ndim, axis))
+
+
+def layer_norm_fwd(dev, x, gamma, beta, y, stats, rows, D, eps=1e-5):
+    """x read as (rows, D); `gamma`, `beta`, `stats` (rows, 2) may be None"""
+    check(lib.nk_layer_norm_fwd(dev.h, _p(x), _p(gamma), _p(beta), _p(y), _p(stats), int(rows), int(D), float(eps)))
+
+
+def layer_norm_bwd(dev, dx, g, x, gamma, stats, rows, D, assign=False):
+    check((lib.nk_layer_norm_bwd_assign if assign else lib.nk_layer_norm_bwd)(dev.h, _p(dx), _p(g), _p(x), _p(gamma), _p(stats), int(rows), int(D)))
+
+
+def layer_norm_bwd_params(dev, dgamma, dbeta, g, x, stats, rows, D, assign=False):
+    """either of `dgamma`, `dbeta` may be None"""
+    check((lib.nk_layer_norm_bwd_params_assign if assign else lib.nk_layer_norm_bwd_params)(dev.h, _p(dgamma), _p(dbeta), _p(g), _p(x), _p(stats),
+                                                                                              int(rows), int(D)))
 
 
 def dropout_fwd(dev, x, y, noise, p, train=True, seed=0, offset=0):
