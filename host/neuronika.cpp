@@ -3,6 +3,7 @@
 // on the device's compute stream in tape order.
 #include "neuronika.hpp"
 
+#include <climits>
 #include <cstdlib>
 
 #include <algorithm>
@@ -1094,6 +1095,120 @@ VarDiff layer_norm_diff(const Var& x, const Shared<Gradient>& dx, const History<
     return VarDiff::node(std::move(var), grad, entry(bw, grad), std::move(h));
 }
 
+// Batch normalisation (ours; the reference has no such node): x read as (N, C, L), L the product of the extents behind the channel
+// axis.  The forward node reads `status` each time it runs on the host (as Dropout's does): training normalises with the batch
+// statistics and updates the running ones in place, inference normalises with the running ones.  Without running statistics the
+// batch statistics serve in both modes.  `stats` = per-channel {mean, rstd} for the backward node; the no-gradient form keeps none.
+struct BatchNormFwd : Forward {
+    Shared<HipArray> x, gamma, beta, running_mean, running_var, y, stats;  // gamma / beta, the running pair, stats: null when absent
+    int N, C, L;
+    double eps, momentum;
+    Shared<bool> status;
+    Shared<bool> trained = std::make_shared<bool>(true);  // the mode of the last forward run, for the backward node
+    void forward() const override {
+        *trained = *status || !running_mean;
+        auto p = [](const Shared<HipArray>& a) { return a ? a->ptr() : nullptr; };
+        if (*trained)
+            check(nk_batch_norm_fwd(D(x), x->ptr(), p(gamma), p(beta), y->ptr(), p(stats), p(running_mean), p(running_var), N, C, L, eps, momentum));
+        else
+            check(nk_batch_norm_infer_fwd(D(x), x->ptr(), p(gamma), p(beta), running_mean->ptr(), running_var->ptr(), y->ptr(), p(stats), N, C, L, eps));
+    }
+};
+// ONE backward entry for up to three gradients: one reduction pass leaves {sum g, sum g * xhat} per channel in `sums`, which dx (in
+// training) and both parameter gradients read.  Each target is written only if that operand is differentiable, each through its
+// own first-writer-assigns state.
+struct BatchNormBwd : Backward {
+    Shared<Gradient> dx, dgamma, dbeta, g;  // any of the three targets may be null
+    Shared<HipArray> x, gamma, stats, sums;
+    Shared<bool> trained;
+    int N, C, L;
+    void backward() const override {
+        const HipArray& G = g->borrow();
+        nk_device* dev = D(x);
+        const bool need_sums = dgamma || dbeta || (dx && *trained);
+        if (need_sums) check(nk_batch_norm_bwd_sums(dev, sums->ptr(), G.ptr(), x->ptr(), stats->ptr(), N, C, L));
+        bool ag = false, ab = false;
+        float* pg = dgamma ? dgamma->borrow_first_write(ag).ptr() : nullptr;
+        float* pb = dbeta ? dbeta->borrow_first_write(ab).ptr() : nullptr;
+        auto params = [&](float* a, float* b, bool assign) {
+            check((assign ? nk_batch_norm_bwd_params_assign : nk_batch_norm_bwd_params)(dev, a, b, sums->ptr(), C));
+        };
+        if (pg && pb && ag != ab) {  // one gradient already written in this pass (a shared parameter), the other not
+            params(pg, nullptr, ag);
+            params(nullptr, pb, ab);
+        } else if (pg || pb) {
+            params(pg, pb, pg ? ag : ab);
+        }
+        if (dx) {
+            bool assign = false;
+            HipArray& d = dx->borrow_first_write(assign);
+            check((assign ? nk_batch_norm_bwd_assign : nk_batch_norm_bwd)(dev, d.ptr(), G.ptr(), x->ptr(), gamma ? gamma->ptr() : nullptr, stats->ptr(),
+                                                                          *trained ? sums->ptr() : nullptr, N, C, L));
+        }
+    }
+    void targets(std::vector<const Gradient*>& out) const override {
+        if (dgamma) out.push_back(dgamma.get());
+        if (dbeta) out.push_back(dbeta.get());
+        if (dx) out.push_back(dx.get());
+    }
+};
+
+Shared<BatchNormFwd> batch_norm_fwd_node(const Var& x, const Var* gamma, const Var* beta, const Var* running_mean, const Var* running_var,
+                                         double momentum, double eps, Shared<bool> status, bool keep_stats) {
+    const Shape& xs = x.shape();
+    if (xs.size() < 2) panic("batch_norm: the input must have at least two dimensions (N, C, ...), got " + std::to_string(xs.size()));
+    const int C = xs[1];
+    if (C <= 0) panic("batch_norm: the channel extent must be positive");
+    auto per_channel = [&](const Var* v, const char* name) {
+        if (v && v->shape() != Shape{C}) panic(std::string("batch_norm: ") + name + " must have shape (C) = (" + std::to_string(C) + ")");
+    };
+    per_channel(gamma, "gamma"); per_channel(beta, "beta"); per_channel(running_mean, "running_mean"); per_channel(running_var, "running_var");
+    if (!running_mean != !running_var) panic("batch_norm: running_mean and running_var come together or not at all");
+    if (!(eps >= 0.0) || !std::isfinite(eps)) panic("batch_norm: eps must be finite and not negative");
+    if (!(momentum >= 0.0 && momentum <= 1.0)) panic("batch_norm: momentum must be in [0, 1]");
+    if (!status) panic("batch_norm: a status flag is required");
+    size_t L = 1;
+    for (size_t i = 2; i < xs.size(); ++i) L *= (size_t)xs[i];
+    if ((size_t)xs[0] * L > (size_t)INT_MAX) panic("batch_norm: more than 2^31 - 1 values per channel");
+    auto n = std::make_shared<BatchNormFwd>();
+    n->N = xs[0]; n->C = C; n->L = (int)L;
+    auto data = [](const Var* v) { return v ? v->data : nullptr; };
+    n->x = x.data; n->gamma = data(gamma); n->beta = data(beta); n->running_mean = data(running_mean); n->running_var = data(running_var);
+    n->y = zeros_like(x.data, xs);
+    if (keep_stats) n->stats = zeros_like(x.data, Shape{C, 2});
+    n->eps = eps; n->momentum = momentum; n->status = std::move(status);
+    return n;
+}
+History<ForwardEntry> batch_norm_history(const Var& x, const Var* gamma, const Var* beta) {
+    History<ForwardEntry> h = x.history;
+    if (gamma) h.merge(gamma->history);
+    if (beta) h.merge(beta->history);
+    return h;
+}
+Var batch_norm_var(const Var& x, const Var* gamma, const Var* beta, const Var* rm, const Var* rv, double momentum, double eps, Shared<bool> status) {
+    auto n = batch_norm_fwd_node(x, gamma, beta, rm, rv, momentum, eps, std::move(status), false);
+    auto y = n->y;
+    return Var::node(y, n, batch_norm_history(x, gamma, beta));
+}
+// x, gamma, beta with their gradients and tapes where differentiable (null otherwise); at least one gradient is not null
+VarDiff batch_norm_diff(const Var& x, const Shared<Gradient>& dx, const History<BackwardEntry>* hx, const Var* gamma,
+                        const Shared<Gradient>& dgamma, const History<BackwardEntry>* hg, const Var* beta, const Shared<Gradient>& dbeta,
+                        const History<BackwardEntry>* hb, const Var* rm, const Var* rv, double momentum, double eps, Shared<bool> status) {
+    auto n = batch_norm_fwd_node(x, gamma, beta, rm, rv, momentum, eps, std::move(status), true);
+    auto y = n->y;
+    Var var = Var::node(y, n, batch_norm_history(x, gamma, beta));
+    History<BackwardEntry> h;
+    if (hx) h = *hx;
+    if (hg) h.merge(*hg);
+    if (hb) h.merge(*hb);
+    auto grad = std::make_shared<Gradient>(var.device(), var.shape());
+    auto bw = std::make_shared<BatchNormBwd>();
+    bw->dx = dx; bw->dgamma = dgamma; bw->dbeta = dbeta; bw->g = grad;
+    bw->x = x.data; bw->gamma = n->gamma; bw->stats = n->stats; bw->sums = zeros_like(x.data, Shape{n->C, 2});
+    bw->trained = n->trained; bw->N = n->N; bw->C = n->C; bw->L = n->L;
+    return VarDiff::node(std::move(var), grad, entry(bw, grad), std::move(h));
+}
+
 Shape mm_shape(const Shape& a, const Shape& b, int kind) {  // utils.rs:46-55 `DotDim`
     if (kind == 4) {
         if (a.size() != 2 || b.size() != 1) panic("mv: matrix and vector expected");
@@ -1269,6 +1384,15 @@ Var Var::layer_norm(const Var& gamma, const Var& beta, double eps) const { retur
 Var Var::layer_norm(const Shape& normalized_shape, double eps) const { return layer_norm_var(*this, nullptr, nullptr, normalized_shape, eps); }
 VarDiff Var::layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps) const {
     return layer_norm_diff(*this, nullptr, nullptr, &gamma.var, gamma.grad, &gamma.history, &beta.var, beta.grad, &beta.history, gamma.shape(), eps);
+}
+Var Var::batch_norm(const Var* gamma, const Var* beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
+                    Shared<bool> status) const {
+    return batch_norm_var(*this, gamma, beta, running_mean, running_var, momentum, eps, std::move(status));
+}
+VarDiff Var::batch_norm(const VarDiff& gamma, const VarDiff& beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
+                        Shared<bool> status) const {
+    return batch_norm_diff(*this, nullptr, nullptr, &gamma.var, gamma.grad, &gamma.history, &beta.var, beta.grad, &beta.history, running_mean,
+                           running_var, momentum, eps, std::move(status));
 }
 Var Var::dropout(double p, Shared<bool> status) const {
     if (!(p >= 0.0 && p <= 1.0)) panic("Wrong probability received: " + std::to_string(p) + ".");
@@ -1685,6 +1809,16 @@ VarDiff VarDiff::layer_norm(const Var& gamma, const Var& beta, double eps) const
 VarDiff VarDiff::layer_norm(const Shape& normalized_shape, double eps) const {
     return layer_norm_diff(var, grad, &history, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, normalized_shape, eps);
 }
+VarDiff VarDiff::batch_norm(const VarDiff& gamma, const VarDiff& beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
+                            Shared<bool> status) const {
+    return batch_norm_diff(var, grad, &history, &gamma.var, gamma.grad, &gamma.history, &beta.var, beta.grad, &beta.history, running_mean, running_var,
+                           momentum, eps, std::move(status));
+}
+VarDiff VarDiff::batch_norm(const Var* gamma, const Var* beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
+                            Shared<bool> status) const {
+    return batch_norm_diff(var, grad, &history, gamma, nullptr, nullptr, beta, nullptr, nullptr, running_mean, running_var, momentum, eps,
+                           std::move(status));
+}
 VarDiff VarDiff::dropout(double p, Shared<bool> status) const {
     Var v = var.dropout(p, status);
     // the forward node owns the noise buffer; share it with the backward node (var.rs:375-393)
@@ -2023,6 +2157,41 @@ VarDiff LayerNorm::forward(const Var& input) const {
 }
 VarDiff LayerNorm::forward(const VarDiff& input) const {
     return elementwise_affine ? input.layer_norm(weight, bias, eps) : input.layer_norm(normalized_shape, eps);
+}
+
+BatchNormNd::BatchNormNd(int nd, DevicePtr dev, int num_features, double eps, double momentum, bool affine, bool track_running_stats)
+    : num_features(num_features), eps(eps), momentum(momentum), affine(affine), track_running_stats(track_running_stats), nd(nd),
+      status(std::make_shared<bool>(true)) {
+    if (num_features <= 0) panic("BatchNorm: num_features must be positive");
+    if (affine) {
+        weight = ones(dev, {num_features}).requires_grad();
+        bias = zeros(dev, {num_features}).requires_grad();
+    }
+    if (track_running_stats) {
+        running_mean = zeros(dev, {num_features});
+        running_var = ones(dev, {num_features});
+    }
+}
+void BatchNormNd::check_input(const Shape& s) const {
+    const std::string name = "BatchNorm" + std::to_string(nd) + "d";
+    const bool rank_ok = nd == 1 ? (s.size() == 2 || s.size() == 3) : s.size() == (size_t)nd + 2;
+    if (!rank_ok)
+        panic(name + ": expected " + (nd == 1 ? std::string("a 2- or 3") : std::to_string(nd + 2)) + "-dimensional input, got " +
+              std::to_string(s.size()) + " dimensions");
+    if (s[1] != num_features) panic(name + ": expected " + std::to_string(num_features) + " channels, got " + std::to_string(s[1]));
+}
+VarDiff BatchNormNd::forward(const Var& input) const {
+    check_input(input.shape());
+    if (!affine) panic("BatchNorm without affine parameters on a Var input has nothing to differentiate: use Var::batch_norm");
+    const Var* rm = track_running_stats ? &running_mean : nullptr;
+    return input.batch_norm(weight, bias, rm, rm ? &running_var : nullptr, momentum, eps, status);
+}
+VarDiff BatchNormNd::forward(const VarDiff& input) const {
+    check_input(input.shape());
+    const Var* rm = track_running_stats ? &running_mean : nullptr;
+    const Var* rv = track_running_stats ? &running_var : nullptr;
+    return affine ? input.batch_norm(weight, bias, rm, rv, momentum, eps, status)
+                  : input.batch_norm((const Var*)nullptr, (const Var*)nullptr, rm, rv, momentum, eps, status);
 }
 
 static VarDiff linear_node(const Linear& l, const Var& x, const Shared<Gradient>& dx, const History<BackwardEntry>* hx, bool relu = false) {
@@ -2443,6 +2612,22 @@ nn::LayerNorm layer_norm_from_json(DevicePtr dev, const Json& j, double eps) {
     return nn::LayerNorm(vardiff_from_json(dev, j.at("weight")), vardiff_from_json(dev, j.at("bias")), eps);
 }
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const std::string& text, double eps) { return layer_norm_from_json(std::move(dev), parse(text), eps); }
+
+std::string to_json(const nn::BatchNormNd& l) {
+    if (!l.affine || !l.track_running_stats) panic("serde: a BatchNorm is serialised with its affine parameters and its running statistics");
+    return "{\"weight\":" + to_json(l.weight) + ",\"bias\":" + to_json(l.bias) + ",\"running_mean\":" + to_json(l.running_mean) +
+           ",\"running_var\":" + to_json(l.running_var) + "}";
+}
+void batch_norm_load_json(nn::BatchNormNd& l, const Json& j) {
+    if (!l.affine || !l.track_running_stats) panic("serde: a BatchNorm is deserialised into a layer with affine parameters and running statistics");
+    DevicePtr dev = l.running_mean.device();
+    VarDiff w = vardiff_from_json(dev, j.at("weight")), b = vardiff_from_json(dev, j.at("bias"));
+    Var rm = var_from_json(dev, j.at("running_mean")), rv = var_from_json(dev, j.at("running_var"));
+    const Shape want{l.num_features};
+    if (w.shape() != want || b.shape() != want || rm.shape() != want || rv.shape() != want) panic("serde: BatchNorm fields must have shape (num_features)");
+    l.weight = std::move(w); l.bias = std::move(b); l.running_mean = std::move(rm); l.running_var = std::move(rv);
+}
+void batch_norm_load_json(nn::BatchNormNd& l, const std::string& text) { batch_norm_load_json(l, parse(text)); }
 
 }  // namespace serde
 

@@ -306,6 +306,15 @@ class Var {
     Var layer_norm(const Var& gamma, const Var& beta, double eps = 1e-5) const;
     Var layer_norm(const Shape& normalized_shape, double eps = 1e-5) const;
     VarDiff layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps = 1e-5) const;
+    // Batch normalisation over (N, spatial...) for each channel of an (N, C, spatial...) input (ours: the reference has none;
+    // semantics in neuronika_hip.h).  gamma / beta of shape (C), both or neither (null: no affine part); running_mean /
+    // running_var of shape (C), both or neither, updated IN PLACE by a training forward.  `status` is read each time the forward
+    // node runs: true trains (batch statistics), false infers (running statistics; the batch's when there are none).  The Var
+    // forms keep no statistics; with differentiable parameters the result is differentiable in them alone.
+    Var batch_norm(const Var* gamma, const Var* beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
+                   Shared<bool> status) const;
+    VarDiff batch_norm(const VarDiff& gamma, const VarDiff& beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
+                       Shared<bool> status) const;
     Var dropout(double p, Shared<bool> status) const; // var.rs:375
     std::vector<Var> chunks(const Shape& chunk_size) const;             // var.rs:401
     Var cat(const std::vector<Var>& variables, int axis) const;         // var.rs:564
@@ -416,6 +425,11 @@ class VarDiff {
     VarDiff layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps = 1e-5) const;
     VarDiff layer_norm(const Var& gamma, const Var& beta, double eps = 1e-5) const;
     VarDiff layer_norm(const Shape& normalized_shape, double eps = 1e-5) const;
+    // one forward and ONE backward entry; gradients flow to self and, independently, to gamma and beta where differentiable
+    VarDiff batch_norm(const VarDiff& gamma, const VarDiff& beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
+                       Shared<bool> status) const;
+    VarDiff batch_norm(const Var* gamma, const Var* beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
+                       Shared<bool> status) const;
     VarDiff dropout(double p, Shared<bool> status) const;
     std::vector<VarDiff> chunks(const Shape& chunk_size) const;
     VarDiff cat(const std::vector<VarDiff>& vars, int axis) const;
@@ -550,6 +564,41 @@ struct LayerNorm {
     LayerNorm(VarDiff weight, VarDiff bias, double eps = 1e-5);  // parameters built elsewhere (e.g. deserialised)
     VarDiff forward(const Var& input) const;  // differentiable in the parameters: needs elementwise_affine
     VarDiff forward(const VarDiff& input) const;
+};
+
+// Batch normalisation over (N, spatial...) per channel (ours: the reference has no normalisation layer), torch's BatchNorm1d/2d/3d:
+// training normalises with the batch's mean and biased variance and moves the running statistics towards them by `momentum` (the
+// running variance takes the unbiased estimate), inference normalises with the running statistics.  weight = ones, bias = zeros:
+// ordinary leaves for the optimizers; running_mean = zeros, running_var = ones: plain buffers.  Without `affine` there are no
+// parameters, without `track_running_stats` no buffers and the batch statistics serve in both modes.  Cumulative averaging and a
+// batches-seen counter are not provided.
+struct BatchNormNd {
+    VarDiff weight, bias;
+    Var running_mean, running_var;
+    int num_features;
+    double eps, momentum;
+    bool affine, track_running_stats;
+    int nd;  // 1: (N, C) or (N, C, L) inputs; 2: (N, C, H, W); 3: (N, C, D, H, W)
+    Shared<bool> status;
+    BatchNormNd(int nd, DevicePtr dev, int num_features, double eps, double momentum, bool affine, bool track_running_stats);
+    void train() const { *status = true; }
+    void eval() const { *status = false; }
+    VarDiff forward(const Var& input) const;  // differentiable in the parameters: needs affine
+    VarDiff forward(const VarDiff& input) const;
+   private:
+    void check_input(const Shape& s) const;
+};
+struct BatchNorm1d : BatchNormNd {
+    BatchNorm1d(DevicePtr dev, int num_features, double eps = 1e-5, double momentum = 0.1, bool affine = true, bool track_running_stats = true)
+        : BatchNormNd(1, std::move(dev), num_features, eps, momentum, affine, track_running_stats) {}
+};
+struct BatchNorm2d : BatchNormNd {
+    BatchNorm2d(DevicePtr dev, int num_features, double eps = 1e-5, double momentum = 0.1, bool affine = true, bool track_running_stats = true)
+        : BatchNormNd(2, std::move(dev), num_features, eps, momentum, affine, track_running_stats) {}
+};
+struct BatchNorm3d : BatchNormNd {
+    BatchNorm3d(DevicePtr dev, int num_features, double eps = 1e-5, double momentum = 0.1, bool affine = true, bool track_running_stats = true)
+        : BatchNormNd(3, std::move(dev), num_features, eps, momentum, affine, track_running_stats) {}
 };
 
 // `LSTMCell` neuronika-nn/src/lib.rs:453-541.  Weights (4H,in)/(4H,H), biases (4H), U(-k,k), k = 1/sqrt(H).
@@ -706,6 +755,12 @@ nn::Linear linear_from_json(DevicePtr dev, const std::string& text);
 std::string to_json(const nn::LayerNorm& l);  // {"weight":..., "bias":...}; eps is not part of the wire format
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const Json& j, double eps = 1e-5);
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const std::string& text, double eps = 1e-5);
+
+// {"weight":..., "bias":..., "running_mean":..., "running_var":...}; eps and momentum are not part of the wire format.  Loading
+// replaces the four fields of an existing layer (any of BatchNorm1d/2d/3d) of the same num_features.
+std::string to_json(const nn::BatchNormNd& l);
+void batch_norm_load_json(nn::BatchNormNd& l, const Json& j);
+void batch_norm_load_json(nn::BatchNormNd& l, const std::string& text);
 
 }  // namespace serde
 

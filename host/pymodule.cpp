@@ -69,6 +69,15 @@ PYBIND11_MODULE(_tape, m) {
         .def("layer_norm", py::overload_cast<const Var&, const Var&, double>(&Var::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const VarDiff&, const VarDiff&, double>(&Var::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const Shape&, double>(&Var::layer_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-5)
+        // gamma / beta: VarDiff (differentiable result), Var, or None; running_mean / running_var: Var or None
+        .def("batch_norm", [](const Var& x, const VarDiff& gamma, const VarDiff& beta, const Var* rm, const Var* rv, double momentum, double eps,
+                              const Status& s) { return x.batch_norm(gamma, beta, rm, rv, momentum, eps, s.flag); },
+             py::arg("gamma"), py::arg("beta"), py::arg("running_mean").none(true), py::arg("running_var").none(true), py::arg("momentum"), py::arg("eps"),
+             py::arg("status"))
+        .def("batch_norm", [](const Var& x, const Var* gamma, const Var* beta, const Var* rm, const Var* rv, double momentum, double eps,
+                              const Status& s) { return x.batch_norm(gamma, beta, rm, rv, momentum, eps, s.flag); },
+             py::arg("gamma").none(true), py::arg("beta").none(true), py::arg("running_mean").none(true), py::arg("running_var").none(true),
+             py::arg("momentum"), py::arg("eps"), py::arg("status"))
         .def("dropout", [](const Var& v, double p, const Status& s) { return v.dropout(p, s.flag); }).def("chunks", &Var::chunks).def("cat", &Var::cat)
         .def("mse", &Var::mse).def("mae", &Var::mae).def("bce", &Var::bce).def("bce_with_logits", &Var::bce_with_logits)
         .def("kldiv", &Var::kldiv).def("nll", &Var::nll).def("stack", &Var::stack)
@@ -135,6 +144,14 @@ PYBIND11_MODULE(_tape, m) {
         .def("layer_norm", py::overload_cast<const VarDiff&, const VarDiff&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const Var&, const Var&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const Shape&, double>(&VarDiff::layer_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-5)
+        .def("batch_norm", [](const VarDiff& x, const VarDiff& gamma, const VarDiff& beta, const Var* rm, const Var* rv, double momentum, double eps,
+                              const Status& s) { return x.batch_norm(gamma, beta, rm, rv, momentum, eps, s.flag); },
+             py::arg("gamma"), py::arg("beta"), py::arg("running_mean").none(true), py::arg("running_var").none(true), py::arg("momentum"), py::arg("eps"),
+             py::arg("status"))
+        .def("batch_norm", [](const VarDiff& x, const Var* gamma, const Var* beta, const Var* rm, const Var* rv, double momentum, double eps,
+                              const Status& s) { return x.batch_norm(gamma, beta, rm, rv, momentum, eps, s.flag); },
+             py::arg("gamma").none(true), py::arg("beta").none(true), py::arg("running_mean").none(true), py::arg("running_var").none(true),
+             py::arg("momentum"), py::arg("eps"), py::arg("status"))
         .def("dropout", [](const VarDiff& v, double p, const Status& s) { return v.dropout(p, s.flag); }).def("chunks", &VarDiff::chunks).def("cat", &VarDiff::cat)
         .def("mse", &VarDiff::mse).def("mae", &VarDiff::mae).def("bce", &VarDiff::bce).def("bce_with_logits", &VarDiff::bce_with_logits)
         .def("kldiv", &VarDiff::kldiv).def("nll", &VarDiff::nll).def("stack", &VarDiff::stack)
@@ -258,6 +275,9 @@ PYBIND11_MODULE(_tape, m) {
     sd.def("layer_norm_from_json", py::overload_cast<DevicePtr, const std::string&, double>(&serde::layer_norm_from_json), py::arg("dev"), py::arg("text"),
            py::arg("eps") = 1e-5);
 
+    sd.def("to_json", py::overload_cast<const nn::BatchNormNd&>(&serde::to_json));
+    sd.def("batch_norm_load_json", py::overload_cast<nn::BatchNormNd&, const std::string&>(&serde::batch_norm_load_json), py::arg("layer"), py::arg("text"));
+
     py::module_ nn = m.def_submodule("nn");
     nn.def("set_relu_peephole", &nn::set_relu_peephole, py::arg("on"));
     py::class_<nn::Linear>(nn, "Linear")
@@ -343,6 +363,31 @@ PYBIND11_MODULE(_tape, m) {
         .def(py::init<DevicePtr, int, int, std::vector<int>, std::vector<int>, PaddingMode, std::vector<int>, std::vector<int>, int, uint64_t>(),
              py::arg("dev"), py::arg("in_channels"), py::arg("out_channels"), py::arg("kernel_size"), py::arg("padding"),
              py::arg("padding_mode"), py::arg("stride"), py::arg("dilation"), py::arg("groups"), py::arg("seed") = 0);
+    py::class_<nn::BatchNormNd>(nn, "BatchNormNd")
+        // without affine parameters there is no weight and no bias, without tracked statistics no buffers: None
+        .def_property_readonly("weight", [](const nn::BatchNormNd& l) { return l.affine ? py::cast(l.weight) : py::object(py::none()); })
+        .def_property_readonly("bias", [](const nn::BatchNormNd& l) { return l.affine ? py::cast(l.bias) : py::object(py::none()); })
+        .def_property_readonly("running_mean", [](const nn::BatchNormNd& l) { return l.track_running_stats ? py::cast(l.running_mean) : py::object(py::none()); })
+        .def_property_readonly("running_var", [](const nn::BatchNormNd& l) { return l.track_running_stats ? py::cast(l.running_var) : py::object(py::none()); })
+        .def_readonly("num_features", &nn::BatchNormNd::num_features)
+        .def_readwrite("eps", &nn::BatchNormNd::eps)
+        .def_readwrite("momentum", &nn::BatchNormNd::momentum)
+        .def_readonly("affine", &nn::BatchNormNd::affine)
+        .def_readonly("track_running_stats", &nn::BatchNormNd::track_running_stats)
+        .def_property_readonly("training", [](const nn::BatchNormNd& l) { return *l.status; })
+        .def("train", &nn::BatchNormNd::train)
+        .def("eval", &nn::BatchNormNd::eval)
+        .def("forward", py::overload_cast<const Var&>(&nn::BatchNormNd::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::BatchNormNd::forward, py::const_));
+    py::class_<nn::BatchNorm1d, nn::BatchNormNd>(nn, "BatchNorm1d")
+        .def(py::init<DevicePtr, int, double, double, bool, bool>(), py::arg("dev"), py::arg("num_features"), py::arg("eps") = 1e-5,
+             py::arg("momentum") = 0.1, py::arg("affine") = true, py::arg("track_running_stats") = true);
+    py::class_<nn::BatchNorm2d, nn::BatchNormNd>(nn, "BatchNorm2d")
+        .def(py::init<DevicePtr, int, double, double, bool, bool>(), py::arg("dev"), py::arg("num_features"), py::arg("eps") = 1e-5,
+             py::arg("momentum") = 0.1, py::arg("affine") = true, py::arg("track_running_stats") = true);
+    py::class_<nn::BatchNorm3d, nn::BatchNormNd>(nn, "BatchNorm3d")
+        .def(py::init<DevicePtr, int, double, double, bool, bool>(), py::arg("dev"), py::arg("num_features"), py::arg("eps") = 1e-5,
+             py::arg("momentum") = 0.1, py::arg("affine") = true, py::arg("track_running_stats") = true);
     py::class_<nn::Dropout>(nn, "Dropout")
         .def(py::init<double>())
         .def("train", &nn::Dropout::train)

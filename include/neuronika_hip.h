@@ -542,6 +542,49 @@ int nk_layer_norm_bwd_params(nk_device* dev, float* dgamma, float* dbeta, const 
 int nk_layer_norm_bwd_params_assign(nk_device* dev, float* dgamma, float* dbeta, const float* g, const float* x,
                                     const float* stats, long long rows, int D);
 
+/* ------------------------------------------------------------------ batch normalisation */
+/* BatchNorm of a contiguous row-major tensor read as (N, C, L), L the product of the extents behind the channel axis (L = 1
+ * for an (N, C) input).  The reference has no such layer; the semantics are fixed here.  Per channel c, over its M = N * L values
+ * x[n][c][l], all in f32:
+ *   mean = sum(x) / M ;  var = sum((x - mean)^2) / M   (biased; centred, not E[x^2] - mean^2)
+ * The M values do not fit in registers, so the construction is part of the contract: the channel is cut into chunks, each chunk's
+ * mean and centred sum of squares M2 are formed from the registers that hold it (values and means taken relative to an anchor, the
+ * first value read or the first partial mean, so that a large common offset costs neither the sums nor the merges their low bits), and the (count, mean, M2) triples are merged
+ * pairwise in a fixed order with Chan's formula  M2 = M2a + M2b + delta^2 * na * nb / (na + nb),  delta = mean_b - mean_a.  x is
+ * read once for the statistics.
+ *   rstd = 1 / sqrt(var + eps) ;  xhat = (x - mean) * rstd ;  y = xhat * gamma + beta     (gamma, beta of C elements)
+ * fwd (training) overwrites y, writes stats[C][2] = {mean, rstd} when `stats` is not NULL, and updates in place, each only when
+ * its pointer is not NULL,
+ *   running_mean = (1 - momentum) * running_mean + momentum * mean
+ *   running_var  = (1 - momentum) * running_var  + momentum * var * M / (M - 1)            (unbiased, as torch)
+ * in the kernel that finishes the statistics.  M == 1 is NK_ERR_INVALID (one value has no variance); momentum outside [0, 1],
+ * a negative or non-finite eps and C <= 0 likewise.  N * L must fit in 31 bits.
+ * infer_fwd: mean = running_mean, rstd = 1 / sqrt(running_var + eps), the same y; nothing is updated; `stats` (optional) receives
+ * {mean, rstd} for a backward pass through the inference form.
+ * Backward, with xhat recomputed from x and stats, s0 = sum(g) and s1 = sum(g * xhat) over the channel:
+ *   bwd_sums   sums[C][2] = {s0, s1}, overwritten: one reduction pass feeds dx and both parameter gradients
+ *   bwd        dx += gamma * rstd * (g - s0 / M - xhat * s1 / M) ;  with sums == NULL the inference form  dx += gamma * rstd * g
+ *              (x may then be NULL too)
+ *   bwd_params dgamma += s1 ;  dbeta += s0                                                  (either output may be NULL, not both)
+ * `gamma` and `beta` may be NULL (y = xhat * 1 + 0).  N == 0 or L == 0 returns NK_OK and writes nothing (the _assign twins
+ * included).  No atomics, and the order of every sum is a function of (N, C, L) and the pointers' 16-byte alignment alone: every
+ * output repeats bit for bit.  A non-finite value stays inside its own channel.  Nothing here synchronises or allocates beyond
+ * the workspace, no block waits on another, so every call can be captured into a graph.  L % 4 == 0 with L >= 256 and 16-byte
+ * aligned pointers takes float4 kernels whose blocks own one channel; L == 1 kernels whose lanes own columns; everything else
+ * scalar kernels.  The `_assign` twins write what their `+=` twin would leave in an all-zero destination, without reading it. */
+int nk_batch_norm_fwd(nk_device* dev, const float* x, const float* gamma, const float* beta, float* y, float* stats,
+                      float* running_mean, float* running_var, int N, int C, int L, double eps, double momentum);
+int nk_batch_norm_infer_fwd(nk_device* dev, const float* x, const float* gamma, const float* beta, const float* running_mean,
+                            const float* running_var, float* y, float* stats, int N, int C, int L, double eps);
+int nk_batch_norm_bwd_sums(nk_device* dev, float* sums, const float* g, const float* x, const float* stats, int N, int C,
+                           int L);
+int nk_batch_norm_bwd(nk_device* dev, float* dx, const float* g, const float* x, const float* gamma, const float* stats,
+                      const float* sums, int N, int C, int L);
+int nk_batch_norm_bwd_assign(nk_device* dev, float* dx, const float* g, const float* x, const float* gamma,
+                             const float* stats, const float* sums, int N, int C, int L);
+int nk_batch_norm_bwd_params(nk_device* dev, float* dgamma, float* dbeta, const float* sums, int C);
+int nk_batch_norm_bwd_params_assign(nk_device* dev, float* dgamma, float* dbeta, const float* sums, int C);
+
 /* ------------------------------------------------------------------ fused attention core ---
  * The composed multi-head attention's per-(sample, head) chain in one kernel per direction (SURVEY.md 8a note; the
  * composition is MatrixMatrixMulT node/matrix_matrix_mul_t/mod.rs:31-41, Multiplication node/multiplication/mod.rs:39-50,

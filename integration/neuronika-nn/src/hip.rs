@@ -77,6 +77,62 @@ impl Linear {
     }
 }
 
+/// Batch normalisation over `(N, spatial...)` per channel (the reference has no normalisation layer; semantics in
+/// `include/neuronika_hip.h`), torch's `BatchNorm1d` / `2d` / `3d`: training normalises with the batch's mean and biased variance
+/// and moves `running_mean` / `running_var` towards them by `momentum` (the running variance takes the unbiased estimate),
+/// inference normalises with the running statistics.  `weight` starts as ones, `bias` as zeros, `running_mean` as zeros,
+/// `running_var` as ones; the running statistics are plain buffers, not parameters.
+macro_rules! batch_norm_layer {
+    ($name:ident, $ranks:expr, $doc:expr) => {
+        #[doc = $doc]
+        pub struct $name {
+            pub weight: HipVarDiff<Ix1>,
+            pub bias: HipVarDiff<Ix1>,
+            pub running_mean: HipVar<Ix1>,
+            pub running_var: HipVar<Ix1>,
+            pub eps: f64,
+            pub momentum: f64,
+            pub status: Rc<Cell<bool>>,
+        }
+
+        impl $name {
+            pub fn new(num_features: usize, eps: f64, momentum: f64, device: &Device) -> Self {
+                Self {
+                    weight: HipVarDiff::parameter(&Array::ones(num_features), device.clone()),
+                    bias: HipVarDiff::parameter(&Array::zeros(num_features), device.clone()),
+                    running_mean: HipVar::from_ndarray(&Array::zeros(num_features), device.clone()),
+                    running_var: HipVar::from_ndarray(&Array::ones(num_features), device.clone()),
+                    eps,
+                    momentum,
+                    status: Rc::new(Cell::new(true)),
+                }
+            }
+
+            pub fn train(&self) {
+                self.status.set(true)
+            }
+
+            pub fn eval(&self) {
+                self.status.set(false)
+            }
+
+            /// ONE forward node (`nk_batch_norm_fwd` / `nk_batch_norm_infer_fwd`) and ONE backward entry (`nk_batch_norm_bwd_sums`,
+            /// `nk_batch_norm_bwd`, `nk_batch_norm_bwd_params`).
+            pub fn forward<D: Dimension + 'static>(&self, input: HipVarDiff<D>) -> HipVarDiff<D> {
+                let shape = input.shape();
+                assert!($ranks.contains(&shape.len()), "{}: an input of {} dimensions", stringify!($name), shape.len());
+                assert!(shape[1] == self.weight.shape()[0], "{}: expected {} channels, got {}", stringify!($name), self.weight.shape()[0], shape[1]);
+                input.batch_norm(self.weight.clone(), self.bias.clone(), Some((self.running_mean.clone(), self.running_var.clone())), self.momentum,
+                                 self.eps, self.status.clone())
+            }
+        }
+    };
+}
+
+batch_norm_layer!(BatchNorm1d, [2usize, 3], "Batch normalisation of `(N, C)` or `(N, C, L)` inputs.");
+batch_norm_layer!(BatchNorm2d, [4usize], "Batch normalisation of `(N, C, H, W)` inputs.");
+batch_norm_layer!(BatchNorm3d, [5usize], "Batch normalisation of `(N, C, D, H, W)` inputs.");
+
 /// Layer normalisation over the trailing dimensions `normalized_shape` of the input (the reference has no normalisation layer;
 /// semantics in `include/neuronika_hip.h`): `y = (x - mean) / sqrt(var + eps) * weight + bias` per row, biased variance.
 /// `weight` starts as ones, `bias` as zeros, both of `normalized_shape` (dimension `E`).

@@ -18,7 +18,7 @@ use super::{
         AttentionState, BinaryOp, BinaryOperation, BinaryOperationBackwardLeft, BinaryOperationBackwardRight, Chunk, ChunkBackward,
         Convolution, ConvolutionBackwardInput, ConvolutionBackwardKernel, ConvolutionBackwardKernelBias, ConvolutionBackwardPadded, ConvolutionBias,
         ConvolutionBiasPadded, Dropout,
-        DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, LayerNorm, LayerNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
+        DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
         ReLUBackward, ReluMask, Softmax, SoftmaxBackward,
@@ -207,6 +207,40 @@ where
 
     pub fn layer_norm<E: 'static + Dimension>(self, gamma: HipVar<E>, beta: HipVar<E>, eps: f64) -> HipVar<D> {
         self.layer_norm_with_stats(gamma, beta, eps, None)
+    }
+
+    /// Batch normalisation over `(N, spatial...)` for each channel of an `(N, C, spatial...)` input: ours, the reference has no
+    /// normalisation node.  `running` = `(running_mean, running_var)`, updated in place by a training forward, or `None` (the
+    /// batch statistics then serve in both modes); `status` is the train / eval switch Dropout uses.  `stats` = the per-channel
+    /// `{mean, rstd}` buffer a backward node will read with the cell that records the mode of the last run, `None` for the
+    /// no-gradient form (`batch_norm`).
+    #[allow(clippy::too_many_arguments)]
+    pub(crate) fn batch_norm_with_stats(mut self, gamma: HipVar<Ix1>, beta: HipVar<Ix1>, running: Option<(HipVar<Ix1>, HipVar<Ix1>)>, momentum: f64,
+                                        eps: f64, status: Rc<Cell<bool>>, stats: Option<(Shared<HipArray<Ix2>>, Rc<Cell<bool>>)>) -> HipVar<D> {
+        let xs = self.data.borrow().shape_c();
+        assert!(xs.len() >= 2, "batch_norm: the input must have at least two dimensions (N, C, ...)");
+        let channels = xs[1] as usize;
+        assert!(gamma.data.borrow().len() == channels && beta.data.borrow().len() == channels, "batch_norm: gamma and beta must have shape (C)");
+        assert!(eps >= 0.0 && eps.is_finite(), "batch_norm: eps must be finite and not negative");
+        assert!((0.0..=1.0).contains(&momentum), "batch_norm: momentum must be in [0, 1]");
+        let running = running.map(|(mean, var)| {
+            assert!(mean.data.borrow().len() == channels && var.data.borrow().len() == channels, "batch_norm: the running statistics must have shape (C)");
+            (mean.data, var.data)
+        });
+        self.history.merge(gamma.history);
+        self.history.merge(beta.history);
+        let data = shared(self.data.borrow().dimension(), &self.device());
+        let (stats, trained) = match stats {
+            Some((s, t)) => (Some(s), t),
+            None => (None, Rc::new(Cell::new(true))),
+        };
+        let op = BatchNorm::new(self.data, gamma.data, beta.data, running, data.clone(), stats, eps, momentum, status, trained);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    pub fn batch_norm(self, gamma: HipVar<Ix1>, beta: HipVar<Ix1>, running: Option<(HipVar<Ix1>, HipVar<Ix1>)>, momentum: f64, eps: f64,
+                      status: Rc<Cell<bool>>) -> HipVar<D> {
+        self.batch_norm_with_stats(gamma, beta, running, momentum, eps, status, None)
     }
 
     /// `Var::log_softmax` (`var.rs:332-344`).
@@ -577,6 +611,23 @@ where
         let var = self.var.layer_norm_with_stats(gamma.var, beta.var, eps, Some(stats.clone()));
         let op: Rc<dyn Backward> = Rc::new(LayerNormBackward::new(input_data, gamma_data, stats, Some(self.grad.clone()), gamma.grad.clone(),
                                                                    beta.grad.clone(), grad.clone()));
+        HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
+    }
+
+    /// Batch normalisation with differentiable parameters: ONE forward node and ONE backward entry writing the gradients of
+    /// `self`, `gamma` and `beta` (`BatchNormBackward`).
+    pub fn batch_norm(mut self, gamma: HipVarDiff<Ix1>, beta: HipVarDiff<Ix1>, running: Option<(HipVar<Ix1>, HipVar<Ix1>)>, momentum: f64, eps: f64,
+                      status: Rc<Cell<bool>>) -> HipVarDiff<D> {
+        self.history.merge(gamma.history);
+        self.history.merge(beta.history);
+        let (input_data, gamma_data) = (self.var.data.clone(), gamma.var.data.clone());
+        let channels = gamma_data.borrow().len();
+        let (stats, sums) = (shared(Ix2(channels, 2), &self.var.device()), shared(Ix2(channels, 2), &self.var.device()));
+        let trained = Rc::new(Cell::new(true));
+        let grad = self.new_grad(self.grad.shape());
+        let var = self.var.batch_norm_with_stats(gamma.var, beta.var, running, momentum, eps, status, Some((stats.clone(), trained.clone())));
+        let op: Rc<dyn Backward> = Rc::new(BatchNormBackward::new(input_data, gamma_data, stats, sums, trained, Some(self.grad.clone()),
+                                                                   gamma.grad.clone(), beta.grad.clone(), grad.clone()));
         HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
     }
 

@@ -3,7 +3,7 @@
 //! reference's ndarray nodes (`node/*/mod.rs`), so graph construction code is unchanged.  Written here: the nodes of
 //! the BASELINE configurations (MatMul / MatMulT, Convolution, broadcast binaries, ReLU, Softmax, Dropout, Sum,
 //! SquaredError, the fused attention core of the composed MHA) and their glue (LogSoftmax, Mean, Pad in all four modes, Chunk,
-//! MultiConcatenate, Transpose, the SGD / Adam steps) and the layer normalisation the reference lacks.  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
+//! MultiConcatenate, Transpose, the SGD / Adam steps) and the layer and batch normalisation the reference lacks.  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
 mod attention;
 mod binary_op;
 mod convolution;

@@ -166,6 +166,13 @@ _SIGS = {
     "nk_layer_norm_bwd_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
     "nk_layer_norm_bwd_params": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
     "nk_layer_norm_bwd_params_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
+    "nk_batch_norm_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double],
+    "nk_batch_norm_infer_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_double],
+    "nk_batch_norm_bwd_sums": [VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int],
+    "nk_batch_norm_bwd": [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int],
+    "nk_batch_norm_bwd_assign": [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int],
+    "nk_batch_norm_bwd_params": [VP, VP, VP, VP, C.c_int],
+    "nk_batch_norm_bwd_params_assign": [VP, VP, VP, VP, C.c_int],
     "nk_attention_supported": [C.c_int, C.c_int, C.c_double, C.c_int],
     "nk_attention_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_attention_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double,
@@ -734,6 +741,33 @@ def layer_norm_bwd_params(dev, dgamma, dbeta, g, x, stats, rows, D, assign=False
     """either of `dgamma`, `dbeta` may be None"""
     check((lib.nk_layer_norm_bwd_params_assign if assign else lib.nk_layer_norm_bwd_params)(dev.h, _p(dgamma), _p(dbeta), _p(g), _p(x), _p(stats),
                                                                                               int(rows), int(D)))
+
+
+def batch_norm_fwd(dev, x, gamma, beta, y, stats, running_mean, running_var, N, C, L, eps=1e-5, momentum=0.1):
+    """training: x read as (N, C, L); `gamma`, `beta`, `stats` (C, 2), `running_mean`, `running_var` may be None"""
+    check(lib.nk_batch_norm_fwd(dev.h, _p(x), _p(gamma), _p(beta), _p(y), _p(stats), _p(running_mean), _p(running_var), int(N), int(C), int(L),
+                                float(eps), float(momentum)))
+
+
+def batch_norm_infer_fwd(dev, x, gamma, beta, running_mean, running_var, y, stats, N, C, L, eps=1e-5):
+    check(lib.nk_batch_norm_infer_fwd(dev.h, _p(x), _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(y), _p(stats), int(N), int(C), int(L),
+                                      float(eps)))
+
+
+def batch_norm_bwd_sums(dev, sums, g, x, stats, N, C, L):
+    """sums (C, 2) = {sum g, sum g * xhat}, overwritten"""
+    check(lib.nk_batch_norm_bwd_sums(dev.h, _p(sums), _p(g), _p(x), _p(stats), int(N), int(C), int(L)))
+
+
+def batch_norm_bwd(dev, dx, g, x, gamma, stats, sums, N, C, L, assign=False):
+    """`sums` None: the inference form"""
+    check((lib.nk_batch_norm_bwd_assign if assign else lib.nk_batch_norm_bwd)(dev.h, _p(dx), _p(g), _p(x), _p(gamma), _p(stats), _p(sums), int(N), int(C),
+                                                                              int(L)))
+
+
+def batch_norm_bwd_params(dev, dgamma, dbeta, sums, C, assign=False):
+    """either of `dgamma`, `dbeta` may be None"""
+    check((lib.nk_batch_norm_bwd_params_assign if assign else lib.nk_batch_norm_bwd_params)(dev.h, _p(dgamma), _p(dbeta), _p(sums), int(C)))
 
 
 def dropout_fwd(dev, x, y, noise, p, train=True, seed=0, offset=0):
