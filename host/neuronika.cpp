@@ -1209,6 +1209,105 @@ VarDiff batch_norm_diff(const Var& x, const Shared<Gradient>& dx, const History<
     return VarDiff::node(std::move(var), grad, entry(bw, grad), std::move(h));
 }
 
+// Pooling (ours; the reference has no such node; semantics in neuronika_hip.h).  The geometry is checked when the graph is built
+// (nk_pool_out_shape holds the rules, the messages here name the offending axis); the max-pool node of a differentiable graph
+// owns `idx`, the int32 offsets of the selected elements, in an f32 array of the output's shape (the same 4 bytes per element).
+struct PoolFwd : Forward {
+    Shared<HipArray> x, y, idx;  // idx: null for average pooling and for the no-gradient max pooling
+    std::vector<int> kernel, stride, padding;
+    bool average = false, count_include_pad = true;
+    void forward() const override {
+        const int nd = (int)kernel.size();
+        if (average)
+            check(nk_avg_pool_fwd(D(x), nd, x->ptr(), x->shape().data(), y->ptr(), kernel.data(), stride.data(), padding.data(), count_include_pad));
+        else
+            check(nk_max_pool_fwd(D(x), nd, x->ptr(), x->shape().data(), y->ptr(), idx ? reinterpret_cast<int*>(idx->ptr()) : nullptr, kernel.data(),
+                                  stride.data(), padding.data()));
+    }
+};
+struct PoolBwd : Backward {
+    Shared<Gradient> dx, g;
+    Shared<HipArray> idx;
+    Shape x_shape;
+    std::vector<int> kernel, stride, padding;
+    bool average = false, count_include_pad = true;
+    void backward() const override {
+        const HipArray& G = g->borrow();
+        bool assign = false;
+        HipArray& d = dx->borrow_first_write(assign);
+        nk_device* dev = d.device()->raw();
+        const int nd = (int)kernel.size();
+        if (average)
+            check((assign ? nk_avg_pool_bwd_assign : nk_avg_pool_bwd)(dev, nd, d.ptr(), x_shape.data(), G.ptr(), kernel.data(), stride.data(),
+                                                                      padding.data(), count_include_pad));
+        else
+            check((assign ? nk_max_pool_bwd_assign : nk_max_pool_bwd)(dev, nd, d.ptr(), x_shape.data(), G.ptr(), reinterpret_cast<const int*>(idx->ptr()),
+                                                                      kernel.data(), stride.data(), padding.data()));
+    }
+    void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
+};
+
+Shared<PoolFwd> pool_fwd_node(const char* what, const Var& x, const std::vector<int>& kernel, const std::vector<int>& stride_in,
+                              const std::vector<int>& padding_in, bool average, bool count_include_pad, bool keep_idx) {
+    const Shape& xs = x.shape();
+    const std::string name = what;
+    if (xs.size() < 3 || xs.size() > 5) panic(name + ": the input must be (N, C, spatial...) with 1 to 3 spatial axes, got " + std::to_string(xs.size()) + " dimensions");
+    const size_t nd = xs.size() - 2;
+    const std::vector<int> stride = stride_in.empty() ? kernel : stride_in;
+    const std::vector<int> padding = padding_in.empty() ? std::vector<int>(nd, 0) : padding_in;
+    if (kernel.size() != nd) panic(name + ": kernel has " + std::to_string(kernel.size()) + " entries for " + std::to_string(nd) + " spatial axes");
+    if (stride.size() != nd) panic(name + ": stride has " + std::to_string(stride.size()) + " entries for " + std::to_string(nd) + " spatial axes");
+    if (padding.size() != nd) panic(name + ": padding has " + std::to_string(padding.size()) + " entries for " + std::to_string(nd) + " spatial axes");
+    for (size_t i = 0; i < nd; ++i) {
+        const std::string axis = " of spatial axis " + std::to_string(i);
+        if (kernel[i] < 1) panic(name + ": window " + std::to_string(kernel[i]) + axis + " (must be >= 1)");
+        if (stride[i] < 1) panic(name + ": stride " + std::to_string(stride[i]) + axis + " (must be >= 1)");
+        if (padding[i] < 0 || padding[i] > kernel[i] / 2)
+            panic(name + ": padding " + std::to_string(padding[i]) + axis + " (must be in [0, window / 2] = [0, " + std::to_string(kernel[i] / 2) + "])");
+        if (xs[2 + i] < 1 || xs[2 + i] + 2 * padding[i] < kernel[i])
+            panic(name + ": window " + std::to_string(kernel[i]) + " exceeds the padded extent " + std::to_string(xs[2 + i]) + " + 2 * " +
+                  std::to_string(padding[i]) + axis + ": no output");
+    }
+    Shape ys(xs.size());
+    if (nk_pool_out_shape((int)nd, xs.data(), kernel.data(), stride.data(), padding.data(), ys.data()) != NK_OK) panic(name + ": " + nk_last_error());
+    auto n = std::make_shared<PoolFwd>();
+    n->x = x.data; n->y = zeros_like(x.data, ys);
+    if (keep_idx) n->idx = zeros_like(x.data, ys);
+    n->kernel = kernel; n->stride = stride; n->padding = padding;
+    n->average = average; n->count_include_pad = count_include_pad;
+    return n;
+}
+Var pool_var(const char* what, const Var& x, const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding,
+             bool average, bool count_include_pad) {
+    auto n = pool_fwd_node(what, x, kernel, stride, padding, average, count_include_pad, false);
+    auto y = n->y;
+    return Var::node(y, n, x.history);
+}
+VarDiff pool_diff(const char* what, const VarDiff& x, const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding,
+                  bool average, bool count_include_pad) {
+    auto n = pool_fwd_node(what, x.var, kernel, stride, padding, average, count_include_pad, !average);
+    auto y = n->y;
+    Var v = Var::node(y, n, x.var.history);
+    auto g = std::make_shared<Gradient>(v.device(), v.shape());
+    auto bw = std::make_shared<PoolBwd>();
+    bw->dx = x.grad; bw->g = g; bw->idx = n->idx; bw->x_shape = x.shape();
+    bw->kernel = n->kernel; bw->stride = n->stride; bw->padding = n->padding;
+    bw->average = average; bw->count_include_pad = count_include_pad;
+    return VarDiff::node(std::move(v), g, entry(bw, g), x.history);
+}
+std::vector<int> spatial_extents(const char* what, const Shape& s) {
+    if (s.size() < 3 || s.size() > 5)
+        panic(std::string(what) + ": the input must be (N, C, spatial...) with 1 to 3 spatial axes, got " + std::to_string(s.size()) + " dimensions");
+    return std::vector<int>(s.begin() + 2, s.end());
+}
+Shape flat_shape(const Shape& s) {
+    if (s.size() < 2) panic("flatten: the input must have at least two dimensions (N, ...), got " + std::to_string(s.size()));
+    size_t n = 1;
+    for (size_t i = 1; i < s.size(); ++i) n *= (size_t)s[i];
+    if (n > (size_t)INT_MAX) panic("flatten: more than 2^31 - 1 values per sample");
+    return Shape{s[0], (int)n};
+}
+
 Shape mm_shape(const Shape& a, const Shape& b, int kind) {  // utils.rs:46-55 `DotDim`
     if (kind == 4) {
         if (a.size() != 2 || b.size() != 1) panic("mv: matrix and vector expected");
@@ -1374,6 +1473,22 @@ Var Var::unsqueeze(int axis) const {
     s.insert(s.begin() + axis, 1);
     auto n = std::make_shared<UnsqueezeFwd>();
     n->x = data; n->y = zeros_like(data, s);
+    auto y = n->y;
+    return Var::node(y, n, history);
+}
+Var Var::max_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding) const {
+    return pool_var("max_pool", *this, kernel, stride, padding, false, true);
+}
+Var Var::avg_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding, bool count_include_pad) const {
+    return pool_var("avg_pool", *this, kernel, stride, padding, true, count_include_pad);
+}
+Var Var::global_avg_pool() const {
+    const std::vector<int> k = spatial_extents("global_avg_pool", shape());
+    return pool_var("global_avg_pool", *this, k, k, std::vector<int>(k.size(), 0), true, true);
+}
+Var Var::flatten() const {  // the Unsqueeze node with another shape: a copy into the reshaped buffer
+    auto n = std::make_shared<UnsqueezeFwd>();
+    n->x = data; n->y = zeros_like(data, flat_shape(shape()));
     auto y = n->y;
     return Var::node(y, n, history);
 }
@@ -1797,6 +1912,23 @@ VarDiff VarDiff::unsqueeze(int axis) const {
     bw->dx = grad; bw->g = g;
     return VarDiff::node(std::move(v), g, entry(bw, g), history);
 }
+VarDiff VarDiff::max_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding) const {
+    return pool_diff("max_pool", *this, kernel, stride, padding, false, true);
+}
+VarDiff VarDiff::avg_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding, bool count_include_pad) const {
+    return pool_diff("avg_pool", *this, kernel, stride, padding, true, count_include_pad);
+}
+VarDiff VarDiff::global_avg_pool() const {
+    const std::vector<int> k = spatial_extents("global_avg_pool", shape());
+    return pool_diff("global_avg_pool", *this, k, k, std::vector<int>(k.size(), 0), true, true);
+}
+VarDiff VarDiff::flatten() const {
+    Var v = var.flatten();
+    auto g = std::make_shared<Gradient>(v.device(), v.shape());
+    auto bw = std::make_shared<UnsqueezeBwd>();
+    bw->dx = grad; bw->g = g;
+    return VarDiff::node(std::move(v), g, entry(bw, g), history);
+}
 VarDiff VarDiff::softmax(int axis) const { check_axis(shape(), axis); return unary_diff(Unary::Softmax, axis, *this, shape()); }
 VarDiff VarDiff::log_softmax(int axis) const { check_axis(shape(), axis); return unary_diff(Unary::LogSoftmax, axis, *this, shape()); }
 VarDiff VarDiff::t() const { return unary_diff(Unary::Transpose, 0, *this, Shape(shape().rbegin(), shape().rend())); }
@@ -2192,6 +2324,34 @@ VarDiff BatchNormNd::forward(const VarDiff& input) const {
     const Var* rv = track_running_stats ? &running_var : nullptr;
     return affine ? input.batch_norm(weight, bias, rm, rv, momentum, eps, status)
                   : input.batch_norm((const Var*)nullptr, (const Var*)nullptr, rm, rv, momentum, eps, status);
+}
+
+PoolNd::PoolNd(int nd, bool average, std::vector<int> kernel_size, std::vector<int> stride, std::vector<int> padding, bool count_include_pad)
+    : kernel_size(std::move(kernel_size)), stride(std::move(stride)), padding(std::move(padding)), average(average),
+      count_include_pad(count_include_pad), nd(nd) {
+    const std::string name = std::string(average ? "AvgPool" : "MaxPool") + std::to_string(nd) + "d";
+    if (this->stride.empty()) this->stride = this->kernel_size;
+    if (this->padding.empty()) this->padding.assign(nd, 0);
+    if ((int)this->kernel_size.size() != nd || (int)this->stride.size() != nd || (int)this->padding.size() != nd)
+        panic(name + ": kernel_size, stride and padding take " + std::to_string(nd) + " entries each");
+    for (int i = 0; i < nd; ++i) {
+        if (this->kernel_size[i] < 1 || this->stride[i] < 1) panic(name + ": window and stride of axis " + std::to_string(i) + " must be >= 1");
+        if (this->padding[i] < 0 || this->padding[i] > this->kernel_size[i] / 2)
+            panic(name + ": padding of axis " + std::to_string(i) + " must be in [0, window / 2]");
+    }
+}
+void PoolNd::check_input(const Shape& s) const {
+    if (s.size() != (size_t)nd + 2)
+        panic(std::string(average ? "AvgPool" : "MaxPool") + std::to_string(nd) + "d: expected " + std::to_string(nd + 2) + "-dimensional input, got " +
+              std::to_string(s.size()) + " dimensions");
+}
+Var PoolNd::forward(const Var& input) const {
+    check_input(input.shape());
+    return average ? input.avg_pool(kernel_size, stride, padding, count_include_pad) : input.max_pool(kernel_size, stride, padding);
+}
+VarDiff PoolNd::forward(const VarDiff& input) const {
+    check_input(input.shape());
+    return average ? input.avg_pool(kernel_size, stride, padding, count_include_pad) : input.max_pool(kernel_size, stride, padding);
 }
 
 static VarDiff linear_node(const Linear& l, const Var& x, const Shared<Gradient>& dx, const History<BackwardEntry>* hx, bool relu = false) {

@@ -297,6 +297,14 @@ class Var {
     Var ln() const;
     Var exp() const;
     Var unsqueeze(int axis) const;
+    // Pooling over the spatial axes of an (N, C, spatial...) input (ours: the reference has none; semantics in neuronika_hip.h):
+    // nd = rank - 2 = the length of `kernel`, `stride` (empty: stride = kernel) and `padding` (empty: zeros); floor mode, dilation 1.
+    // global_avg_pool = avg_pool over the whole spatial extents, result (N, C, 1, ..); flatten: (N, d_1, .., d_r) -> (N, prod d_i).
+    Var max_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding) const;
+    Var avg_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding,
+                 bool count_include_pad = true) const;
+    Var global_avg_pool() const;
+    Var flatten() const;
     Var softmax(int axis) const;                      // var.rs:318
     Var log_softmax(int axis) const;                  // var.rs:338
     Var t() const;                                    // var.rs:347
@@ -418,6 +426,12 @@ class VarDiff {
     VarDiff ln() const;
     VarDiff exp() const;
     VarDiff unsqueeze(int axis) const;
+    // the differentiable max-pool node owns the int32 offsets of the selected elements (4 bytes per output)
+    VarDiff max_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding) const;
+    VarDiff avg_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding,
+                     bool count_include_pad = true) const;
+    VarDiff global_avg_pool() const;
+    VarDiff flatten() const;
     VarDiff softmax(int axis) const;
     VarDiff log_softmax(int axis) const;
     VarDiff t() const;
@@ -599,6 +613,43 @@ struct BatchNorm2d : BatchNormNd {
 struct BatchNorm3d : BatchNormNd {
     BatchNorm3d(DevicePtr dev, int num_features, double eps = 1e-5, double momentum = 0.1, bool affine = true, bool track_running_stats = true)
         : BatchNormNd(3, std::move(dev), num_features, eps, momentum, affine, track_running_stats) {}
+};
+
+// Max / average pooling layers (ours: the reference has none), torch's MaxPool1d/2d/3d and AvgPool1d/2d/3d in floor mode with
+// dilation 1: no parameters; an empty `stride` means stride = kernel_size, an empty `padding` zeros.
+struct PoolNd {
+    std::vector<int> kernel_size, stride, padding;
+    bool average, count_include_pad;
+    int nd;
+    PoolNd(int nd, bool average, std::vector<int> kernel_size, std::vector<int> stride, std::vector<int> padding, bool count_include_pad);
+    Var forward(const Var& input) const;
+    VarDiff forward(const VarDiff& input) const;
+   private:
+    void check_input(const Shape& s) const;
+};
+struct MaxPool1d : PoolNd {
+    MaxPool1d(int kernel_size, int stride = 0, int padding = 0)
+        : PoolNd(1, false, {kernel_size}, stride ? std::vector<int>{stride} : std::vector<int>{}, {padding}, true) {}
+};
+struct MaxPool2d : PoolNd {
+    MaxPool2d(std::vector<int> kernel_size, std::vector<int> stride = {}, std::vector<int> padding = {})
+        : PoolNd(2, false, std::move(kernel_size), std::move(stride), std::move(padding), true) {}
+};
+struct MaxPool3d : PoolNd {
+    MaxPool3d(std::vector<int> kernel_size, std::vector<int> stride = {}, std::vector<int> padding = {})
+        : PoolNd(3, false, std::move(kernel_size), std::move(stride), std::move(padding), true) {}
+};
+struct AvgPool1d : PoolNd {
+    AvgPool1d(int kernel_size, int stride = 0, int padding = 0, bool count_include_pad = true)
+        : PoolNd(1, true, {kernel_size}, stride ? std::vector<int>{stride} : std::vector<int>{}, {padding}, count_include_pad) {}
+};
+struct AvgPool2d : PoolNd {
+    AvgPool2d(std::vector<int> kernel_size, std::vector<int> stride = {}, std::vector<int> padding = {}, bool count_include_pad = true)
+        : PoolNd(2, true, std::move(kernel_size), std::move(stride), std::move(padding), count_include_pad) {}
+};
+struct AvgPool3d : PoolNd {
+    AvgPool3d(std::vector<int> kernel_size, std::vector<int> stride = {}, std::vector<int> padding = {}, bool count_include_pad = true)
+        : PoolNd(3, true, std::move(kernel_size), std::move(stride), std::move(padding), count_include_pad) {}
 };
 
 // `LSTMCell` neuronika-nn/src/lib.rs:453-541.  Weights (4H,in)/(4H,H), biases (4H), U(-k,k), k = 1/sqrt(H).

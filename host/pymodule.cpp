@@ -65,6 +65,9 @@ PYBIND11_MODULE(_tape, m) {
         .def("__neg__", &Var::neg).def("pow", &Var::pow).def("sqrt", &Var::sqrt).def("leaky_relu", &Var::leaky_relu)
         .def("softplus", &Var::softplus).def("sigmoid", &Var::sigmoid).def("tanh", &Var::tanh).def("ln", &Var::ln)
         .def("exp", &Var::exp).def("unsqueeze", &Var::unsqueeze)
+        .def("max_pool", &Var::max_pool, py::arg("kernel"), py::arg("stride") = std::vector<int>{}, py::arg("padding") = std::vector<int>{})
+        .def("avg_pool", &Var::avg_pool, py::arg("kernel"), py::arg("stride") = std::vector<int>{}, py::arg("padding") = std::vector<int>{}, py::arg("count_include_pad") = true)
+        .def("global_avg_pool", &Var::global_avg_pool).def("flatten", &Var::flatten)
         .def("softmax", &Var::softmax).def("log_softmax", &Var::log_softmax).def("t", &Var::t)
         .def("layer_norm", py::overload_cast<const Var&, const Var&, double>(&Var::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const VarDiff&, const VarDiff&, double>(&Var::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
@@ -140,6 +143,9 @@ PYBIND11_MODULE(_tape, m) {
         .def("__neg__", &VarDiff::neg).def("pow", &VarDiff::pow).def("sqrt", &VarDiff::sqrt).def("leaky_relu", &VarDiff::leaky_relu)
         .def("softplus", &VarDiff::softplus).def("sigmoid", &VarDiff::sigmoid).def("tanh", &VarDiff::tanh).def("ln", &VarDiff::ln)
         .def("exp", &VarDiff::exp).def("unsqueeze", &VarDiff::unsqueeze)
+        .def("max_pool", &VarDiff::max_pool, py::arg("kernel"), py::arg("stride") = std::vector<int>{}, py::arg("padding") = std::vector<int>{})
+        .def("avg_pool", &VarDiff::avg_pool, py::arg("kernel"), py::arg("stride") = std::vector<int>{}, py::arg("padding") = std::vector<int>{}, py::arg("count_include_pad") = true)
+        .def("global_avg_pool", &VarDiff::global_avg_pool).def("flatten", &VarDiff::flatten)
         .def("softmax", &VarDiff::softmax).def("log_softmax", &VarDiff::log_softmax).def("t", &VarDiff::t)
         .def("layer_norm", py::overload_cast<const VarDiff&, const VarDiff&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const Var&, const Var&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
@@ -388,6 +394,29 @@ PYBIND11_MODULE(_tape, m) {
     py::class_<nn::BatchNorm3d, nn::BatchNormNd>(nn, "BatchNorm3d")
         .def(py::init<DevicePtr, int, double, double, bool, bool>(), py::arg("dev"), py::arg("num_features"), py::arg("eps") = 1e-5,
              py::arg("momentum") = 0.1, py::arg("affine") = true, py::arg("track_running_stats") = true);
+    py::class_<nn::PoolNd>(nn, "PoolNd")
+        .def_readonly("kernel_size", &nn::PoolNd::kernel_size)
+        .def_readonly("stride", &nn::PoolNd::stride)
+        .def_readonly("padding", &nn::PoolNd::padding)
+        .def_readonly("count_include_pad", &nn::PoolNd::count_include_pad)
+        .def("forward", py::overload_cast<const Var&>(&nn::PoolNd::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::PoolNd::forward, py::const_));
+    py::class_<nn::MaxPool1d, nn::PoolNd>(nn, "MaxPool1d")
+        .def(py::init<int, int, int>(), py::arg("kernel_size"), py::arg("stride") = 0, py::arg("padding") = 0);
+    py::class_<nn::MaxPool2d, nn::PoolNd>(nn, "MaxPool2d")
+        .def(py::init<std::vector<int>, std::vector<int>, std::vector<int>>(), py::arg("kernel_size"), py::arg("stride") = std::vector<int>{},
+             py::arg("padding") = std::vector<int>{});
+    py::class_<nn::MaxPool3d, nn::PoolNd>(nn, "MaxPool3d")
+        .def(py::init<std::vector<int>, std::vector<int>, std::vector<int>>(), py::arg("kernel_size"), py::arg("stride") = std::vector<int>{},
+             py::arg("padding") = std::vector<int>{});
+    py::class_<nn::AvgPool1d, nn::PoolNd>(nn, "AvgPool1d")
+        .def(py::init<int, int, int, bool>(), py::arg("kernel_size"), py::arg("stride") = 0, py::arg("padding") = 0, py::arg("count_include_pad") = true);
+    py::class_<nn::AvgPool2d, nn::PoolNd>(nn, "AvgPool2d")
+        .def(py::init<std::vector<int>, std::vector<int>, std::vector<int>, bool>(), py::arg("kernel_size"), py::arg("stride") = std::vector<int>{},
+             py::arg("padding") = std::vector<int>{}, py::arg("count_include_pad") = true);
+    py::class_<nn::AvgPool3d, nn::PoolNd>(nn, "AvgPool3d")
+        .def(py::init<std::vector<int>, std::vector<int>, std::vector<int>, bool>(), py::arg("kernel_size"), py::arg("stride") = std::vector<int>{},
+             py::arg("padding") = std::vector<int>{}, py::arg("count_include_pad") = true);
     py::class_<nn::Dropout>(nn, "Dropout")
         .def(py::init<double>())
         .def("train", &nn::Dropout::train)

@@ -585,6 +585,57 @@ int nk_batch_norm_bwd_assign(nk_device* dev, float* dx, const float* g, const fl
 int nk_batch_norm_bwd_params(nk_device* dev, float* dgamma, float* dbeta, const float* sums, int C);
 int nk_batch_norm_bwd_params_assign(nk_device* dev, float* dgamma, float* dbeta, const float* sums, int C);
 
+/* ------------------------------------------------------------------ pooling */
+/* Max and average pooling of a contiguous f32 tensor x of shape (N, C, in_1 .. in_nd), nd = 1, 2, 3.  The reference has no pooling;
+ * the semantics are fixed here and they are torch's (max_pool / avg_pool 1d, 2d, 3d).  Per spatial axis i: window k_i >= 1, stride
+ * s_i >= 1, symmetric padding 0 <= p_i <= k_i / 2.  Dilation is 1 and the output extent is floored: there is no ceil_mode and no
+ * dilation argument.
+ *   out_i = (in_i + 2 p_i - k_i) / s_i + 1            (integer division)
+ * x_shape has 2 + nd entries, kernel / stride / padding nd entries each.  NK_ERR_INVALID, with nothing launched and nothing written:
+ * nd outside 1..3, a negative N or C, in_i < 1, a parameter outside the ranges above, out_i <= 0 (the window exceeds the padded
+ * extent), or a plane (prod in_i or prod out_i) that does not fit in 31 bits.  nk_pool_out_shape is that arithmetic and those rules on
+ * the host (y_shape: 2 + nd entries; no device is needed); the other six entries call it.  N * C == 0 returns NK_OK and writes
+ * nothing, the _assign twins included.
+ * Max pooling.  y[n][c][o] = the maximum over the in-range positions of window o; padding is never selected (it acts as -inf).
+ *   idx[n][c][o] (int32) = the offset of the selected element inside its own (n, c) input plane, (d * in_2 + h) * in_3 + w: what
+ *   torch's return_indices gives.  Ties: the first maximum in row-major window order (a later element replaces the held one only if
+ *   it compares greater).  A NaN in the window makes y NaN and idx the offset of the first NaN met; a window of nothing but -inf gives
+ *   -inf and the first in-range offset.  idx may be NULL in the forward.
+ *   bwd:  dx[n][c][idx[n][c][o]] += g[n][c][o] for every o.  Windows overlap whenever s < k: several outputs can route to one element.
+ * Average pooling.  y = (sum over the in-range positions, row-major, f32) / divisor; divisor = prod k_i with count_include_pad != 0
+ *   (torch's default), the number of in-range positions otherwise.
+ *   bwd:  dx[i] += sum over the windows o that contain i of g[o] / divisor(o).
+ * Global average pooling is avg_pool with k_i = s_i = in_i and p_i = 0 (the plane class below).
+ * No atomics: both backward passes are gathers - a thread owns input elements and walks the covering outputs (at most
+ * prod ceil(k_i / s_i)) in ascending row-major order of o, adding g[o] where idx[o] is its own offset (max) or g[o] / divisor(o)
+ * (average).  The order of every sum is a function of the geometry and the pointers' 16-byte alignment alone: every output repeats bit
+ * for bit.  Nothing here synchronises, allocates or uses the workspace, and no block waits on another: every call can be captured
+ * into a graph.  A non-finite value stays inside the windows that hold it.
+ * Kernel classes, chosen inside each call:
+ *   plane     every out_i == 1 with k_i == in_i and p_i == 0: 16 / 64 / 256 lanes own one contiguous plane of L = prod in_i floats
+ *             (L <= 128 / <= 16384 / larger), each lane summing (or scanning) every G-th element or 16-byte group (L % 4 == 0, x
+ *             16-byte aligned) in ascending order, the lanes' results merged by a butterfly; max pooling carries (value, offset)
+ *             pairs.  Backward: 16-byte stores when L % 4 == 0 and dx is 16-byte aligned, the generic kernel otherwise.
+ *   windowed  nd <= 2 (or in_1 == 1 of 3) with (k, s, p) of the innermost axis one of 2/2/0, 3/2/0, 3/2/1, 3/1/0, 3/1/1, any window on
+ *             the other axis, in_W % 4 == 0 and x (forward) / dx (backward) 16-byte aligned: a lane makes four adjacent outputs from
+ *             16-byte loads (y and idx leave as 16-byte stores when out_W % 4 == 0 and they are aligned), or owns 16 bytes of dx.
+ *             Sums in the same order as the generic class.
+ *   generic   everything else (nd = 3, other windows, ragged widths, unaligned pointers): scalar kernels.
+ * The `_assign` twins write what their `+=` twin would leave in an all-zero dx, without reading it. */
+int nk_pool_out_shape(int nd, const int* x_shape, const int* kernel, const int* stride, const int* padding, int* y_shape);
+int nk_max_pool_fwd(nk_device* dev, int nd, const float* x, const int* x_shape, float* y, int* idx, const int* kernel,
+                    const int* stride, const int* padding);
+int nk_max_pool_bwd(nk_device* dev, int nd, float* dx, const int* x_shape, const float* g, const int* idx, const int* kernel,
+                    const int* stride, const int* padding);
+int nk_max_pool_bwd_assign(nk_device* dev, int nd, float* dx, const int* x_shape, const float* g, const int* idx,
+                           const int* kernel, const int* stride, const int* padding);
+int nk_avg_pool_fwd(nk_device* dev, int nd, const float* x, const int* x_shape, float* y, const int* kernel, const int* stride,
+                    const int* padding, int count_include_pad);
+int nk_avg_pool_bwd(nk_device* dev, int nd, float* dx, const int* x_shape, const float* g, const int* kernel, const int* stride,
+                    const int* padding, int count_include_pad);
+int nk_avg_pool_bwd_assign(nk_device* dev, int nd, float* dx, const int* x_shape, const float* g, const int* kernel,
+                           const int* stride, const int* padding, int count_include_pad);
+
 /* ------------------------------------------------------------------ fused attention core ---
  * The composed multi-head attention's per-(sample, head) chain in one kernel per direction (SURVEY.md 8a note; the
  * composition is MatrixMatrixMulT node/matrix_matrix_mul_t/mod.rs:31-41, Multiplication node/multiplication/mod.rs:39-50,

@@ -133,6 +133,47 @@ batch_norm_layer!(BatchNorm1d, [2usize, 3], "Batch normalisation of `(N, C)` or 
 batch_norm_layer!(BatchNorm2d, [4usize], "Batch normalisation of `(N, C, H, W)` inputs.");
 batch_norm_layer!(BatchNorm3d, [5usize], "Batch normalisation of `(N, C, D, H, W)` inputs.");
 
+/// Max / average pooling layers (the reference has none; semantics in `include/neuronika_hip.h`), torch's `MaxPool1d / 2d / 3d` and
+/// `AvgPool1d / 2d / 3d` in floor mode with dilation 1: no parameters; an empty `stride` means `stride = kernel_size`.
+macro_rules! pool_layer {
+    ($name:ident, $nd:expr, $average:expr, $doc:expr) => {
+        #[doc = $doc]
+        pub struct $name {
+            pub kernel_size: Vec<usize>,
+            pub stride: Vec<usize>,
+            pub padding: Vec<usize>,
+            pub count_include_pad: bool,
+        }
+
+        impl $name {
+            pub fn new(kernel_size: &[usize], stride: &[usize], padding: &[usize]) -> Self {
+                assert!(kernel_size.len() == $nd, "{}: kernel_size takes {} entries", stringify!($name), $nd);
+                let stride = if stride.is_empty() { kernel_size } else { stride };
+                let padding = if padding.is_empty() { vec![0; $nd] } else { padding.to_vec() };
+                assert!(stride.len() == $nd && padding.len() == $nd, "{}: stride and padding take {} entries", stringify!($name), $nd);
+                Self { kernel_size: kernel_size.to_vec(), stride: stride.to_vec(), padding, count_include_pad: true }
+            }
+
+            /// ONE forward node and ONE backward entry (`nk_max_pool_fwd` / `nk_max_pool_bwd`, `nk_avg_pool_fwd` / `nk_avg_pool_bwd`).
+            pub fn forward<D: Dimension + 'static>(&self, input: HipVarDiff<D>) -> HipVarDiff<D> {
+                assert!(input.shape().len() == $nd + 2, "{}: an input of {} dimensions", stringify!($name), input.shape().len());
+                if $average {
+                    input.avg_pool(&self.kernel_size, &self.stride, &self.padding, self.count_include_pad)
+                } else {
+                    input.max_pool(&self.kernel_size, &self.stride, &self.padding)
+                }
+            }
+        }
+    };
+}
+
+pool_layer!(MaxPool1d, 1usize, false, "Max pooling of `(N, C, L)` inputs.");
+pool_layer!(MaxPool2d, 2usize, false, "Max pooling of `(N, C, H, W)` inputs.");
+pool_layer!(MaxPool3d, 3usize, false, "Max pooling of `(N, C, D, H, W)` inputs.");
+pool_layer!(AvgPool1d, 1usize, true, "Average pooling of `(N, C, L)` inputs (`count_include_pad` is a public field, `true` after `new`).");
+pool_layer!(AvgPool2d, 2usize, true, "Average pooling of `(N, C, H, W)` inputs (`count_include_pad` is a public field, `true` after `new`).");
+pool_layer!(AvgPool3d, 3usize, true, "Average pooling of `(N, C, D, H, W)` inputs (`count_include_pad` is a public field, `true` after `new`).");
+
 /// Layer normalisation over the trailing dimensions `normalized_shape` of the input (the reference has no normalisation layer;
 /// semantics in `include/neuronika_hip.h`): `y = (x - mean) / sqrt(var + eps) * weight + bias` per row, biased variance.
 /// `weight` starts as ones, `bias` as zeros, both of `normalized_shape` (dimension `E`).

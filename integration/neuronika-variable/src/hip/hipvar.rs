@@ -12,12 +12,14 @@ use ndarray::{DimMax, Dimension, IntoDimension, Ix0, Ix1, Ix2, Ix3, RemoveAxis};
 
 use super::{
     device::Device,
+    ffi,
     dp::GradientSync,
     hiparray::HipArray,
     node::{
         AttentionState, BinaryOp, BinaryOperation, BinaryOperationBackwardLeft, BinaryOperationBackwardRight, Chunk, ChunkBackward,
         Convolution, ConvolutionBackwardInput, ConvolutionBackwardKernel, ConvolutionBackwardKernelBias, ConvolutionBackwardPadded, ConvolutionBias,
         ConvolutionBiasPadded, Dropout,
+        AvgPool, AvgPoolBackward, MaxPool, MaxPoolBackward,
         DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
@@ -35,6 +37,25 @@ use crate::{
 
 type Fwd = History<(Rc<dyn Forward>, Cell<bool>)>;
 type Bwd = History<(Rc<dyn Backward>, Rc<dyn NoGrad>)>;
+
+/// Host side of the pooling geometry (`nk_pool_out_shape` holds the rules): the per-axis vectors for the C ABI and the output dimension.
+/// An empty `stride` means `stride = kernel`.
+fn pool_setup<D: Dimension>(dim: &D, kernel: &[usize], stride: &[usize], padding: &[usize]) -> (D, Vec<i32>, Vec<i32>, Vec<i32>) {
+    let xs: Vec<i32> = dim.slice().iter().map(|&e| e as i32).collect();
+    assert!((3..=5).contains(&xs.len()), "pooling: the input must be (N, C, spatial...) with 1 to 3 spatial axes");
+    let nd = xs.len() - 2;
+    let stride = if stride.is_empty() { kernel } else { stride };
+    assert!(kernel.len() == nd && stride.len() == nd && padding.len() == nd, "pooling: kernel, stride and padding take {} entries each", nd);
+    let to_c = |v: &[usize]| v.iter().map(|&e| e as i32).collect::<Vec<i32>>();
+    let (k, s, p) = (to_c(kernel), to_c(stride), to_c(padding));
+    let mut ys = vec![0i32; xs.len()];
+    ffi::check(unsafe { ffi::nk_pool_out_shape(nd as i32, xs.as_ptr(), k.as_ptr(), s.as_ptr(), p.as_ptr(), ys.as_mut_ptr()) });
+    let mut out = dim.clone();
+    for (o, &y) in out.slice_mut().iter_mut().zip(&ys) {
+        *o = y as usize;
+    }
+    (out, k, s, p)
+}
 
 fn shared<D: Dimension>(dim: D, device: &Device) -> Shared<HipArray<D>> {
     Rc::new(RefCell::new(HipArray::zeroed(dim, device.clone())))
@@ -241,6 +262,34 @@ where
     pub fn batch_norm(self, gamma: HipVar<Ix1>, beta: HipVar<Ix1>, running: Option<(HipVar<Ix1>, HipVar<Ix1>)>, momentum: f64, eps: f64,
                       status: Rc<Cell<bool>>) -> HipVar<D> {
         self.batch_norm_with_stats(gamma, beta, running, momentum, eps, status, None)
+    }
+
+    /// Max pooling over the spatial axes (ours, the reference has no pooling; semantics in `include/neuronika_hip.h`).  `indices` = the
+    /// offsets buffer a backward node will read, `None` for the no-gradient form (`max_pool`).
+    pub(crate) fn max_pool_with_indices(self, kernel: &[usize], stride: &[usize], padding: &[usize], indices: Option<Shared<HipArray<D>>>) -> HipVar<D> {
+        let (dim, k, s, p) = pool_setup(&self.data.borrow().dimension(), kernel, stride, padding);
+        let data = shared(dim, &self.device());
+        let op = MaxPool::new(self.data, data.clone(), indices, k, s, p);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    pub fn max_pool(self, kernel: &[usize], stride: &[usize], padding: &[usize]) -> HipVar<D> {
+        self.max_pool_with_indices(kernel, stride, padding, None)
+    }
+
+    /// Average pooling; `count_include_pad` divides by the window size, otherwise by the number of in-range positions.
+    pub fn avg_pool(self, kernel: &[usize], stride: &[usize], padding: &[usize], count_include_pad: bool) -> HipVar<D> {
+        let (dim, k, s, p) = pool_setup(&self.data.borrow().dimension(), kernel, stride, padding);
+        let data = shared(dim, &self.device());
+        let op = AvgPool::new(self.data, data.clone(), k, s, p, count_include_pad);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    /// `avg_pool` over the whole spatial extents: `(N, C, 1, ..)`.
+    pub fn global_avg_pool(self) -> HipVar<D> {
+        let extents: Vec<usize> = self.data.borrow().dimension().slice()[2..].to_vec();
+        let zeros = vec![0usize; extents.len()];
+        self.avg_pool(&extents, &extents, &zeros, true)
     }
 
     /// `Var::log_softmax` (`var.rs:332-344`).
@@ -629,6 +678,31 @@ where
         let op: Rc<dyn Backward> = Rc::new(BatchNormBackward::new(input_data, gamma_data, stats, sums, trained, Some(self.grad.clone()),
                                                                    gamma.grad.clone(), beta.grad.clone(), grad.clone()));
         HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
+    }
+
+    /// Max pooling: the forward node writes the offsets of the selected elements, the backward node gathers through them.
+    pub fn max_pool(self, kernel: &[usize], stride: &[usize], padding: &[usize]) -> HipVarDiff<D> {
+        let (dim, k, s, p) = pool_setup(&self.var.data.borrow().dimension(), kernel, stride, padding);
+        let indices = shared(dim.clone(), &self.var.device());
+        let grad = self.new_grad(dim);
+        let var = self.var.max_pool_with_indices(kernel, stride, padding, Some(indices.clone()));
+        let op = MaxPoolBackward::new(self.grad.clone(), indices, grad.clone(), k, s, p);
+        HipVarDiff::node(var, grad.clone(), (Rc::new(op), grad), self.history)
+    }
+
+    pub fn avg_pool(self, kernel: &[usize], stride: &[usize], padding: &[usize], count_include_pad: bool) -> HipVarDiff<D> {
+        let (dim, k, s, p) = pool_setup(&self.var.data.borrow().dimension(), kernel, stride, padding);
+        let grad = self.new_grad(dim);
+        let var = self.var.avg_pool(kernel, stride, padding, count_include_pad);
+        let op = AvgPoolBackward::new(self.grad.clone(), grad.clone(), k, s, p, count_include_pad);
+        HipVarDiff::node(var, grad.clone(), (Rc::new(op), grad), self.history)
+    }
+
+    /// `avg_pool` over the whole spatial extents: `(N, C, 1, ..)`.
+    pub fn global_avg_pool(self) -> HipVarDiff<D> {
+        let extents: Vec<usize> = self.var.data.borrow().dimension().slice()[2..].to_vec();
+        let zeros = vec![0usize; extents.len()];
+        self.avg_pool(&extents, &extents, &zeros, true)
     }
 
     /// `VarDiff::log_softmax` (`vardiff.rs:381-387`).

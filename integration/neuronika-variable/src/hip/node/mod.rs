@@ -3,7 +3,7 @@
 //! reference's ndarray nodes (`node/*/mod.rs`), so graph construction code is unchanged.  Written here: the nodes of
 //! the BASELINE configurations (MatMul / MatMulT, Convolution, broadcast binaries, ReLU, Softmax, Dropout, Sum,
 //! SquaredError, the fused attention core of the composed MHA) and their glue (LogSoftmax, Mean, Pad in all four modes, Chunk,
-//! MultiConcatenate, Transpose, the SGD / Adam steps) and the layer and batch normalisation the reference lacks.  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
+//! MultiConcatenate, Transpose, the SGD / Adam steps) and the layer and batch normalisation and the max / average pooling the reference lacks.  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
 mod attention;
 mod binary_op;
 mod convolution;
@@ -14,6 +14,7 @@ mod matrix_matrix_mul_t;
 mod normalization;
 mod optim;
 mod pointwise;
+mod pooling;
 mod reduction;
 
 pub(crate) use attention::*;
@@ -26,6 +27,7 @@ pub(crate) use matrix_matrix_mul_t::*;
 pub(crate) use normalization::*;
 pub(crate) use optim::*;
 pub(crate) use pointwise::*;
+pub(crate) use pooling::*;
 pub(crate) use reduction::*;
 
 use std::rc::Rc;

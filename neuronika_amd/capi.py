@@ -173,6 +173,13 @@ _SIGS = {
     "nk_batch_norm_bwd_assign": [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int],
     "nk_batch_norm_bwd_params": [VP, VP, VP, VP, C.c_int],
     "nk_batch_norm_bwd_params_assign": [VP, VP, VP, VP, C.c_int],
+    "nk_pool_out_shape": [C.c_int, c_intp, c_intp, c_intp, c_intp, c_intp],
+    "nk_max_pool_fwd": [VP, C.c_int, VP, c_intp, VP, VP, c_intp, c_intp, c_intp],
+    "nk_max_pool_bwd": [VP, C.c_int, VP, c_intp, VP, VP, c_intp, c_intp, c_intp],
+    "nk_max_pool_bwd_assign": [VP, C.c_int, VP, c_intp, VP, VP, c_intp, c_intp, c_intp],
+    "nk_avg_pool_fwd": [VP, C.c_int, VP, c_intp, VP, c_intp, c_intp, c_intp, C.c_int],
+    "nk_avg_pool_bwd": [VP, C.c_int, VP, c_intp, VP, c_intp, c_intp, c_intp, C.c_int],
+    "nk_avg_pool_bwd_assign": [VP, C.c_int, VP, c_intp, VP, c_intp, c_intp, c_intp, C.c_int],
     "nk_attention_supported": [C.c_int, C.c_int, C.c_double, C.c_int],
     "nk_attention_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_attention_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double,
@@ -371,6 +378,16 @@ class Device:
         out.fill(value)
         return out
 
+    def int_array(self, a) -> "HipIntArray":
+        """int32 device array holding `a` (the `idx` of max pooling)"""
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        out = HipIntArray(self, a.shape)
+        out.upload(a)
+        return out
+
+    def int_zeros(self, shape) -> "HipIntArray":
+        return HipIntArray(self, shape)
+
     def close(self):
         if self.h and self._own:
             lib.nk_device_destroy(self.h)
@@ -444,6 +461,33 @@ class HipArray:
                 lib.nk_free(self.dev.h, self.p)
         except Exception:
             pass
+
+
+class HipIntArray(HipArray):
+    """int32 twin of HipArray: the same 4-byte cells, moved as they are (the `idx` output of max pooling)"""
+
+    def upload(self, a: np.ndarray):
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        assert a.size == self.size, (a.shape, self.shape)
+        check(lib.nk_upload(self.dev.h, self.p, a.ctypes.data_as(VP), self.size))
+        return self
+
+    def numpy(self) -> np.ndarray:
+        out = np.empty(self.shape, dtype=np.int32)
+        check(lib.nk_download(self.dev.h, out.ctypes.data_as(VP), self.p, self.size))
+        return out
+
+    def item(self) -> int:
+        return int(self.numpy().reshape(-1)[0])
+
+    def fill(self, v: int):
+        return self.upload(np.full(self.shape, int(v), dtype=np.int32))
+
+    def view_offset(self, first: int) -> "HipIntArray":
+        v = HipIntArray.__new__(HipIntArray)
+        v.dev, v.shape, v.size, v._parent = self.dev, (self.size - first,), self.size - first, self
+        v.p = VP(self.p.value + 4 * int(first))
+        return v
 
 
 KERNEL_SGEMM, KERNEL_CONV, KERNEL_ATTENTION = 0, 1, 2
@@ -768,6 +812,34 @@ def batch_norm_bwd(dev, dx, g, x, gamma, stats, sums, N, C, L, assign=False):
 def batch_norm_bwd_params(dev, dgamma, dbeta, sums, C, assign=False):
     """either of `dgamma`, `dbeta` may be None"""
     check((lib.nk_batch_norm_bwd_params_assign if assign else lib.nk_batch_norm_bwd_params)(dev.h, _p(dgamma), _p(dbeta), _p(sums), int(C)))
+
+
+def pool_out_shape(x_shape, kernel, stride, padding):
+    """nk_pool_out_shape: (N, C, out...) of a pooling with these per-axis windows, strides and paddings; raises NeuronikaHipError
+    for a geometry outside the header's contract.  Needs no device."""
+    nd = len(x_shape) - 2
+    out = (C.c_int * max(1, len(x_shape)))()
+    check(lib.nk_pool_out_shape(nd, ints(x_shape), ints(kernel), ints(stride), ints(padding), out))
+    return tuple(out[i] for i in range(len(x_shape)))
+
+
+def max_pool_fwd(dev, x, x_shape, y, idx, kernel, stride, padding):
+    """`x_shape` = (N, C, in...) gives the geometry (`x`, `y` may be flat or offset views); `idx`: a HipIntArray or None"""
+    check(lib.nk_max_pool_fwd(dev.h, len(x_shape) - 2, _p(x), ints(x_shape), _p(y), _p(idx), ints(kernel), ints(stride), ints(padding)))
+
+
+def max_pool_bwd(dev, dx, x_shape, g, idx, kernel, stride, padding, assign=False):
+    check((lib.nk_max_pool_bwd_assign if assign else lib.nk_max_pool_bwd)(dev.h, len(x_shape) - 2, _p(dx), ints(x_shape), _p(g), _p(idx), ints(kernel),
+                                                                          ints(stride), ints(padding)))
+
+
+def avg_pool_fwd(dev, x, x_shape, y, kernel, stride, padding, count_include_pad=True):
+    check(lib.nk_avg_pool_fwd(dev.h, len(x_shape) - 2, _p(x), ints(x_shape), _p(y), ints(kernel), ints(stride), ints(padding), int(bool(count_include_pad))))
+
+
+def avg_pool_bwd(dev, dx, x_shape, g, kernel, stride, padding, count_include_pad=True, assign=False):
+    check((lib.nk_avg_pool_bwd_assign if assign else lib.nk_avg_pool_bwd)(dev.h, len(x_shape) - 2, _p(dx), ints(x_shape), _p(g), ints(kernel), ints(stride),
+                                                                          ints(padding), int(bool(count_include_pad))))
 
 
 def dropout_fwd(dev, x, y, noise, p, train=True, seed=0, offset=0):
