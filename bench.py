@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the neuronika HIP backend on MI355X.
 
-    python bench.py --gpus 1 --steps 200 --warmup 5
+    python bench.py --gpus 1 --steps 200 --warmup 5            # the headline figure and nothing else
+    python bench.py --gpus 1 --steps 200 --warmup 5 --full     # + CPU baselines, the other configurations, diagnostics
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N            # no launcher: spawns the N ranks itself (one process per GPU)
@@ -19,31 +20,35 @@ One "step" = forward, re-zero the intermediate gradients, backward(seed = 1/N) w
 overlapped all-reduce, join, SGD step and zero_grad — the whole training step through the
 C++ tape mirror (host/neuronika.hpp) and the C-ABI HIP library; nothing is skipped.
 
-One JSON line is printed by rank 0.  `value` = samples/s of the whole job.  `roofline` is for
-the dominant kernel (the f32 MFMA GEMM): achieved = algorithmic flop of the GEMM launches in
-the timed region / their summed HIP-event durations (events on the compute stream, recorded
-inside the library around every launch).  `cpu_baseline` = the CPU oracle (a NumPy/OpenBLAS
-restatement of the reference's ndarray path; the Rust reference cannot be built here) timed
-on this host on a bounded sample, rank 0, N = 1 only, in the two variants BASELINE.md section 4
-names: "reference-default" (1 BLAS thread for mm / mm_t = the single-threaded matrixmultiply
-sgemm of the default features, neuronika-variable/Cargo.toml:25-29; all cores for the
-convolution, which is rayon batch-parallel, node/convolution/mod.rs:110-122) and
-"reference+blas" (OpenBLAS on all cores = the `blas` feature).  The default line also carries
-`matmul_4096` (the second half of BASELINE.json's metric: C2 at N = 4096, fwd+bwd, TFLOP/s and
-fraction of the f32 MFMA peak), `rccl_ranks`, `allreduce_bytes_per_step` and `exposed_comm_ms`
-(step time minus the step time of the same loop with the gradient exchange switched off).
+One JSON line is printed by rank 0.  A plain run does what its headline figure needs and nothing else: set-up, the W
+warm-up steps and the clock settle phase, the K timed steps, the dump if `--dump-outputs` is given, the line.  `value` =
+samples/s of the whole job.  `roofline` is for the dominant kernel (the f32 MFMA GEMM): achieved = algorithmic flop of the
+GEMM launches in the timed region / their summed HIP-event durations (events on the compute stream, recorded inside the
+library around every launch) - a by-product of the timed steps, so every line has it.
 
-At N = 1 the default line additionally carries every other BASELINE configuration as a sub-record of the same shape
-(value, ms_per_step, roofline{achieved, frac, launches, avg_launch_ms}), SUB_STEPS timed steps each after the clock
-settle phase: `matmul_1024 / _2048 / _4096 / _8192` (C2), `conv_c3` (C3) and `mha_c5` (C5, with `attention_core`) -
-about 3 s of GPU time in total - so that one driver-run record holds all headline numbers.
+`--full` adds everything that takes runs of its own (about half a minute at N = 1); the timed steps and the headline fields
+are the plain run's.
+* `cpu_baseline` = the CPU oracle (a NumPy/OpenBLAS restatement of the reference's ndarray path; the Rust reference cannot
+  be built here) timed on this host on a bounded sample, rank 0, N = 1 only, in the two variants BASELINE.md section 4
+  names: "reference-default" (1 BLAS thread for mm / mm_t = the single-threaded matrixmultiply sgemm of the default
+  features, neuronika-variable/Cargo.toml:25-29; all cores for the convolution, which is rayon batch-parallel,
+  node/convolution/mod.rs:110-122) and "reference+blas" (OpenBLAS on all cores = the `blas` feature).
+  `--no-cpu-baseline` leaves it out of a `--full` run.
+* At N = 1 every other BASELINE configuration as a sub-record of the same shape (value, ms_per_step, roofline{achieved,
+  frac, launches, avg_launch_ms}), SUB_STEPS timed steps each after the clock settle phase: `matmul_1024 / _2048 / _4096 /
+  _8192` (C2; `matmul_4096` is the second half of BASELINE.json's metric: fwd+bwd, TFLOP/s and fraction of the f32 MFMA
+  peak), `conv_c3` (C3) and `mha_c5` (C5, with `attention_core`), and the HBM-bound kernels (`hbm_kernels`) - about 3 s of
+  GPU time in total - so that one record holds all headline numbers.
+* At N > 1 the line becomes self-diagnosing: a stand-alone all-reduce of the step's gradient bytes before the timed loop
+  (`allreduce_alone`: ms, algorithm and bus GB/s, also at the bucket sizes the step uses), `exposed_comm_ms` (step time
+  minus the step time of the same loop with the gradient exchange switched off), the GEMM launch time with and without
+  the overlapped exchange (`gemm_contention`), what RCCL chose (`rccl`: version, channels, algorithm / protocol per
+  message size, parsed from rank 0's NCCL_DEBUG=INFO log) and `matmul_4096`.
+* `--workload matmul`: the `roofline` of the GEMM launches (a second pass of K steps with HIP events around them).
 
-At N > 1 the line is self-diagnosing: per-rank device ms/step (`per_rank_device_ms_per_step`, min / max), a stand-alone
-all-reduce of the step's gradient bytes before the timed loop (`allreduce_alone`: ms, algorithm and bus GB/s, also at
-the bucket sizes the step uses), `exposed_comm_ms`, the GEMM launch time with and without the overlapped exchange
-(`gemm_contention`), and what RCCL chose (`rccl`: version, channels, algorithm / protocol per message size, parsed from
-rank 0's NCCL_DEBUG=INFO log).  Every rank arms a watchdog (NK_BENCH_TIMEOUT_S, default 600 s) that dumps the Python
-stack of a hung rank and exits; the self-spawning launcher has an overall timeout and relays the last 2 KB of every
+Every N > 1 line carries `rccl_ranks`, `allreduce_bytes_per_step` and the per-rank device ms/step
+(`per_rank_device_ms_per_step`, min / max).  Every rank arms a watchdog (NK_BENCH_TIMEOUT_S, default 600 s) that dumps the
+Python stack of a hung rank and exits; the self-spawning launcher has an overall timeout and relays the last 2 KB of every
 rank's stderr when the job fails.
 
 `--dump-outputs DIR` (default workload) writes what the LAST timed step handed to its caller as DIR/<name>.npy, f32: the
@@ -101,7 +106,11 @@ def parse():
     ap.add_argument("--batch", type=int, default=4096, help="rows per GPU (mlp)")
     ap.add_argument("--n", type=int, default=4096, help="matrix size (matmul)")
     ap.add_argument("--no-optimizer", action="store_true", help="time fwd+bwd+allreduce only (metric's literal definition)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baselines, the other BASELINE "
+                         "configurations and the HBM-bound kernels as sub-records, the GEMM roofline pass of --workload matmul, "
+                         "the N > 1 diagnostics (stand-alone all-reduce, exposed communication, what RCCL chose)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--dp-channels", type=int, default=16,
                     help="N > 1: cap RCCL at this many channels (NCCL_MAX_NCHANNELS, unless the caller set it) and tell the GEMMs "
                          "that many resident-block slots are busy while the exchange runs; 0: RCCL's own choice, GEMMs plan for an idle chip")
@@ -428,10 +437,10 @@ class _CapiSync:  # adapt capi.Device to the `sync()` interface of the tape's De
     def sync(self): self.dev.sync()
 
 
-def matmul_fwd_bwd(dist, dev, n, steps, warmup):
+def matmul_fwd_bwd(dist, dev, n, steps, warmup, roofline=True):
     """C2 on device `dev` (capi.Device): C = A.B, then the node's backward dA += G.B^T, dB += A^T.G (one call: both products in
     one launch where neither fills the chip, nk_sgemm_pair's rule - 1024 and 2048; two launches at 4096 and 8192).  Returns (seconds for the K steps, max over
-    ranks, timed WITHOUT per-launch events; the GEMM launch statistics of a second pass of K steps with them)."""
+    ranks, timed WITHOUT per-launch events; the GEMM launch statistics of a second pass of K steps with them, None without `roofline`)."""
     from neuronika_amd import capi as c
     mk = lambda s: dev.array(np.random.default_rng(s).random((n, n), dtype=np.float32))
     A, B, G = mk(0), mk(1), mk(2)
@@ -441,24 +450,28 @@ def matmul_fwd_bwd(dist, dev, n, steps, warmup):
         c.mm_fwd(dev, A, B, Cm); c.mm_bwd(dev, dA, dB, G, A, B)   # MatrixMatrixMul::forward, MatrixMatrixMulBackward::backward
     sync = _CapiSync(dev)
     dt, _, _, _ = timed_steps(dist, sync, dev, step, steps, warmup, profile=False)
+    if not roofline:
+        return dt, None
     settle = EXTRA_STATS["settle_steps"]
     _, _, gemm, _ = timed_steps(dist, sync, dev, step, steps, 0)
     EXTRA_STATS["settle_steps"] = settle
     return dt, gemm
 
 
-def matmul_record(dist, dev, n, steps, warmup):
+def matmul_record(dist, dev, n, steps, warmup, roofline=True):
     """One C2 size as a record: value = whole fwd+bwd TFLOP/s (host clock over the K timed steps, no per-launch events),
     roofline = the GEMM launches themselves (HIP event pairs around the launches of a second pass of K steps, every
-    LAUNCH_EVENTS_EVERY-th step of it)."""
-    dt, gemm = matmul_fwd_bwd(dist, dev, n, steps, warmup)
+    LAUNCH_EVENTS_EVERY-th step of it; `roofline=False`: no second pass, no such fields)."""
+    dt, gemm = matmul_fwd_bwd(dist, dev, n, steps, warmup, roofline)
     tf = 6.0 * n ** 3 * steps / dt / 1e12
-    roof = roofline_mfma(gemm, "sgemm_kernel" if n >= 4096 else "sgemm_kernel (forward), sgemm_pair_kernel (both backward products, one launch)",
-                         "sgemm_kernel" if n == 4096 else None)
-    return {"workload": f"C2: mm fwd + bwd (left and right products), N={n}, {steps} steps", "value": round(tf, 2), "unit": "TFLOP/s",
-            "tflops": round(tf, 2), "frac_of_mfma_peak": round(tf * 1e12 / MFMA_F32_PEAK, 4),
-            "kernel_tflops": roof["achieved"], "kernel_frac": roof["frac"], "steps": steps,
-            "ms_per_step": round(dt / steps * 1e3, 4), "roofline": roof}
+    rec = {"workload": f"C2: mm fwd + bwd (left and right products), N={n}, {steps} steps", "value": round(tf, 2), "unit": "TFLOP/s",
+           "tflops": round(tf, 2), "frac_of_mfma_peak": round(tf * 1e12 / MFMA_F32_PEAK, 4), "steps": steps,
+           "ms_per_step": round(dt / steps * 1e3, 4)}
+    if roofline:
+        roof = roofline_mfma(gemm, "sgemm_kernel" if n >= 4096 else "sgemm_kernel (forward), sgemm_pair_kernel (both backward products, one launch)",
+                             "sgemm_kernel" if n == 4096 else None)
+        rec.update(kernel_tflops=roof["achieved"], kernel_frac=roof["frac"], roofline=roof)
+    return rec
 
 
 def measure_conv(dist, tdev, cdev, steps, warmup):
@@ -759,7 +772,7 @@ def run_mlp(a, dist):
         opt.zero_grad()
 
     alone = None
-    if real_rccl:   # before the timed loop: what the fabric gives an all-reduce with nothing else running
+    if real_rccl and a.full:   # before the timed loop: what the fabric gives an all-reduce with nothing else running
         total = sync.bytes_per_step()
         sizes = sorted({total, 4 * H * H, 2 * H * H}, reverse=True)   # everything / one weight gradient / the half the step hands over
         alone = allreduce_alone(dist, tdev, cdev, comm.raw(), sizes)
@@ -791,14 +804,14 @@ def run_mlp(a, dist):
         _log(f"dumped {len(arrays)} arrays, {dumped['bytes']} bytes, to {a.dump_outputs}")
     n_exch = sync.exchanges_issued() if sync is not None else 0
     per_rank = dist.gather(ev_ms / a.steps)
-    exposed, gemm_off = 0.0, None
-    if sync is not None:                           # the same loop with the exchange switched off: what the all-reduce costs
+    exposed, gemm_off = (0.0 if sync is None else None), None   # (None: not measured)
+    if sync is not None and a.full:                # the same loop with the exchange switched off: what the all-reduce costs
         exchange[0] = False
         dt_off, _, gemm_off, _ = timed_steps(dist, tdev, cdev, step, a.steps, 2)
         exposed = (dt - dt_off) / a.steps * 1e3
         _log(f"exchange off: {dt_off / a.steps * 1e3:.3f} ms/step")
     subs = {}
-    if world == 1 and not os.environ.get("NK_BENCH_NO_SUBRECORDS"):
+    if a.full and world == 1:
         # every other BASELINE configuration, same record shape, SUB_STEPS timed steps each (C2 at 4096: the second
         # half of BASELINE.json's metric, "MatMul MFMA %peak")
         for n in (1024, 2048, 4096, 8192):
@@ -812,7 +825,7 @@ def run_mlp(a, dist):
             subs["matmul_4096"]["cpu_baseline"] = cpu_baseline_matmul(4096, min_s=2.0)
             subs["conv_c3"]["cpu_baseline"] = cpu_baseline_conv(min_s=2.0)
             subs["mha_c5"]["cpu_baseline"] = cpu_baseline_mha(1, 1024, 1024, 16, 0.1, min_s=1.5)
-    elif os.environ.get("NK_BENCH_NO_SUBRECORDS") != "2":   # ("2": the C4 step alone - kernel traces of exactly this workload)
+    elif a.full:
         subs["matmul_4096"] = matmul_record(dist, cdev, 4096, SUB_STEPS, SUB_WARMUP)
     res = None
     if dist.rank == 0:
@@ -834,7 +847,7 @@ def run_mlp(a, dist):
             "allreduce_launches_per_step": n_exch // (a.steps + a.warmup + settle) if sync is not None else 0,
             "clock_settle_steps": settle,
             # (a replica communicator moves nothing over the fabric: its "exposed communication" is not one)
-            "exposed_comm_ms": None if replicas > 1 else round(exposed, 4),
+            "exposed_comm_ms": None if replicas > 1 or exposed is None else round(exposed, 4),
             "roofline": roofline_mfma(gemm, "sgemm_kernel (f32 MFMA 32x32x2, 128x128x32 tiles)", "sgemm_kernel"),
             **subs,
             "device_ms_per_step": round(ev_ms / a.steps, 4), "loss": loss_val,
@@ -846,6 +859,7 @@ def run_mlp(a, dist):
             res["dp_channels"] = {"nccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS"), "gemm_busy_slots": sync.busy_slots()}
             res["per_rank_device_ms_per_step"] = [round(v, 4) for v in per_rank]
             res["per_rank_device_ms_min_max"] = [round(min(per_rank), 4), round(max(per_rank), 4)]
+        if gemm_off is not None:
             # the same GEMM work per step with the exchange running beside it and without (sums of the HIP-event durations
             # of the step's GEMM launches: with the exchange on, the weight-gradient GEMMs are issued as two row blocks, so
             # launch counts differ and per-launch averages are not comparable)
@@ -861,7 +875,7 @@ def run_mlp(a, dist):
                                       "busbw_GBps": alone[0]["busbw_GBps"], "by_size": alone,
                                       "one_link_ring_floor_ms": round(ring_ms, 4)}
             res["rccl"] = read_rccl_log()
-        if world == 1 and not debug_run and not a.no_cpu_baseline:
+        if a.full and world == 1 and not debug_run and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_mlp(H, B)
     if comm is not None:
         tdev.sync()
@@ -893,14 +907,14 @@ def run_matmul(a, dist):
     """C2: C = A.B forward + dA += G.B^T, dB += A^T.G, f32 N x N."""
     from neuronika_amd import capi as c
     dev = c.Device(dist.local)
-    rec = matmul_record(dist, dev, a.n, a.steps, a.warmup)
+    rec = matmul_record(dist, dev, a.n, a.steps, a.warmup, roofline=a.full)
     if dist.rank != 0:
         return None
     rec["value"] = round(rec["value"] * dist.world, 2)
     res = _headline({"n_gpus": dist.world, "warmup": a.warmup}, rec, "MatMul fwd+bwd TFLOP/s (MFMA %peak)", {"n": a.n})
     for k in ("tflops", "frac_of_mfma_peak", "kernel_tflops", "kernel_frac"):
         res.pop(k, None)
-    if dist.world == 1 and not a.no_cpu_baseline:
+    if a.full and dist.world == 1 and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_matmul(a.n)
     return res
 
@@ -918,7 +932,7 @@ def run_conv(a, dist):
     if dist.rank != 0:
         return None
     res = _headline({"n_gpus": dist.world, "warmup": a.warmup}, rec, "Conv2d fwd+bwd samples/s")
-    if dist.world == 1 and not a.no_cpu_baseline:
+    if a.full and dist.world == 1 and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_conv(128)
     return res
 
@@ -929,7 +943,7 @@ def run_mha(a, dist):
     if dist.rank != 0:
         return None
     res = _headline({"n_gpus": dist.world, "warmup": a.warmup}, rec, "MultiheadAttention fwd+bwd sequences/s")
-    if dist.world == 1 and not a.no_cpu_baseline:
+    if a.full and dist.world == 1 and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_mha(2, 1024, 1024, 16, 0.1)
     return res
 
@@ -1034,7 +1048,7 @@ def main():
             # RCCL's channel workgroups share the CUs with the backward GEMMs: a known, small number of them (the step's
             # 201 MB of gradients need tens of GB/s, not the fabric's peak) that the GEMM launcher plans around
             os.environ.setdefault("NCCL_MAX_NCHANNELS", str(a.dp_channels))
-        if rank == 0 and "NCCL_DEBUG" not in os.environ:
+        if a.full and rank == 0 and "NCCL_DEBUG" not in os.environ:
             # what RCCL chose (channels, algorithm / protocol per size) goes into the record: rank 0 logs INIT + TUNING
             # to a file of its own, parsed after the run (read_rccl_log)
             fd, path = tempfile.mkstemp(prefix="nk_rccl_rank0_", suffix=".log")

@@ -77,10 +77,9 @@ def test_dump_outputs_is_refused_where_it_is_not_defined(tmp_path, argv):
 
 def _run(tmp_path, name, steps, warmup):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    env["NK_BENCH_NO_SUBRECORDS"] = "1"                         # the headline step alone
     out = tmp_path / name
     r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--hidden", "512",
-                        "--batch", "384", "--no-cpu-baseline", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, env=env)
+                        "--batch", "384", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     return line, {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}

@@ -295,3 +295,18 @@ def test_bench_is_torch_free():
     """bench.py must not import torch in-process (second HIP runtime; see rendezvous.py)."""
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")).read()
     assert "import torch" not in src
+
+
+def test_bench_full_is_an_option_off_by_default(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures its headline and nothing else: every record that takes runs of
+    its own (CPU baselines, sub-records, N > 1 diagnostics) waits for `--full`."""
+    import importlib.util, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("nk_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and (a.gpus, a.steps, a.warmup) == (1, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.no_cpu_baseline is True

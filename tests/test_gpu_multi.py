@@ -10,6 +10,7 @@ import os
 import socket
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -40,7 +41,7 @@ def test_bench_refuses_more_ranks_than_gpus():
 @pytest.mark.skipif(_ngpu() < 2, reason="needs two GPUs")
 def test_bench_self_spawns_two_ranks():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-                        "--hidden", "1024", "--batch", "512", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--hidden", "1024", "--batch", "512", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     res = json.loads(line)
@@ -122,10 +123,28 @@ def _bench_line(args, env_extra=None, timeout=900):
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]), r.stderr
 
 
+def test_bench_plain_run_does_only_what_its_headline_needs():
+    """`bench.py --gpus 1 --steps K --warmup W` with nothing else: set-up, warm-up, the K timed steps, the line - the headline
+    fields and the roofline the timed steps leave behind, none of the records that take runs of their own (`--full`), and
+    at most 30 s of the whole run, process start to exit, outside its steps."""
+    steps, warmup = 3, 1
+    t0 = time.perf_counter()
+    res, _ = _bench_line(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)])
+    outside = time.perf_counter() - t0 - (steps + warmup) * res["ms_per_step"] * 1e-3
+    assert res["metric"] == "training-step samples/sec (fwd+bwd+allreduce)" and res["unit"] == "samples/s"
+    assert res["higher_is_better"] is True and res["dtype"] == "f32" and res["n_gpus"] == 1 and res["steps"] == steps
+    assert res["ms_per_step"] > 0 and res["value"] == pytest.approx(4096 * 1e3 / res["ms_per_step"], rel=1e-3)
+    assert res["roofline"]["frac"] > 0 and res["roofline"]["launches"] > 0 and np.isfinite(res["loss"])
+    moved = [k for k in res if k.startswith("matmul_") or k in ("conv_c3", "mha_c5", "hbm_kernels", "cpu_baseline", "allreduce_alone",
+                                                                "gemm_contention", "rccl")]
+    assert moved == []
+    assert outside < 30.0, outside
+
+
 def test_bench_default_line_carries_every_baseline_config():
-    """The ONE driver-run record holds all headline numbers: C4 at the top level, C2 at 1024 / 2048 / 4096 / 8192,
+    """The ONE `--full` record holds all headline numbers: C4 at the top level, C2 at 1024 / 2048 / 4096 / 8192,
     C3 and C5 as sub-records of the same shape (value, ms_per_step, roofline{achieved, frac, launches, avg_launch_ms})."""
-    res, _ = _bench_line(["--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    res, _ = _bench_line(["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert res["n_gpus"] == 1 and res["roofline"]["frac"] > 0 and res["roofline"]["traffic_measured_at_commit"]
     for key, unit in [("matmul_1024", "TFLOP/s"), ("matmul_2048", "TFLOP/s"), ("matmul_4096", "TFLOP/s"), ("matmul_8192", "TFLOP/s"),
                       ("conv_c3", "samples/s"), ("mha_c5", "sequences/s")]:
@@ -150,7 +169,7 @@ def test_bench_multi_rank_record_is_self_diagnosing():
     """Every line of bench.py's N > 1 path on ONE GPU: a one-rank RCCL communicator with the exchange forced on
     (NK_BENCH_FORCE_RCCL=1).  The record must carry the diagnostics the first real multi-GPU run will be tuned from and
     must not be readable as a measurement."""
-    res, err = _bench_line(["--steps", "3", "--warmup", "1", "--hidden", "1024", "--batch", "512", "--no-cpu-baseline"],
+    res, err = _bench_line(["--steps", "3", "--warmup", "1", "--hidden", "1024", "--batch", "512", "--full", "--no-cpu-baseline"],
                            {"NK_BENCH_FORCE_RCCL": "1", "NK_BENCH_VERBOSE": "1"})
     assert res["rccl_single_rank_debug"] is True and res["metric"].startswith("DEBUG RUN")
     assert res["rccl_ranks"] == 1 and res["allreduce_bytes_per_step"] == 3 * (1024 * 1024 + 1024) * 4
@@ -170,8 +189,8 @@ def test_bench_multi_rank_record_is_self_diagnosing():
 
 
 def test_replica_debug_run_is_not_readable_as_a_measurement():
-    res, _ = _bench_line(["--steps", "2", "--warmup", "1", "--hidden", "1024", "--batch", "512", "--no-cpu-baseline"],
-                         {"NK_BENCH_REPLICAS": "4", "NK_BENCH_NO_SUBRECORDS": "1"})
+    res, _ = _bench_line(["--steps", "2", "--warmup", "1", "--hidden", "1024", "--batch", "512", "--full", "--no-cpu-baseline"],
+                         {"NK_BENCH_REPLICAS": "4"})
     assert res["metric"].startswith("DEBUG RUN") and res["exposed_comm_ms"] is None and res["replica_ranks_debug"] == 4
 
 

@@ -3,7 +3,7 @@
 # tests of the product path, then the weak-scaling bench at 2 / 4 / 8 GPUs, everything a post-mortem needs in one tarball.
 #     bash tools/first_multi_gpu.sh [OUTDIR]          (about 5 minutes on an 8-GPU node)
 # bench.py --gpus N spawns its own N ranks (one process per GPU, RCCL over xGMI, rendezvous on 127.0.0.1) and prints one JSON
-# line per run with per-rank device times, the stand-alone all-reduce, exposed communication and what RCCL chose.
+# line per run; with --full it carries per-rank device times, the stand-alone all-reduce, exposed communication and what RCCL chose.
 set -u
 root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 out=${1:-$root/gpurun_out/first_multi_gpu}
@@ -18,7 +18,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_multi.py -x -q > "$out/pytest_
 echo "pytest tests/test_gpu_multi.py rc=$?  $(tail -1 "$out/pytest_multi.log")" | tee -a "$out/summary.txt"
 for n in 1 2 4 8; do
   [ "$n" -gt "$ngpu" ] && break
-  NCCL_DEBUG=INFO NCCL_DEBUG_FILE="$out/rccl_n${n}_%h_%p.log" timeout -k 10 600 python bench.py --gpus $n --steps 50 --warmup 5 \
+  NCCL_DEBUG=INFO NCCL_DEBUG_FILE="$out/rccl_n${n}_%h_%p.log" timeout -k 10 600 python bench.py --gpus $n --steps 50 --warmup 5 --full \
       > "$out/bench_n$n.json" 2> "$out/bench_n$n.err"
   echo "bench --gpus $n rc=$?" | tee -a "$out/summary.txt"
   python - "$out/bench_n$n.json" <<'P' | tee -a "$out/summary.txt"
@@ -39,7 +39,7 @@ if [ "$nmax" -gt 1 ]; then
     for told in 1 0; do
       tag="n${nmax}_ch${ch}_told${told}"
       if [ "$told" = 1 ]; then flag="--dp-channels $ch"; env_ch=""; else flag="--dp-channels 0"; env_ch="NCCL_MAX_NCHANNELS=$ch"; fi
-      env $env_ch timeout -k 10 600 python bench.py --gpus $nmax --steps 50 --warmup 5 --no-cpu-baseline $flag \
+      env $env_ch timeout -k 10 600 python bench.py --gpus $nmax --steps 50 --warmup 5 --full --no-cpu-baseline $flag \
           > "$out/bench_$tag.json" 2> "$out/bench_$tag.err"
       python - "$out/bench_$tag.json" "$tag" <<'P' | tee -a "$out/summary.txt"
 import json, sys

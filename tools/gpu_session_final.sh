@@ -10,7 +10,7 @@ cd $root
 timeout -k 5 600 python -m pytest tests -m gpu -x -q > $out/z_pytest.log 2>&1; echo "pytest rc=$?" >> $out/z_pytest.log
 grep -E "passed|failed" $out/z_pytest.log | tail -2
 cp $out/tolerance_margins.json $out/${tag}_tolerance_margins.json
-timeout -k 5 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_driver_invocation.json 2> $out/z_bench_driver.err; echo "bench rc=$?"
+timeout -k 5 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/${tag}_bench_driver_invocation.json 2> $out/z_bench_driver.err; echo "bench rc=$?"
 bash tools/profile_round.sh gpurun_out/${tag}z $tag > $out/z_profile_round.log 2>&1
 bash tools/traffic_pmc.sh gpurun_out/${tag}z_traffic > $out/z_traffic.log 2>&1
 python tools/make_roofline_traffic.py gpurun_out/${tag}z_traffic $commit > $out/${tag}_traffic_pmc.md 2>> $out/z_traffic.log
