@@ -393,10 +393,20 @@ static int launch_epx(nk_device* dev, const GemmArgs& p, int nbatch, bool aligne
 }
 // the extended-epilogue kernels (EPX, see gemm_epilogue) where the launch needs them - and for every NT launch, which they run
 // 1.6 % faster at 4096^3 than the plain kernel does; the plain kernels elsewhere (TN: +3.2 %)
+// Only the instantiations an entry point can reach exist: every NT launch is an EPX one, and the epilogue functions come from
+// nk_linear_relu_fwd (NT) and nk_linear_bwd_input_relu (NN) alone - an A stored transposed (TN, TT) with ReLU or a mask is refused,
+// not instantiated (tests/dispatch_paths_mfma.py: a kernel nobody can launch is a kernel nobody has compared with anything).
 template <bool TA, bool TB>
 static int launch(nk_device* dev, const GemmArgs& p, int nbatch, bool aligned, int ti, int tj, int kg) {
-    const bool epx = p.relu || p.mask != nullptr || (!TA && TB);
-    return epx ? launch_epx<TA, TB, true>(dev, p, nbatch, aligned, ti, tj, kg) : launch_epx<TA, TB, false>(dev, p, nbatch, aligned, ti, tj, kg);
+    if constexpr (!TA && TB) {
+        return launch_epx<TA, TB, true>(dev, p, nbatch, aligned, ti, tj, kg);
+    } else if constexpr (TA) {
+        NK_CHECK(!p.relu && p.mask == nullptr, "GEMM with a transposed A has no ReLU / mask epilogue");
+        return launch_epx<TA, TB, false>(dev, p, nbatch, aligned, ti, tj, kg);
+    } else {
+        const bool epx = p.relu || p.mask != nullptr;
+        return epx ? launch_epx<TA, TB, true>(dev, p, nbatch, aligned, ti, tj, kg) : launch_epx<TA, TB, false>(dev, p, nbatch, aligned, ti, tj, kg);
+    }
 }
 
 // What gemm_impl decided for one problem: the kernel arguments and the instantiation (tile shape, k-pair, aligned loads).
@@ -430,6 +440,7 @@ static int gemm_plan(nk_device* dev, int transA, int transB, int M, int N, int K
     p.bias = bias;
     p.relu = relu; p.mask = mask; p.ldm = ldm;
     NK_CHECK(mask == nullptr || (nbatch == 1 && ldm >= N), "masked GEMM: one matrix, ldm >= N");
+    NK_CHECK(!transA || (!relu && mask == nullptr), "GEMM with a transposed A has no ReLU / mask epilogue");  // (never instantiated: launch())
     p.batch_inner = batch_inner;
     p.sAo = sAo; p.sAi = sAi; p.sBo = sBo; p.sBi = sBi; p.sCo = sCo; p.sCi = sCi;
 
@@ -570,9 +581,15 @@ static int gemm_plan(nk_device* dev, int transA, int transB, int M, int N, int K
 // along K.  `p`: the plan of an aligned, unsplit, unbatched 128x128-tile launch.  *taken = false: the grid divides (or the
 // tail cannot be cut usefully) - the caller launches as usual.
 template <bool TA, bool TB>
-static void launch_tail(nk_device* dev, const GemmTailArgs& pp, dim3 grid, bool epx) {
-    if (epx) hipLaunchKernelGGL((sgemm_tail_kernel<TA, TB, true>), grid, dim3(NT), 0, dev->compute, pp);
-    else hipLaunchKernelGGL((sgemm_tail_kernel<TA, TB, false>), grid, dim3(NT), 0, dev->compute, pp);
+static void launch_tail(nk_device* dev, const GemmTailArgs& pp, dim3 grid, bool epx) {  // (the same instantiation rule as launch())
+    if constexpr (!TA && TB) {
+        hipLaunchKernelGGL((sgemm_tail_kernel<TA, TB, true>), grid, dim3(NT), 0, dev->compute, pp);
+    } else if constexpr (TA) {
+        hipLaunchKernelGGL((sgemm_tail_kernel<TA, TB, false>), grid, dim3(NT), 0, dev->compute, pp);
+    } else {
+        if (epx) hipLaunchKernelGGL((sgemm_tail_kernel<TA, TB, true>), grid, dim3(NT), 0, dev->compute, pp);
+        else hipLaunchKernelGGL((sgemm_tail_kernel<TA, TB, false>), grid, dim3(NT), 0, dev->compute, pp);
+    }
 }
 static int gemm_tail_launch(nk_device* dev, int transA, int transB, const GemmArgs& p, bool* taken) {
     *taken = false;

@@ -3,13 +3,15 @@
 summary (tools/rocpd_kernel_stats.py) prints: `reduce_cols4_kernel<0>`, `binary_fwd_kernel<2, true>`.
 
     python tools/list_unit_kernels.py                      # the streaming units of tests/dispatch_paths.py
-    python tools/list_unit_kernels.py nk_gemm.hip
+    python tools/list_unit_kernels.py nk_gemm.hip nk_conv.hip nk_attention.hip
+    python tools/list_unit_kernels.py --all                # every translation unit of the library
 
 The library's `.hip_fatbin` section is a run of clang offload bundles, one per translation unit; each holds one gfx950 code
-object (an ELF) whose symbol table names every kernel twice: `<sym>` (the code) and `<sym>.kd` (its descriptor).  A kernel is
-attributed to a unit by its function name: the `__global__` functions that unit's source defines.  Only the demangler is run
-as a program (`c++filt` or `llvm-cxxfilt` when one is on the PATH; without one, the plain names these units use are decoded
-here); everything else is parsed here."""
+object (an ELF) whose symbol table names every kernel twice: `<sym>` (the code) and `<sym>.kd` (its descriptor).  A kernel
+belongs to the unit whose code object holds it; a code object is matched to its unit by function names: the `__global__`
+functions the unit's source defines, in the `.hip` file itself or in the `nk_*.h` headers it includes (nk_conv.hip defines no
+kernel of its own).  Only the demangler is run as a program (`c++filt` or `llvm-cxxfilt` when one is on the PATH; without one,
+the plain names these units use are decoded here); everything else is parsed here."""
 import os
 import re
 import shutil
@@ -60,23 +62,38 @@ def kernel_symbols(elf):
 
 
 def _demangle_plain(m):
-    """the subset of the Itanium mangling the streaming kernels use - an optionally nested function name with integer and
-    bool template arguments - for machines without a demangler program; None for anything else"""
-    g = re.match(r"_Z(N?)((?:\d+[A-Za-z_]\w*?)+?)(?:I((?:L[ib]n?\d+E)+)E)?(?(1)E|)(?=[^\d])", m)
-    if not g:
-        return None
-    ids, rest = [], g.group(2)
-    while rest:
-        n = re.match(r"\d+", rest)
-        if not n or len(rest) < n.end() + int(n.group()):
+    """the subset of the Itanium mangling this library's kernels use - a function name, nested in namespaces or not, with integer
+    and bool template arguments (any number of them), whatever the parameter list - for machines without a demangler program;
+    an `extern "C"` kernel is its own name; None for anything else (type template arguments)"""
+    if not m.startswith("_Z"):
+        return m + "(" if re.fullmatch(r"[A-Za-z_]\w*", m) else None
+    at, nested = 2, m.startswith("_ZN")
+    at += nested
+    ids = []
+    while True:
+        n = re.match(r"\d+", m[at:])
+        if not n:
+            break
+        size, at = int(n.group()), at + n.end()
+        if size == 0 or len(m) < at + size:
             return None
-        ids.append(rest[n.end():n.end() + int(n.group())])
-        rest = rest[n.end() + int(n.group()):]
+        ids.append(m[at:at + size])
+        at += size
+        if not nested:
+            break
+    if not ids or not all(re.fullmatch(r"[A-Za-z_]\w*", i) for i in ids):
+        return None
     name = "::".join("(anonymous namespace)" if i == "_GLOBAL__N_1" else i for i in ids)
-    if g.group(3):
+    if m[at:at + 1] == "I":
+        g = re.match(r"I((?:L[ib]n?\d+E)+)E", m[at:])
+        if not g:
+            return None
         args = [("true" if v == "1" else "false") if t == "b" else ("-" if neg else "") + v
-                for t, neg, v in re.findall(r"L([ib])(n?)(\d+)E", g.group(3))]
+                for t, neg, v in re.findall(r"L([ib])(n?)(\d+)E", g.group(1))]
         name += "<" + ", ".join(args) + ">"
+        at += g.end()
+    if nested and m[at:at + 1] != "E":
+        return None
     return name + "("
 
 
@@ -97,27 +114,78 @@ def trace_name(demangled):
     return re.sub(r"^void\s+", "", s).strip()
 
 
-def source_kernels(unit):
-    """names of the `__global__` functions a unit's source defines"""
-    txt = open(os.path.join(CSRC, unit)).read()
+def file_kernels(path):
+    """names of the `__global__` functions one file defines itself: `__global__`, then in any order `void`, `static`, `inline` and a
+    `__launch_bounds__(...)` whose argument list may nest parentheses, then the name and its `(`"""
+    txt = open(path).read()
     txt = re.sub(r"//[^\n]*", "", txt)
-    return set(re.findall(r"__global__\s+(?:__launch_bounds__\s*\([^)]*\)\s*)?void\s+(\w+)\s*\(", txt))
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    names = set()
+    for g in re.finditer(r"\b__global__\b", txt):
+        at = g.end()
+        while True:
+            t = re.compile(r"\s*(\w+)").match(txt, at)
+            if not t:
+                break
+            word, at = t.group(1), t.end()
+            if word == "__launch_bounds__":
+                o = re.compile(r"\s*\(").match(txt, at)
+                if not o:
+                    break
+                depth, at = 1, o.end()
+                while depth and at < len(txt):
+                    depth += {"(": 1, ")": -1}.get(txt[at], 0)
+                    at += 1
+            elif word not in ("void", "static", "inline"):
+                if re.compile(r"\s*\(").match(txt, at):
+                    names.add(word)
+                break
+    return names
+
+
+def unit_sources(unit):
+    """the unit's own file and every `nk_*.h` it includes, directly or through another header"""
+    seen, todo = [], [unit]
+    while todo:
+        f = todo.pop()
+        if f in seen or not os.path.exists(os.path.join(CSRC, f)):
+            continue
+        seen.append(f)
+        todo += re.findall(r'^\s*#\s*include\s+"(nk_\w+\.h)"', open(os.path.join(CSRC, f)).read(), re.M)
+    return seen
+
+
+def source_kernels(unit):
+    """names of the `__global__` functions a unit defines: its own and those of the headers it includes"""
+    return set().union(*(file_kernels(os.path.join(CSRC, f)) for f in unit_sources(unit)))
+
+
+def all_units():
+    return tuple(sorted(f for f in os.listdir(CSRC) if f.endswith(".hip")))
+
+
+def object_kernels(lib_path=LIB):
+    """[sorted trace names of the kernel instantiations of one code object], one entry per translation unit of the library"""
+    out = []
+    for elf in code_objects(lib_path):
+        mangled = kernel_symbols(elf)
+        out.append(sorted({trace_name(d) for d in demangle(mangled)}))
+    return out
 
 
 def unit_kernels(units=STREAMING_UNITS, lib_path=LIB):
-    """{unit: sorted trace names of its kernel instantiations in the built library}"""
-    mangled = sorted({k for elf in code_objects(lib_path) for k in kernel_symbols(elf)})
-    built = {}
-    for m, d in zip(mangled, demangle(mangled)):
-        t = trace_name(d)
-        built.setdefault(re.sub(r"<.*$", "", t), set()).add(t)
+    """{unit: sorted trace names of its kernel instantiations in the built library}: the kernels of the code object(s) that hold
+    a function the unit's sources define"""
+    objs = object_kernels(lib_path)
     out = {}
     for u in units:
-        out[u] = sorted(t for fn in source_kernels(u) for t in built.get(fn, ()))
+        fns = source_kernels(u)
+        out[u] = sorted({k for ks in objs if any(re.sub(r"<.*$", "", k) in fns for k in ks) for k in ks})
     return out
 
 
 if __name__ == "__main__":
-    for unit, ks in unit_kernels(tuple(sys.argv[1:]) or STREAMING_UNITS).items():
+    args = sys.argv[1:]
+    for unit, ks in unit_kernels(all_units() if args == ["--all"] else tuple(args) or STREAMING_UNITS).items():
         for k in ks:
             print(unit, k)
