@@ -1308,6 +1308,45 @@ Shape flat_shape(const Shape& s) {
     return Shape{s[0], (int)n};
 }
 
+// Embedding (ours; the reference has no such node; semantics in neuronika_hip.h): rows of the (V, D) table selected by the ids of
+// `idx`, f32 as the NLL targets are, of any shape.  Differentiable in the table only; the ids are data.
+struct EmbeddingFwd : Forward {
+    Shared<HipArray> weight, idx, y;
+    void forward() const override {
+        const Shape& ws = weight->shape();
+        check(nk_embedding_fwd(D(weight), weight->ptr(), idx->ptr(), y->ptr(), (long long)idx->len(), ws[0], ws[1]));
+    }
+};
+// the table's gradient: the ordered sum per row.  The first writer of the pass takes the assign form, which covers the whole table
+// (no memset, no read); a second embedding on the same table (tied weights) takes the `+=` form.
+struct EmbeddingBwd : Backward {
+    Shared<Gradient> dw, g;
+    Shared<HipArray> idx;
+    long long padding_idx = -1;
+    void backward() const override {
+        const HipArray& G = g->borrow();
+        bool assign = false;
+        HipArray& d = dw->borrow_first_write(assign);
+        const Shape& ws = d.shape();
+        check((assign ? nk_embedding_bwd_assign : nk_embedding_bwd)(d.device()->raw(), d.ptr(), G.ptr(), idx->ptr(), (long long)idx->len(), ws[0],
+                                                                    ws[1], padding_idx));
+    }
+    void targets(std::vector<const Gradient*>& out) const override { out.push_back(dw.get()); }
+};
+Shared<EmbeddingFwd> embedding_fwd_node(const Var& weight, const Var& indices, long padding_idx) {
+    const Shape& ws = weight.shape();
+    if (ws.size() != 2 || ws[0] < 1 || ws[1] < 1) panic("embedding: the table must be (num_embeddings, embedding_dim), both at least 1");
+    if (ws[0] > (1 << 24)) panic("embedding: at most 2^24 rows (ids are stored as f32), got " + std::to_string(ws[0]));
+    if (padding_idx >= ws[0]) panic("embedding: padding_idx " + std::to_string(padding_idx) + " is not a row of a table of " + std::to_string(ws[0]));
+    if (indices.data->len() > ((size_t)1 << 30)) panic("embedding: more than 2^30 ids");
+    if (indices.device().get() != weight.device().get()) panic("embedding: table and ids live on different devices");
+    Shape ys = indices.shape();
+    ys.push_back(ws[1]);
+    auto n = std::make_shared<EmbeddingFwd>();
+    n->weight = weight.data; n->idx = indices.data; n->y = zeros_like(weight.data, ys);
+    return n;
+}
+
 Shape mm_shape(const Shape& a, const Shape& b, int kind) {  // utils.rs:46-55 `DotDim`
     if (kind == 4) {
         if (a.size() != 2 || b.size() != 1) panic("mv: matrix and vector expected");
@@ -1941,6 +1980,17 @@ VarDiff VarDiff::layer_norm(const Var& gamma, const Var& beta, double eps) const
 VarDiff VarDiff::layer_norm(const Shape& normalized_shape, double eps) const {
     return layer_norm_diff(var, grad, &history, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, normalized_shape, eps);
 }
+VarDiff VarDiff::embedding(const Var& indices, long padding_idx) const {
+    auto n = embedding_fwd_node(var, indices, padding_idx);
+    auto y = n->y;
+    History<ForwardEntry> fh = var.history;
+    fh.merge(indices.history);
+    Var v = Var::node(y, n, std::move(fh));
+    auto g = std::make_shared<Gradient>(v.device(), v.shape());
+    auto bw = std::make_shared<EmbeddingBwd>();
+    bw->dw = grad; bw->g = g; bw->idx = indices.data; bw->padding_idx = padding_idx < 0 ? -1 : padding_idx;
+    return VarDiff::node(std::move(v), g, entry(bw, g), history);
+}
 VarDiff VarDiff::batch_norm(const VarDiff& gamma, const VarDiff& beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
                             Shared<bool> status) const {
     return batch_norm_diff(var, grad, &history, &gamma.var, gamma.grad, &gamma.history, &beta.var, beta.grad, &beta.history, running_mean, running_var,
@@ -2290,6 +2340,30 @@ VarDiff LayerNorm::forward(const Var& input) const {
 VarDiff LayerNorm::forward(const VarDiff& input) const {
     return elementwise_affine ? input.layer_norm(weight, bias, eps) : input.layer_norm(normalized_shape, eps);
 }
+static void embedding_check(const Shape& ws, long padding_idx) {
+    if (ws.size() != 2 || ws[0] < 1 || ws[1] < 1) panic("Embedding: the table must be (num_embeddings, embedding_dim), both at least 1");
+    if (ws[0] > (1 << 24)) panic("Embedding: at most 2^24 rows (ids are stored as f32), got " + std::to_string(ws[0]));
+    if (padding_idx >= ws[0]) panic("Embedding: padding_idx " + std::to_string(padding_idx) + " is not a row of a table of " + std::to_string(ws[0]));
+}
+Embedding::Embedding(DevicePtr dev, size_t num_embeddings, size_t embedding_dim, long padding_idx, uint64_t seed)
+    : num_embeddings(num_embeddings), embedding_dim(embedding_dim), padding_idx(padding_idx < 0 ? -1 : padding_idx) {
+    if (num_embeddings > ((size_t)1 << 24) || embedding_dim > ((size_t)1 << 24)) panic("Embedding: at most 2^24 rows (ids are stored as f32) of at most 2^24 values");
+    const Shape ws{(int)num_embeddings, (int)embedding_dim};
+    embedding_check(ws, padding_idx);
+    std::mt19937_64 rng(seed);  // init::normal(weight, 0, 1, seed), with the padding row zeroed before the one upload
+    std::normal_distribution<float> d(0.f, 1.f);
+    std::vector<float> h(numel(ws));
+    for (float& v : h) v = d(rng);
+    if (padding_idx >= 0) std::fill(h.begin() + (size_t)padding_idx * embedding_dim, h.begin() + ((size_t)padding_idx + 1) * embedding_dim, 0.f);
+    weight = from_host(dev, ws, h.data()).requires_grad();
+}
+Embedding::Embedding(VarDiff w, long padding_idx) : weight(std::move(w)), padding_idx(padding_idx < 0 ? -1 : padding_idx) {
+    embedding_check(weight.shape(), padding_idx);
+    num_embeddings = (size_t)weight.shape()[0];
+    embedding_dim = (size_t)weight.shape()[1];
+}
+VarDiff Embedding::forward(const Var& indices) const { return weight.embedding(indices, padding_idx); }
+
 
 BatchNormNd::BatchNormNd(int nd, DevicePtr dev, int num_features, double eps, double momentum, bool affine, bool track_running_stats)
     : num_features(num_features), eps(eps), momentum(momentum), affine(affine), track_running_stats(track_running_stats), nd(nd),
@@ -2772,6 +2846,14 @@ nn::LayerNorm layer_norm_from_json(DevicePtr dev, const Json& j, double eps) {
     return nn::LayerNorm(vardiff_from_json(dev, j.at("weight")), vardiff_from_json(dev, j.at("bias")), eps);
 }
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const std::string& text, double eps) { return layer_norm_from_json(std::move(dev), parse(text), eps); }
+
+std::string to_json(const nn::Embedding& e) { return "{\"weight\":" + to_json(e.weight) + "}"; }
+nn::Embedding embedding_from_json(DevicePtr dev, const Json& j, long padding_idx) {
+    return nn::Embedding(vardiff_from_json(dev, j.at("weight")), padding_idx);
+}
+nn::Embedding embedding_from_json(DevicePtr dev, const std::string& text, long padding_idx) {
+    return embedding_from_json(std::move(dev), parse(text), padding_idx);
+}
 
 std::string to_json(const nn::BatchNormNd& l) {
     if (!l.affine || !l.track_running_stats) panic("serde: a BatchNorm is serialised with its affine parameters and its running statistics");

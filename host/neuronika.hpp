@@ -439,6 +439,10 @@ class VarDiff {
     VarDiff layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps = 1e-5) const;
     VarDiff layer_norm(const Var& gamma, const Var& beta, double eps = 1e-5) const;
     VarDiff layer_norm(const Shape& normalized_shape, double eps = 1e-5) const;
+    // Embedding (ours: the reference has none; semantics in neuronika_hip.h): self is the (V, D) table, `indices` holds ids as f32
+    // (read as the NLL targets are) in any shape; the result has shape indices.shape + (D,).  Differentiable in the table only:
+    // its gradient is the ordered sum per row, no atomics; rows selected through `padding_idx` (< 0: none) receive no gradient.
+    VarDiff embedding(const Var& indices, long padding_idx = -1) const;
     // one forward and ONE backward entry; gradients flow to self and, independently, to gamma and beta where differentiable
     VarDiff batch_norm(const VarDiff& gamma, const VarDiff& beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
                        Shared<bool> status) const;
@@ -652,6 +656,19 @@ struct AvgPool3d : PoolNd {
         : PoolNd(3, true, std::move(kernel_size), std::move(stride), std::move(padding), count_include_pad) {}
 };
 
+// Embedding table (ours: the reference has no such layer): forward(indices) = the rows of `weight` (num_embeddings,
+// embedding_dim) selected by the ids of `indices` (f32, any shape), shape indices.shape + (embedding_dim,).  weight ~ N(0, 1)
+// (init::normal), the row `padding_idx` zeroed; that row receives no gradient, so it stays zero under the optimizers.  The
+// weight is an ordinary leaf for the optimizers, dp::GradientSync and serde; two modules may share one (tied weights).
+struct Embedding {
+    VarDiff weight;
+    size_t num_embeddings, embedding_dim;
+    long padding_idx = -1;
+    Embedding(DevicePtr dev, size_t num_embeddings, size_t embedding_dim, long padding_idx = -1, uint64_t seed = 0);
+    Embedding(VarDiff weight, long padding_idx = -1);  // a table built elsewhere (deserialised, or shared with another module)
+    VarDiff forward(const Var& indices) const;
+};
+
 // `LSTMCell` neuronika-nn/src/lib.rs:453-541.  Weights (4H,in)/(4H,H), biases (4H), U(-k,k), k = 1/sqrt(H).
 // `forward` keeps the reference's exact composition: state = (cell_state, hidden); gate chunks 0..3 get
 // sigmoid, tanh, sigmoid, sigmoid (:528-533); returns (new_cell_state, new_hidden) (:534-537).
@@ -806,6 +823,9 @@ nn::Linear linear_from_json(DevicePtr dev, const std::string& text);
 std::string to_json(const nn::LayerNorm& l);  // {"weight":..., "bias":...}; eps is not part of the wire format
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const Json& j, double eps = 1e-5);
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const std::string& text, double eps = 1e-5);
+std::string to_json(const nn::Embedding& e);  // {"weight":...}; padding_idx is not part of the wire format
+nn::Embedding embedding_from_json(DevicePtr dev, const Json& j, long padding_idx = -1);
+nn::Embedding embedding_from_json(DevicePtr dev, const std::string& text, long padding_idx = -1);
 
 // {"weight":..., "bias":..., "running_mean":..., "running_var":...}; eps and momentum are not part of the wire format.  Loading
 // replaces the four fields of an existing layer (any of BatchNorm1d/2d/3d) of the same num_features.

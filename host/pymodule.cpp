@@ -150,6 +150,7 @@ PYBIND11_MODULE(_tape, m) {
         .def("layer_norm", py::overload_cast<const VarDiff&, const VarDiff&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const Var&, const Var&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const Shape&, double>(&VarDiff::layer_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-5)
+        .def("embedding", &VarDiff::embedding, py::arg("indices"), py::arg("padding_idx") = -1)
         .def("batch_norm", [](const VarDiff& x, const VarDiff& gamma, const VarDiff& beta, const Var* rm, const Var* rv, double momentum, double eps,
                               const Status& s) { return x.batch_norm(gamma, beta, rm, rv, momentum, eps, s.flag); },
              py::arg("gamma"), py::arg("beta"), py::arg("running_mean").none(true), py::arg("running_var").none(true), py::arg("momentum"), py::arg("eps"),
@@ -280,6 +281,9 @@ PYBIND11_MODULE(_tape, m) {
     sd.def("to_json", py::overload_cast<const nn::LayerNorm&>(&serde::to_json));
     sd.def("layer_norm_from_json", py::overload_cast<DevicePtr, const std::string&, double>(&serde::layer_norm_from_json), py::arg("dev"), py::arg("text"),
            py::arg("eps") = 1e-5);
+    sd.def("to_json", py::overload_cast<const nn::Embedding&>(&serde::to_json));
+    sd.def("embedding_from_json", py::overload_cast<DevicePtr, const std::string&, long>(&serde::embedding_from_json), py::arg("dev"), py::arg("text"),
+           py::arg("padding_idx") = -1);
 
     sd.def("to_json", py::overload_cast<const nn::BatchNormNd&>(&serde::to_json));
     sd.def("batch_norm_load_json", py::overload_cast<nn::BatchNormNd&, const std::string&>(&serde::batch_norm_load_json), py::arg("layer"), py::arg("text"));
@@ -308,6 +312,15 @@ PYBIND11_MODULE(_tape, m) {
         .def_readonly("elementwise_affine", &nn::LayerNorm::elementwise_affine)
         .def("forward", py::overload_cast<const Var&>(&nn::LayerNorm::forward, py::const_))
         .def("forward", py::overload_cast<const VarDiff&>(&nn::LayerNorm::forward, py::const_));
+    py::class_<nn::Embedding>(nn, "Embedding")
+        .def(py::init<DevicePtr, size_t, size_t, long, uint64_t>(), py::arg("dev"), py::arg("num_embeddings"), py::arg("embedding_dim"),
+             py::arg("padding_idx") = -1, py::arg("seed") = 0)
+        .def(py::init<VarDiff, long>(), py::arg("weight"), py::arg("padding_idx") = -1)
+        .def_readonly("weight", &nn::Embedding::weight)
+        .def_readonly("num_embeddings", &nn::Embedding::num_embeddings)
+        .def_readonly("embedding_dim", &nn::Embedding::embedding_dim)
+        .def_readonly("padding_idx", &nn::Embedding::padding_idx)
+        .def("forward", &nn::Embedding::forward);
     {
         py::module_ im = nn.def_submodule("init");
         im.def("calculate_gain", &nn::init::calculate_gain);

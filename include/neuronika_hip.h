@@ -542,6 +542,31 @@ int nk_layer_norm_bwd_params(nk_device* dev, float* dgamma, float* dbeta, const 
 int nk_layer_norm_bwd_params_assign(nk_device* dev, float* dgamma, float* dbeta, const float* g, const float* x,
                                     const float* stats, long long rows, int D);
 
+/* ------------------------------------------------------------------ embedding table */
+/* Rows of a (V, D) f32 table selected by id.  The reference has no such layer; the semantics are fixed here.
+ *   weight: (V, D) row-major.  idx: n ids STORED AS f32 and read exactly as nk_nll_* reads its targets (Rust's saturating
+ *   `as usize`: NaN and negatives are 0, the fraction is dropped).  f32 holds ids exactly up to 2^24: V outside 1 .. 2^24 is
+ *   NK_ERR_INVALID, as are n outside 0 .. 2^30 and D outside 1 .. 2^24.  The index tensor may have any shape; it is read flat.
+ *   fwd:  out[t, :] = weight[idx[t], :] for t < n (out: (n, D)); an id >= V selects nothing and yields a zero row.
+ *   bwd:  dweight[v, :] += the sum over the t with idx[t] == v of g[t, :], summed in f32 in ASCENDING t starting from the first
+ *         contribution itself (a row one token selected receives that gradient row as it is, -0.0 included); ids >= V and ids
+ *         equal to `padding_idx` contribute nothing; padding_idx < 0 means none.  A row more than 128 tokens selected is summed in
+ *         chunks of 128 consecutive contributions, each as above, and the chunks' sums are added in chunk order starting from the
+ *         first; 128 is a constant of the library, the same on every device.  dweight[v, :] = dweight[v, :] + that sum, one
+ *         addition per element; rows no token selected are not touched.
+ *   bwd_assign: what bwd leaves in an all-zero table, written without reading it (see "first-write variants"): rows no token
+ *         selected are written as zeros, n == 0 included, so the whole (V, D) destination is covered.
+ * No float atomics: an inverted index of the ids (per table row, its token positions ascending) is built in the device workspace
+ * on every backward call and each table row has one owner, so every result repeats bit for bit.  Nothing synchronises, and nothing
+ * allocates beyond the workspace (4 (2 V + n) bytes and a little more): the calls can be captured into a graph after one eager
+ * call of the same sizes.  16-byte accesses where D % 4 == 0 and the pointers are 16-byte aligned, scalar accesses otherwise.
+ * n == 0: fwd and bwd write nothing.  Out-of-range ids never read or write outside the buffers. */
+int nk_embedding_fwd(nk_device* dev, const float* weight, const float* idx, float* out, long long n, int V, int D);
+int nk_embedding_bwd(nk_device* dev, float* dweight, const float* g, const float* idx, long long n, int V, int D,
+                     long long padding_idx);
+int nk_embedding_bwd_assign(nk_device* dev, float* dweight, const float* g, const float* idx, long long n, int V, int D,
+                            long long padding_idx);
+
 /* ------------------------------------------------------------------ batch normalisation */
 /* BatchNorm of a contiguous row-major tensor read as (N, C, L), L the product of the extents behind the channel axis (L = 1
  * for an (N, C) input).  The reference has no such layer; the semantics are fixed here.  Per channel c, over its M = N * L values

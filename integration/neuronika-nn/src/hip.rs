@@ -198,6 +198,33 @@ impl<E: Dimension + 'static> LayerNorm<E> {
     }
 }
 
+/// Embedding table (the reference has no such layer; semantics in `include/neuronika_hip.h`): `forward(indices)` = the rows of
+/// `weight` `(num_embeddings, embedding_dim)` selected by the ids of `indices` (f32, any dimension), with one more axis of extent
+/// `embedding_dim`.  `weight` ~ N(0, 1) (`init::normal`, `neuronika-nn/src/init.rs:195-201`), the row `padding_idx` zeroed; that row
+/// receives no gradient.
+pub struct Embedding {
+    pub weight: HipVarDiff<Ix2>,
+    pub padding_idx: Option<usize>,
+}
+
+impl Embedding {
+    pub fn new(num_embeddings: usize, embedding_dim: usize, padding_idx: Option<usize>, device: &Device) -> Self {
+        assert!(padding_idx.map_or(true, |p| p < num_embeddings), "Embedding: padding_idx is not a row of the table");
+        let mut rng = rand::thread_rng();
+        let normal = rand_distr::Normal::new(0f32, 1f32).unwrap();
+        let mut host = Array::from_shape_simple_fn((num_embeddings, embedding_dim), || normal.sample(&mut rng));
+        if let Some(p) = padding_idx {
+            host.row_mut(p).fill(0.);
+        }
+        Self { weight: HipVarDiff::parameter(&host, device.clone()), padding_idx }
+    }
+
+    /// ONE forward node (`nk_embedding_fwd`) and ONE backward entry (`nk_embedding_bwd`).
+    pub fn forward<E: Dimension + 'static>(&self, indices: HipVar<E>) -> HipVarDiff<E::Larger> {
+        self.weight.clone().embedding(indices, self.padding_idx)
+    }
+}
+
 /// `ModelStatus`-style switch shared with the dropout nodes (`neuronika-nn/src/lib.rs:84-137`, `node/dropout/mod.rs:27`).
 pub struct Dropout {
     pub p: f64,

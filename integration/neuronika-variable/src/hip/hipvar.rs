@@ -8,7 +8,7 @@ use std::{
     rc::Rc,
 };
 
-use ndarray::{DimMax, Dimension, IntoDimension, Ix0, Ix1, Ix2, Ix3, RemoveAxis};
+use ndarray::{Axis, DimMax, Dimension, IntoDimension, Ix0, Ix1, Ix2, Ix3, RemoveAxis};
 
 use super::{
     device::Device,
@@ -18,7 +18,7 @@ use super::{
     node::{
         AttentionState, BinaryOp, BinaryOperation, BinaryOperationBackwardLeft, BinaryOperationBackwardRight, Chunk, ChunkBackward,
         Convolution, ConvolutionBackwardInput, ConvolutionBackwardKernel, ConvolutionBackwardKernelBias, ConvolutionBackwardPadded, ConvolutionBias,
-        ConvolutionBiasPadded, Dropout,
+        ConvolutionBiasPadded, Dropout, Embedding, EmbeddingBackward,
         AvgPool, AvgPoolBackward, MaxPool, MaxPoolBackward,
         DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
@@ -437,6 +437,21 @@ impl HipVar<Ix2> {
         let (n, o) = (self.data.borrow().dimension()[0], rhs.data.borrow().dimension()[0]);
         let data = shared(ndarray::Dim([n, o]), &self.device());
         let op = MatrixMatrixMulT::new(self.data, rhs.data, data.clone());
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+}
+
+impl HipVar<Ix2> {
+    /// Embedding (ours: the reference has none; semantics in `include/neuronika_hip.h`): `self` is the `(V, D)` table, `indices` holds
+    /// ids as f32 (read as the NLL targets are) in any dimension `E`; the result has the shape of `indices` plus a last axis `D`.
+    pub fn embedding<E: 'static + Dimension>(mut self, indices: HipVar<E>) -> HipVar<E::Larger> {
+        self.history.merge(indices.history);
+        let d = self.data.borrow().dimension()[1];
+        let idim = indices.data.borrow().dimension();
+        let mut dim = idim.insert_axis(Axis(idim.ndim()));
+        dim.slice_mut()[idim.ndim()] = d;
+        let data = shared(dim, &self.device());
+        let op = Embedding::new(self.data, indices.data, data.clone());
         HipVar::node(data, Rc::new(op), self.history)
     }
 }
@@ -904,6 +919,21 @@ where
         let bwd = ConvolutionBackwardPadded::new(input.var.data, self.var.data, input.grad, self.grad, bias.grad, grad.clone(), to_i32(padding),
                                                  to_i32(stride), to_i32(dilation), groups as i32);
         let op: Rc<dyn Backward> = Rc::new(bwd);
+        HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
+    }
+}
+
+impl HipVarDiff<Ix2> {
+    /// Embedding over a differentiable table: ONE forward node and ONE backward entry (`EmbeddingBackward`: the ordered sum per
+    /// table row).  Differentiable in the table only; ids equal to `padding_idx` contribute no gradient.
+    pub fn embedding<E: 'static + Dimension>(self, indices: HipVar<E>, padding_idx: Option<usize>) -> HipVarDiff<E::Larger> {
+        let rows = self.var.data.borrow().dimension()[0];
+        assert!(rows <= 1 << 24, "embedding: at most 2^24 rows (ids are stored as f32)");
+        assert!(padding_idx.map_or(true, |p| p < rows), "embedding: padding_idx is not a row of the table");
+        let indices_data = indices.data.clone();
+        let var = self.var.embedding(indices);
+        let grad = Rc::new(Gradient::hip_zeros(var.data.borrow().dimension(), var.device()));
+        let op: Rc<dyn Backward> = Rc::new(EmbeddingBackward::new(indices_data, self.grad.clone(), grad.clone(), padding_idx.map_or(-1, |p| p as i64)));
         HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
     }
 }

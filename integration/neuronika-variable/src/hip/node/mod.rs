@@ -7,6 +7,7 @@
 mod attention;
 mod binary_op;
 mod convolution;
+mod embedding;
 mod layout;
 mod linear;
 mod matrix_matrix_mul;
@@ -20,6 +21,7 @@ mod reduction;
 pub(crate) use attention::*;
 pub(crate) use binary_op::*;
 pub(crate) use convolution::*;
+pub(crate) use embedding::*;
 pub(crate) use layout::*;
 pub(crate) use linear::*;
 pub(crate) use matrix_matrix_mul::*;

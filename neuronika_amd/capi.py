@@ -166,6 +166,9 @@ _SIGS = {
     "nk_layer_norm_bwd_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
     "nk_layer_norm_bwd_params": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
     "nk_layer_norm_bwd_params_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
+    "nk_embedding_fwd": [VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_int],
+    "nk_embedding_bwd": [VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_int, C.c_longlong],
+    "nk_embedding_bwd_assign": [VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_int, C.c_longlong],
     "nk_batch_norm_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double],
     "nk_batch_norm_infer_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_double],
     "nk_batch_norm_bwd_sums": [VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int],
@@ -840,6 +843,17 @@ def avg_pool_fwd(dev, x, x_shape, y, kernel, stride, padding, count_include_pad=
 def avg_pool_bwd(dev, dx, x_shape, g, kernel, stride, padding, count_include_pad=True, assign=False):
     check((lib.nk_avg_pool_bwd_assign if assign else lib.nk_avg_pool_bwd)(dev.h, len(x_shape) - 2, _p(dx), ints(x_shape), _p(g), ints(kernel), ints(stride),
                                                                           ints(padding), int(bool(count_include_pad))))
+
+
+def embedding_fwd(dev, weight, idx, out, n, V, D):
+    """out (n, D) = rows of weight (V, D) selected by the n ids of `idx`, stored as f32 (arrays may be flat or offset views)"""
+    check(lib.nk_embedding_fwd(dev.h, _p(weight), _p(idx), _p(out), int(n), int(V), int(D)))
+
+
+def embedding_bwd(dev, dweight, g, idx, n, V, D, padding_idx=-1, assign=False):
+    """dweight (V, D) += (or, `assign`, =) the ordered sum of the rows of g (n, D) per id; `padding_idx` < 0: none"""
+    check((lib.nk_embedding_bwd_assign if assign else lib.nk_embedding_bwd)(dev.h, _p(dweight), _p(g), _p(idx), int(n), int(V), int(D),
+                                                                            int(padding_idx)))
 
 
 def dropout_fwd(dev, x, y, noise, p, train=True, seed=0, offset=0):

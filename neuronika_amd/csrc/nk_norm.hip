@@ -8,6 +8,7 @@
 //   dgamma / dbeta one pass over g, x, stats: a block owns a tile of columns and a SPLIT of the rows and leaves one partial row
 //                  pair in the workspace; a second kernel sums the splits in a fixed order.  No atomics: results repeat bit for bit.
 #include "nk_common.h"
+#include "nk_embedding.h"
 
 namespace {
 
