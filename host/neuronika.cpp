@@ -909,6 +909,37 @@ struct LossBwd : Backward {
     void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
 };
 
+// Cross entropy of class logits against integer targets (ours; the reference has no such node; semantics in neuronika_hip.h):
+// log-softmax and NLL in one forward node, which owns `lse` (one float per position); the backward recomputes the softmax from the
+// logits.  The first writer of the logits' gradient takes the assign form (no memset, no read; inactive rows written as zeros).
+struct CrossEntropyFwd : Forward {
+    Shared<HipArray> x, t, lse, out;
+    Reduction red;
+    long long ignore_index = -1;
+    double label_smoothing = 0.0;
+    void forward() const override {
+        const Shape& s = x->shape();
+        check(nk_cross_entropy_fwd(D(x), x->ptr(), t->ptr(), s.data(), (int)s.size(), (int)red, ignore_index, label_smoothing, lse->ptr(),
+                                   out->ptr()));
+    }
+};
+struct CrossEntropyBwd : Backward {
+    Shared<HipArray> x, t, lse;
+    Shared<Gradient> dx, g;
+    Reduction red;
+    long long ignore_index = -1;
+    double label_smoothing = 0.0;
+    void backward() const override {
+        const HipArray& G = g->borrow();
+        bool assign = false;
+        HipArray& d = dx->borrow_first_write(assign);
+        const Shape& s = d.shape();
+        check((assign ? nk_cross_entropy_bwd_assign : nk_cross_entropy_bwd)(D(x), d.ptr(), G.ptr(), x->ptr(), t->ptr(), lse->ptr(), s.data(),
+                                                                            (int)s.size(), (int)red, ignore_index, label_smoothing));
+    }
+    void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
+};
+
 // `Linear::forward` as one node: mm_t + broadcast Addition (neuronika-nn/src/lib.rs:443-446); `relu`: followed by the ReLU
 // node (node/relu/mod.rs:29-38) in the same epilogue
 struct LinearFwd : Forward {
@@ -1632,6 +1663,37 @@ static VarDiff loss_diff(int kind, const VarDiff& x, const Var& target, Reductio
     bw->kind = kind; bw->x = x.var.data; bw->t = target.data; bw->dx = x.grad; bw->g = g; bw->red = reduction;
     return VarDiff::node(std::move(out), g, entry(bw, g), x.history);
 }
+static Shared<CrossEntropyFwd> cross_entropy_fwd_node(const Var& x, const Var& target, Reduction reduction, long ignore_index, double label_smoothing) {
+    Shape want = x.shape();
+    if (want.size() < 2) panic("cross_entropy: input of shape (minibatch, C, ...) expected");
+    want.erase(want.begin() + 1);
+    if (target.shape() != want) panic("cross_entropy: target must have shape (minibatch, d1, ..., dk)");
+    if (!(label_smoothing >= 0.0 && label_smoothing < 1.0)) panic("cross_entropy: label_smoothing must be in [0, 1), got " + std::to_string(label_smoothing));
+    if (target.device().get() != x.device().get()) panic("cross_entropy: logits and target live on different devices");
+    auto op = std::make_shared<CrossEntropyFwd>();
+    op->x = x.data; op->t = target.data; op->lse = zeros_like(x.data, want); op->out = zeros_like(x.data, {});
+    op->red = reduction; op->ignore_index = ignore_index < 0 ? -1 : ignore_index; op->label_smoothing = label_smoothing;
+    return op;
+}
+Var Var::cross_entropy(const Var& target, Reduction reduction, long ignore_index, double label_smoothing) const {
+    auto op = cross_entropy_fwd_node(*this, target, reduction, ignore_index, label_smoothing);
+    History<ForwardEntry> h = history;
+    h.merge(target.history);
+    auto y = op->out;
+    return Var::node(y, op, std::move(h));
+}
+VarDiff VarDiff::cross_entropy(const Var& target, Reduction reduction, long ignore_index, double label_smoothing) const {
+    auto op = cross_entropy_fwd_node(var, target, reduction, ignore_index, label_smoothing);
+    History<ForwardEntry> h = var.history;
+    h.merge(target.history);
+    auto y = op->out;
+    Var out = Var::node(y, op, std::move(h));
+    auto g = std::make_shared<Gradient>(device(), Shape{});
+    auto bw = std::make_shared<CrossEntropyBwd>();
+    bw->x = var.data; bw->t = target.data; bw->lse = op->lse; bw->dx = grad; bw->g = g;
+    bw->red = reduction; bw->ignore_index = op->ignore_index; bw->label_smoothing = label_smoothing;
+    return VarDiff::node(std::move(out), g, entry(bw, g), history);
+}
 Var Var::mae(const Var& t, Reduction r) const { return loss_var(NK_LOSS_MAE, *this, t, r); }
 Var Var::bce(const Var& t, Reduction r) const { return loss_var(NK_LOSS_BCE, *this, t, r); }
 Var Var::bce_with_logits(const Var& t, Reduction r) const { return loss_var(NK_LOSS_BCE_WITH_LOGITS, *this, t, r); }
@@ -2339,6 +2401,14 @@ VarDiff LayerNorm::forward(const Var& input) const {
 }
 VarDiff LayerNorm::forward(const VarDiff& input) const {
     return elementwise_affine ? input.layer_norm(weight, bias, eps) : input.layer_norm(normalized_shape, eps);
+}
+CrossEntropyLoss::CrossEntropyLoss(Reduction reduction, long ignore_index, double label_smoothing)
+    : reduction(reduction), ignore_index(ignore_index < 0 ? -1 : ignore_index), label_smoothing(label_smoothing) {
+    if (!(label_smoothing >= 0.0 && label_smoothing < 1.0)) panic("CrossEntropyLoss: label_smoothing must be in [0, 1), got " + std::to_string(label_smoothing));
+}
+Var CrossEntropyLoss::forward(const Var& logits, const Var& target) const { return logits.cross_entropy(target, reduction, ignore_index, label_smoothing); }
+VarDiff CrossEntropyLoss::forward(const VarDiff& logits, const Var& target) const {
+    return logits.cross_entropy(target, reduction, ignore_index, label_smoothing);
 }
 static void embedding_check(const Shape& ws, long padding_idx) {
     if (ws.size() != 2 || ws[0] < 1 || ws[1] < 1) panic("Embedding: the table must be (num_embeddings, embedding_dim), both at least 1");

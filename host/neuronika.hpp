@@ -333,6 +333,10 @@ class Var {
     Var bce_with_logits(const Var& target, Reduction reduction) const;  // var.rs:513
     Var kldiv(const Var& target, Reduction reduction) const;            // var.rs:542
     Var nll(const Var& target, Reduction reduction) const;              // var.rs:671
+    // Cross entropy of class logits (ours: the reference stops at nll; semantics in neuronika_hip.h): self is (minibatch, C, d1..dk),
+    // `target` (minibatch, d1..dk) holds class ids as f32; log-softmax and NLL in ONE node, no (N, C) intermediate.  Ids >= C and
+    // ids equal to `ignore_index` (< 0: none) are inactive; Mean divides by the number of active positions.
+    Var cross_entropy(const Var& target, Reduction reduction, long ignore_index = -1, double label_smoothing = 0.0) const;
     Var mv(const Var& rhs) const;                                        // var.rs:1098 (matrix . vector)
     VarDiff mv(const VarDiff& rhs) const;
     Var vm(const Var& rhs) const;                                        // var.rs:1129 (vector . matrix)
@@ -458,6 +462,9 @@ class VarDiff {
     VarDiff bce_with_logits(const Var& target, Reduction reduction) const;  // vardiff.rs:554
     VarDiff kldiv(const Var& target, Reduction reduction) const;            // vardiff.rs:583
     VarDiff nll(const Var& target, Reduction reduction) const;              // vardiff.rs:725
+    // ONE forward node (it owns the per-position lse) and ONE backward entry, which recomputes the softmax from the logits; the
+    // first writer of the logits' gradient assigns (inactive rows written as zeros), a later one accumulates
+    VarDiff cross_entropy(const Var& target, Reduction reduction, long ignore_index = -1, double label_smoothing = 0.0) const;
     VarDiff mv(const Var& rhs) const;
     VarDiff mv(const VarDiff& rhs) const;
     VarDiff vm(const Var& rhs) const;
@@ -667,6 +674,17 @@ struct Embedding {
     Embedding(DevicePtr dev, size_t num_embeddings, size_t embedding_dim, long padding_idx = -1, uint64_t seed = 0);
     Embedding(VarDiff weight, long padding_idx = -1);  // a table built elsewhere (deserialised, or shared with another module)
     VarDiff forward(const Var& indices) const;
+};
+
+// Cross entropy criterion (ours: the reference has no such layer): forward(logits, target) = logits.cross_entropy(target, reduction,
+// ignore_index, label_smoothing).  No parameters.  `ignore_index` < 0: none (use it for padded tokens, with Embedding's padding_idx).
+struct CrossEntropyLoss {
+    Reduction reduction = Reduction::Mean;
+    long ignore_index = -1;
+    double label_smoothing = 0.0;
+    explicit CrossEntropyLoss(Reduction reduction = Reduction::Mean, long ignore_index = -1, double label_smoothing = 0.0);
+    Var forward(const Var& logits, const Var& target) const;
+    VarDiff forward(const VarDiff& logits, const Var& target) const;
 };
 
 // `LSTMCell` neuronika-nn/src/lib.rs:453-541.  Weights (4H,in)/(4H,H), biases (4H), U(-k,k), k = 1/sqrt(H).

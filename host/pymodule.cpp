@@ -84,6 +84,7 @@ PYBIND11_MODULE(_tape, m) {
         .def("dropout", [](const Var& v, double p, const Status& s) { return v.dropout(p, s.flag); }).def("chunks", &Var::chunks).def("cat", &Var::cat)
         .def("mse", &Var::mse).def("mae", &Var::mae).def("bce", &Var::bce).def("bce_with_logits", &Var::bce_with_logits)
         .def("kldiv", &Var::kldiv).def("nll", &Var::nll).def("stack", &Var::stack)
+        .def("cross_entropy", &Var::cross_entropy, py::arg("target"), py::arg("reduction"), py::arg("ignore_index") = -1, py::arg("label_smoothing") = 0.0)
         .def("mv", py::overload_cast<const Var&>(&Var::mv, py::const_)).def("mv", py::overload_cast<const VarDiff&>(&Var::mv, py::const_))
         .def("vm", py::overload_cast<const Var&>(&Var::vm, py::const_)).def("vm", py::overload_cast<const VarDiff&>(&Var::vm, py::const_))
         .def("vv", py::overload_cast<const Var&>(&Var::vv, py::const_)).def("vv", py::overload_cast<const VarDiff&>(&Var::vv, py::const_)).def("pad", py::overload_cast<const std::vector<int>&, float>(&Var::pad, py::const_), py::arg("padding"), py::arg("value") = 0.f)
@@ -162,6 +163,7 @@ PYBIND11_MODULE(_tape, m) {
         .def("dropout", [](const VarDiff& v, double p, const Status& s) { return v.dropout(p, s.flag); }).def("chunks", &VarDiff::chunks).def("cat", &VarDiff::cat)
         .def("mse", &VarDiff::mse).def("mae", &VarDiff::mae).def("bce", &VarDiff::bce).def("bce_with_logits", &VarDiff::bce_with_logits)
         .def("kldiv", &VarDiff::kldiv).def("nll", &VarDiff::nll).def("stack", &VarDiff::stack)
+        .def("cross_entropy", &VarDiff::cross_entropy, py::arg("target"), py::arg("reduction"), py::arg("ignore_index") = -1, py::arg("label_smoothing") = 0.0)
         .def("mv", py::overload_cast<const Var&>(&VarDiff::mv, py::const_)).def("mv", py::overload_cast<const VarDiff&>(&VarDiff::mv, py::const_))
         .def("vm", py::overload_cast<const Var&>(&VarDiff::vm, py::const_)).def("vm", py::overload_cast<const VarDiff&>(&VarDiff::vm, py::const_))
         .def("vv", py::overload_cast<const Var&>(&VarDiff::vv, py::const_)).def("vv", py::overload_cast<const VarDiff&>(&VarDiff::vv, py::const_)).def("pad", py::overload_cast<const std::vector<int>&, float>(&VarDiff::pad, py::const_), py::arg("padding"), py::arg("value") = 0.f)
@@ -312,6 +314,13 @@ PYBIND11_MODULE(_tape, m) {
         .def_readonly("elementwise_affine", &nn::LayerNorm::elementwise_affine)
         .def("forward", py::overload_cast<const Var&>(&nn::LayerNorm::forward, py::const_))
         .def("forward", py::overload_cast<const VarDiff&>(&nn::LayerNorm::forward, py::const_));
+    py::class_<nn::CrossEntropyLoss>(nn, "CrossEntropyLoss")
+        .def(py::init<Reduction, long, double>(), py::arg("reduction") = Reduction::Mean, py::arg("ignore_index") = -1, py::arg("label_smoothing") = 0.0)
+        .def_readonly("reduction", &nn::CrossEntropyLoss::reduction)
+        .def_readonly("ignore_index", &nn::CrossEntropyLoss::ignore_index)
+        .def_readonly("label_smoothing", &nn::CrossEntropyLoss::label_smoothing)
+        .def("forward", py::overload_cast<const Var&, const Var&>(&nn::CrossEntropyLoss::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&, const Var&>(&nn::CrossEntropyLoss::forward, py::const_));
     py::class_<nn::Embedding>(nn, "Embedding")
         .def(py::init<DevicePtr, size_t, size_t, long, uint64_t>(), py::arg("dev"), py::arg("num_embeddings"), py::arg("embedding_dim"),
              py::arg("padding_idx") = -1, py::arg("seed") = 0)

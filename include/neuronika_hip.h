@@ -465,6 +465,44 @@ int nk_nll_fwd(nk_device* dev, const float* x, const float* target, const int* s
 int nk_nll_bwd(nk_device* dev, float* dx, const float* g, const float* target, const int* shape, int nd,
                int reduction);
 
+/* ------------------------------------------------------------------ cross entropy */
+/* Cross entropy over class logits with integer targets: log-softmax and NLL in one pass.  The reference has no such node (it
+ * stops at nll); the semantics are fixed here, chosen so that the result is nk_nll(nk_log_softmax(x, 1), target) wherever that
+ * composition is defined.
+ *   x: logits (N, C, d1..dk), f32, C-contiguous (NLL's layout).  target: (N, d1..dk) class ids STORED AS f32 and read exactly as
+ *   nk_nll_* and nk_embedding_* read them (Rust's saturating `as usize`: NaN and negatives are 0, the fraction is dropped).
+ *   positions = N d1 .. dk (at most 2^31 - 1), inner = d1 .. dk.  nd in 2 .. NK_MAX_DIMS.
+ *   A position is INACTIVE when its id is >= C (NLL: "selects nothing") or equals `ignore_index` (negative: none).  Inactive
+ *   positions add nothing to the loss and receive a zero gradient row, whatever their logits hold.
+ *   Per active position p with class t, lse = log sum_c exp(x_c) and label smoothing e = `label_smoothing` in [0, 1):
+ *       loss_p = (1 - e) (lse - x_t) + e (lse - mean_c x_c)          d loss_p / d x_c = softmax_c - (1 - e) [c == t] - e / C
+ *   NK_REDUCTION_SUM: the sum over the active positions.  NK_REDUCTION_MEAN: that sum divided by the NUMBER OF ACTIVE POSITIONS,
+ *   an exact integer count taken on the device, forward and backward alike; with no active position the loss and the gradient
+ *   are 0 (torch gives NaN there).  nk_nll's Mean divides the forward by shape[0] and the backward by target.len(): the two
+ *   agree with this entry under Mean only for 2-d inputs with every position active, and under Sum always.
+ *   The running maximum starts from f32::MIN as the softmax kernels' does, so -inf logits are ordinary; a NaN or +inf logit makes
+ *   its position's lse, its loss and (where the position is active) its whole gradient row NaN, as nk_log_softmax + nk_nll do.
+ *   fwd: writes out[0] and lse[p] for EVERY position (`positions` floats, active or not).  Nothing of size (N, C) is saved.
+ *   bwd: dx += g[0] w (d loss_p / d x), w = 1 (Sum) or 1 / active count (Mean; re-derived from `target` on the device, so bwd
+ *        depends on (x, target, lse) only), softmax recomputed as exp(x - lse).  Inactive rows are not touched.
+ *   bwd_assign: what bwd leaves in an all-zero tensor, written without reading it (see "first-write variants"): inactive rows are
+ *        written as zeros, so the whole destination is covered.
+ * No float atomics: per-position losses go to the device workspace and are summed over fixed spans in a fixed order, the count
+ * is an integer sum; two calls on the same data give the same bits.  Nothing synchronises or reads the count on the host; the
+ * workspace use is 4 positions bytes and a little more, so the calls can be captured into a graph after one eager call of the
+ * same sizes.  positions == 0 or C == 0 is a valid empty call: fwd writes out[0] = 0 and no lse, bwd writes nothing.
+ * Kernels (documented because tests choose shapes against them).  inner == 1: C <= 2048 one wave per row with the row in
+ * registers; larger C one block per row in one pass (256 threads up to C = 16384, 512 up to 65536, 1024 beyond).  Both walk a row
+ * as scalars up to the first 16-byte boundary, 16-byte accesses, and scalars after the last: any C, any row start.  The backward
+ * forms need x and dx to share their offset from a 16-byte boundary; otherwise, and for inner > 1, generic kernels run (a thread
+ * per position, lanes along inner). */
+int nk_cross_entropy_fwd(nk_device* dev, const float* x, const float* target, const int* shape, int nd, int reduction,
+                         long long ignore_index, double label_smoothing, float* lse, float* out);
+int nk_cross_entropy_bwd(nk_device* dev, float* dx, const float* g, const float* x, const float* target, const float* lse,
+                         const int* shape, int nd, int reduction, long long ignore_index, double label_smoothing);
+int nk_cross_entropy_bwd_assign(nk_device* dev, float* dx, const float* g, const float* x, const float* target, const float* lse,
+                                const int* shape, int nd, int reduction, long long ignore_index, double label_smoothing);
+
 /* ------------------------------------------------------------------ GEMV / dot ---------- */
 /* MatrixVectorMul node/matrix_vector_mul/mod.rs:31-41  y(n) = A(n,m).x(m);  BackwardLeft :63-69  dA += g (x) x;
  * BackwardRight :92-102  dx += A^T.g */

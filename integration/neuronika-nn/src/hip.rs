@@ -16,8 +16,11 @@
 //! arity).  The tested host mirror of the same layers is `host/neuronika.hpp` (`nn::*`) in this repository.
 use std::{cell::Cell, rc::Rc};
 
-use ndarray::{Array, Dimension, Ix1, Ix2, Ix3, Ix4, Ix5};
-use neuronika_variable::hip::{Device, HipVar, HipVarDiff, PaddingMode};
+use ndarray::{Array, Dimension, Ix0, Ix1, Ix2, Ix3, Ix4, Ix5, RemoveAxis};
+use neuronika_variable::{
+    hip::{Device, HipVar, HipVarDiff, PaddingMode},
+    Reduction,
+};
 use rand::distributions::{Distribution, Uniform};
 
 /// `init::uniform` (`neuronika-nn/src/init.rs:177-193`) for a fresh parameter: values from U(low, high), drawn on the host.
@@ -222,6 +225,26 @@ impl Embedding {
     /// ONE forward node (`nk_embedding_fwd`) and ONE backward entry (`nk_embedding_bwd`).
     pub fn forward<E: Dimension + 'static>(&self, indices: HipVar<E>) -> HipVarDiff<E::Larger> {
         self.weight.clone().embedding(indices, self.padding_idx)
+    }
+}
+
+/// Cross entropy criterion (the reference has no such layer; semantics in `include/neuronika_hip.h`): `forward(logits, target)` =
+/// `logits.cross_entropy(target, reduction, ignore_index, label_smoothing)`, log-softmax and NLL in one node.  No parameters.
+pub struct CrossEntropyLoss {
+    pub reduction: Reduction,
+    pub ignore_index: Option<usize>,
+    pub label_smoothing: f64,
+}
+
+impl CrossEntropyLoss {
+    pub fn new(reduction: Reduction, ignore_index: Option<usize>, label_smoothing: f64) -> Self {
+        assert!((0. ..1.).contains(&label_smoothing), "CrossEntropyLoss: label_smoothing must be in [0, 1)");
+        Self { reduction, ignore_index, label_smoothing }
+    }
+
+    /// ONE forward node (`nk_cross_entropy_fwd`) and ONE backward entry (`nk_cross_entropy_bwd`).
+    pub fn forward<D: Dimension + RemoveAxis + 'static>(&self, logits: HipVarDiff<D>, target: HipVar<D::Smaller>) -> HipVarDiff<Ix0> {
+        logits.cross_entropy(target, self.reduction.clone(), self.ignore_index, self.label_smoothing)
     }
 }
 

@@ -18,7 +18,7 @@ use super::{
     node::{
         AttentionState, BinaryOp, BinaryOperation, BinaryOperationBackwardLeft, BinaryOperationBackwardRight, Chunk, ChunkBackward,
         Convolution, ConvolutionBackwardInput, ConvolutionBackwardKernel, ConvolutionBackwardKernelBias, ConvolutionBackwardPadded, ConvolutionBias,
-        ConvolutionBiasPadded, Dropout, Embedding, EmbeddingBackward,
+        ConvolutionBiasPadded, CrossEntropy, CrossEntropyBackward, Dropout, Embedding, EmbeddingBackward,
         AvgPool, AvgPoolBackward, MaxPool, MaxPoolBackward,
         DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
@@ -438,6 +438,33 @@ impl HipVar<Ix2> {
         let data = shared(ndarray::Dim([n, o]), &self.device());
         let op = MatrixMatrixMulT::new(self.data, rhs.data, data.clone());
         HipVar::node(data, Rc::new(op), self.history)
+    }
+}
+
+impl<D> HipVar<D>
+where
+    D: 'static + Dimension + RemoveAxis,
+{
+    /// Cross entropy of class logits (ours: the reference stops at `nll`; semantics in `include/neuronika_hip.h`): `self` is
+    /// `(minibatch, C, d1..dk)`, `target` `(minibatch, d1..dk)` holds class ids as f32 (read as the NLL targets are).  ONE forward node
+    /// (`nk_cross_entropy_fwd`): no log-probability tensor.  Ids `>= C` and ids equal to `ignore_index` are inactive; `Mean` divides by
+    /// the number of active positions.
+    pub fn cross_entropy(self, target: HipVar<D::Smaller>, reduction: Reduction, ignore_index: Option<usize>, label_smoothing: f64) -> HipVar<Ix0> {
+        self.cross_entropy_with_lse(target, reduction, ignore_index, label_smoothing).0
+    }
+
+    /// The node and the per-position `lse` it owns (what the backward entry reads).
+    pub(crate) fn cross_entropy_with_lse(mut self, target: HipVar<D::Smaller>, reduction: Reduction, ignore_index: Option<usize>,
+                                         label_smoothing: f64) -> (HipVar<Ix0>, Shared<HipArray<D::Smaller>>) {
+        assert!((0. ..1.).contains(&label_smoothing), "cross_entropy: label_smoothing must be in [0, 1)");
+        let dim = self.data.borrow().dimension();
+        assert!(dim.ndim() >= 2, "cross_entropy: input of shape (minibatch, C, ...) expected");
+        assert!(dim.remove_axis(Axis(1)) == target.data.borrow().dimension(), "cross_entropy: target must have shape (minibatch, d1, ..., dk)");
+        self.history.merge(target.history);
+        let lse = shared(dim.remove_axis(Axis(1)), &self.device());
+        let data = shared(ndarray::Dim(()), &self.device());
+        let op = CrossEntropy::new(self.data, target.data, lse.clone(), data.clone(), reduction, ignore_index.map_or(-1, |i| i as i64), label_smoothing);
+        (HipVar::node(data, Rc::new(op), self.history), lse)
     }
 }
 
@@ -920,6 +947,22 @@ where
                                                  to_i32(stride), to_i32(dilation), groups as i32);
         let op: Rc<dyn Backward> = Rc::new(bwd);
         HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
+    }
+}
+
+impl<D> HipVarDiff<D>
+where
+    D: 'static + Dimension + RemoveAxis,
+{
+    /// Cross entropy of differentiable logits: ONE forward node and ONE backward entry (`CrossEntropyBackward`: the softmax
+    /// recomputed from the logits and the forward's `lse`).  The targets are data: no gradient flows to them.
+    pub fn cross_entropy(self, target: HipVar<D::Smaller>, reduction: Reduction, ignore_index: Option<usize>, label_smoothing: f64) -> HipVarDiff<Ix0> {
+        let grad = self.new_grad(ndarray::Dim(()));
+        let (input_data, target_data) = (self.var.data.clone(), target.data.clone());
+        let (var, lse) = self.var.cross_entropy_with_lse(target, reduction.clone(), ignore_index, label_smoothing);
+        let op = CrossEntropyBackward::new(input_data, target_data, lse, self.grad.clone(), grad.clone(), reduction, ignore_index.map_or(-1, |i| i as i64),
+                                           label_smoothing);
+        HipVarDiff::node(var, grad.clone(), (Rc::new(op), grad), self.history)
     }
 }
 

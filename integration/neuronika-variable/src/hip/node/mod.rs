@@ -7,6 +7,7 @@
 mod attention;
 mod binary_op;
 mod convolution;
+mod cross_entropy;
 mod embedding;
 mod layout;
 mod linear;
@@ -21,6 +22,7 @@ mod reduction;
 pub(crate) use attention::*;
 pub(crate) use binary_op::*;
 pub(crate) use convolution::*;
+pub(crate) use cross_entropy::*;
 pub(crate) use embedding::*;
 pub(crate) use layout::*;
 pub(crate) use linear::*;

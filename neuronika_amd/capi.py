@@ -149,6 +149,9 @@ _SIGS = {
     "nk_loss_bwd": [VP, C.c_int, VP, VP, VP, VP, c_intp, C.c_int, C.c_int],
     "nk_nll_fwd": [VP, VP, VP, c_intp, C.c_int, C.c_int, VP],
     "nk_nll_bwd": [VP, VP, VP, VP, c_intp, C.c_int, C.c_int],
+    "nk_cross_entropy_fwd": [VP, VP, VP, c_intp, C.c_int, C.c_int, C.c_longlong, C.c_double, VP, VP],
+    "nk_cross_entropy_bwd": [VP, VP, VP, VP, VP, VP, c_intp, C.c_int, C.c_int, C.c_longlong, C.c_double],
+    "nk_cross_entropy_bwd_assign": [VP, VP, VP, VP, VP, VP, c_intp, C.c_int, C.c_int, C.c_longlong, C.c_double],
     "nk_mv_fwd": [VP, VP, VP, VP, C.c_int, C.c_int],
     "nk_mv_bwd_left": [VP, VP, VP, VP, C.c_int, C.c_int],
     "nk_mv_bwd_right": [VP, VP, VP, VP, C.c_int, C.c_int],
@@ -725,6 +728,19 @@ def nll_fwd(dev, x, t, out, reduction="mean"):
 
 def nll_bwd(dev, dx, g, t, reduction="mean"):
     check(lib.nk_nll_bwd(dev.h, dx.p, g.p, t.p, dx.shape_c(), dx.ndim, REDUCTION[reduction]))
+
+
+def cross_entropy_fwd(dev, x, t, lse, out, shape, reduction="mean", ignore_index=-1, label_smoothing=0.0):
+    """out[0] = the cross entropy of the logits x `shape` = (N, C, d1..dk) against the ids t (N, d1..dk), stored as f32; lse: one
+    float per position (arrays may be flat or offset views: the shape is given)"""
+    check(lib.nk_cross_entropy_fwd(dev.h, _p(x), _p(t), ints(shape), len(shape), REDUCTION[reduction], int(ignore_index),
+                                   float(label_smoothing), _p(lse), _p(out)))
+
+
+def cross_entropy_bwd(dev, dx, g, x, t, lse, shape, reduction="mean", ignore_index=-1, label_smoothing=0.0, assign=False):
+    """dx += (or, `assign`, =) g[0] * d(loss) / dx, softmax recomputed from x and the forward's lse"""
+    check((lib.nk_cross_entropy_bwd_assign if assign else lib.nk_cross_entropy_bwd)(
+        dev.h, _p(dx), _p(g), _p(x), _p(t), _p(lse), ints(shape), len(shape), REDUCTION[reduction], int(ignore_index), float(label_smoothing)))
 
 
 def mv_fwd(dev, A, x, y):

@@ -9,6 +9,7 @@
 //                  pair in the workspace; a second kernel sums the splits in a fixed order.  No atomics: results repeat bit for bit.
 #include "nk_common.h"
 #include "nk_embedding.h"
+#include "nk_cross_entropy.h"
 
 namespace {
 
