@@ -2956,7 +2956,12 @@ void Optimizer::register_param(const VarDiff& p) {
     steps_.push_back(0);
 }
 void Optimizer::step() {
-    for (size_t i = 0; i < params_.size(); ++i) optimize(params_[i], state_[i], ++steps_[i]);
+    // a parameter's 1-based step number advances only once its update has been issued: a refused launch (Adam and a decayed
+    // Adagrad refuse while the stream is captured) throws out of `optimize` and must leave the bias corrections on schedule
+    for (size_t i = 0; i < params_.size(); ++i) {
+        optimize(params_[i], state_[i], steps_[i] + 1);
+        ++steps_[i];
+    }
 }
 void Optimizer::zero_grad() const {
     for (const VarDiff& p : params_) p.zero_grad();
@@ -2967,25 +2972,26 @@ SGD::SGD(float lr, Penalty penalty, float momentum, float dampening, bool nester
 void SGD::step() {
     // one launch per device for all registered parameters (their updates are independent; optimizer.rs:81-86)
     std::vector<float*> w, g, v;
-    std::vector<size_t> n;
+    std::vector<size_t> n, launched;
     std::vector<bool> done(params_.size(), false);
     for (size_t i = 0; i < params_.size(); ++i) {
         if (done[i]) continue;
         const DevicePtr dev = params_[i].device();
-        w.clear(); g.clear(); v.clear(); n.clear();
+        w.clear(); g.clear(); v.clear(); n.clear(); launched.clear();
         for (size_t k = i; k < params_.size(); ++k) {
             if (done[k] || params_[k].device().get() != dev.get()) continue;
             // a parameter registered twice is updated twice, one after the other (the reference iterates its list,
             // optimizer.rs:81-86): the second registration waits for a later launch instead of racing in this one
             if (std::find(w.begin(), w.end(), params_[k].var.data->ptr()) != w.end()) continue;
             done[k] = true;
-            ++steps_[k];
+            launched.push_back(k);
             HipArray& gr = params_[k].grad->borrow();
             w.push_back(params_[k].var.data->ptr()); g.push_back(gr.ptr());
             v.push_back(state_[k].empty() ? nullptr : state_[k][0]->ptr()); n.push_back(gr.len());
         }
         check(nk_sgd_step_multi(dev->raw(), (int)w.size(), w.data(), g.data(), v.data(), n.data(), lr_, momentum_, dampening_,
                                 nesterov_ ? 1 : 0, penalty_.l1, penalty_.l2));
+        for (size_t k : launched) ++steps_[k];  // counted once issued, as in Optimizer::step (SGD itself ignores the number)
     }
 }
 void SGD::optimize(const VarDiff& p, std::vector<Shared<HipArray>>& st, int) {

@@ -151,8 +151,10 @@ int nk_stream_wait_event(nk_device* dev, int on_comm_stream, nk_event* ev);
  * is recorded into a hipGraph instead of executed; nk_graph_launch replays it with one submission.  The captured
  * region must not synchronise with the host (no nk_download / nk_device_sync / item()) nor grow an allocation, and
  * it replays the SAME launches: scalars baked into kernel arguments (the learning rate) stay what they were at capture
- * time.  Calls whose kernel arguments must change from call to call REFUSE to be captured (NK_ERR_INVALID) instead of
- * freezing them: optimizer steps that depend on the step count (nk_adam_step: 1 - beta^step; nk_adagrad_step with
+ * time.  A captured SGD / RMSProp / undecayed-Adagrad step therefore keeps the rate it was captured with: `set_lr` or an
+ * lr_scheduler step after the capture changes the host's value, not what a replay applies - capture again after
+ * changing the rate (tests/test_gpu_tape_optim.py pins this).  Calls whose kernel arguments must change from call to
+ * call REFUSE to be captured (NK_ERR_INVALID) instead of freezing them: optimizer steps that depend on the step count (nk_adam_step: 1 - beta^step; nk_adagrad_step with
  * lr_decay != 0), and the forwards that draw a dropout mask (nk_dropout_fwd / nk_scale_softmax_dropout_fwd /
  * nk_attention_fwd with train != 0 and 0 < p < 1: the Philox offset - every replay would drop the same elements).
  * SGD / RMSProp steps, evaluation-mode and p = 0 dropout capture fine.  A workspace the
