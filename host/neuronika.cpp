@@ -909,6 +909,31 @@ struct LossBwd : Backward {
     void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
 };
 
+// Smooth and gated activations (ours; the reference has no such node; semantics in neuronika_hip.h): one forward node, one backward
+// entry that keeps the INPUT and recomputes from it.  `H` == 0: pointwise over the whole array; otherwise the gated form over
+// (rows, 2 H).  The first writer of the input's gradient takes the assign form.
+struct ActivationFwd : Forward {
+    int act = 0, H = 0;
+    Shared<HipArray> x, y;
+    void forward() const override {
+        if (H == 0) check(nk_activation_fwd(D(x), act, x->ptr(), y->ptr(), x->len()));
+        else check(nk_glu_fwd(D(x), act, x->ptr(), y->ptr(), (long long)(y->len() / (size_t)H), H));
+    }
+};
+struct ActivationBwd : Backward {
+    int act = 0, H = 0;
+    Shared<HipArray> x;
+    Shared<Gradient> dx, g;
+    void backward() const override {
+        const HipArray& G = g->borrow();
+        bool assign = false;
+        HipArray& d = dx->borrow_first_write(assign);
+        if (H == 0) check((assign ? nk_activation_bwd_assign : nk_activation_bwd)(D(x), act, d.ptr(), G.ptr(), x->ptr(), d.len()));
+        else check((assign ? nk_glu_bwd_assign : nk_glu_bwd)(D(x), act, d.ptr(), G.ptr(), x->ptr(), (long long)(G.len() / (size_t)H), H));
+    }
+    void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
+};
+
 // Cross entropy of class logits against integer targets (ours; the reference has no such node; semantics in neuronika_hip.h):
 // log-softmax and NLL in one forward node, which owns `lse` (one float per position); the backward recomputes the softmax from the
 // logits.  The first writer of the logits' gradient takes the assign form (no memset, no read; inactive rows written as zeros).
@@ -1528,6 +1553,37 @@ static VarDiff pointwise_diff(int op, int iparam, const VarDiff& x) {
     if (op != NK_NEG) bw->ref = keeps_output ? v.data : x.var.data;
     return VarDiff::node(std::move(v), g, entry(bw, g), x.history);
 }
+// `gated`: the last axis is halved (it must be even)
+static Shared<ActivationFwd> activation_fwd_node(const Var& x, Activation act, bool gated) {
+    Shape out = x.shape();
+    int H = 0;
+    if (gated) {
+        if (out.empty() || out.back() % 2 != 0) panic("glu: the last axis must have an even extent");
+        H = out.back() / 2;
+        out.back() = H;
+        if (H == 0) panic("glu: the last axis is empty");
+    }
+    auto n = std::make_shared<ActivationFwd>();
+    n->act = (int)act; n->H = H; n->x = x.data; n->y = zeros_like(x.data, out);
+    return n;
+}
+static Var activation_var(const Var& x, Activation act, bool gated) {
+    auto n = activation_fwd_node(x, act, gated);
+    auto y = n->y;
+    return Var::node(y, n, x.history);
+}
+static VarDiff activation_diff(const VarDiff& x, Activation act, bool gated) {
+    auto n = activation_fwd_node(x.var, act, gated);
+    auto y = n->y;
+    Var v = Var::node(y, n, x.var.history);
+    auto g = std::make_shared<Gradient>(v.device(), v.shape());
+    auto bw = std::make_shared<ActivationBwd>();
+    bw->act = n->act; bw->H = n->H; bw->x = x.var.data; bw->dx = x.grad; bw->g = g;
+    return VarDiff::node(std::move(v), g, entry(bw, g), x.history);
+}
+Var Var::gelu(bool tanh_approx) const { return activation_var(*this, tanh_approx ? Activation::GeluTanh : Activation::Gelu, false); }
+Var Var::silu() const { return activation_var(*this, Activation::Silu, false); }
+Var Var::glu(Activation gate) const { return activation_var(*this, gate, true); }
 Var Var::neg() const { return pointwise_var(NK_NEG, 0, *this); }
 Var Var::pow(int e) const { return pointwise_var(NK_POW, e, *this); }
 Var Var::sqrt() const { return pointwise_var(NK_SQRT, 0, *this); }
@@ -2003,6 +2059,9 @@ VarDiff VarDiff::sqrt() const { return pointwise_diff(NK_SQRT, 0, *this); }
 VarDiff VarDiff::leaky_relu() const { return pointwise_diff(NK_LEAKY_RELU, 0, *this); }
 VarDiff VarDiff::softplus() const { return pointwise_diff(NK_SOFTPLUS, 0, *this); }
 VarDiff VarDiff::sigmoid() const { return pointwise_diff(NK_SIGMOID, 0, *this); }
+VarDiff VarDiff::gelu(bool tanh_approx) const { return activation_diff(*this, tanh_approx ? Activation::GeluTanh : Activation::Gelu, false); }
+VarDiff VarDiff::silu() const { return activation_diff(*this, Activation::Silu, false); }
+VarDiff VarDiff::glu(Activation gate) const { return activation_diff(*this, gate, true); }
 VarDiff VarDiff::tanh() const { return pointwise_diff(NK_TANH, 0, *this); }
 VarDiff VarDiff::ln() const { return pointwise_diff(NK_LN, 0, *this); }
 VarDiff VarDiff::exp() const { return pointwise_diff(NK_EXP, 0, *this); }
@@ -2402,6 +2461,12 @@ VarDiff LayerNorm::forward(const Var& input) const {
 VarDiff LayerNorm::forward(const VarDiff& input) const {
     return elementwise_affine ? input.layer_norm(weight, bias, eps) : input.layer_norm(normalized_shape, eps);
 }
+Var GELU::forward(const Var& input) const { return input.gelu(approximate_tanh); }
+VarDiff GELU::forward(const VarDiff& input) const { return input.gelu(approximate_tanh); }
+Var SiLU::forward(const Var& input) const { return input.silu(); }
+VarDiff SiLU::forward(const VarDiff& input) const { return input.silu(); }
+Var GLU::forward(const Var& input) const { return input.glu(gate); }
+VarDiff GLU::forward(const VarDiff& input) const { return input.glu(gate); }
 CrossEntropyLoss::CrossEntropyLoss(Reduction reduction, long ignore_index, double label_smoothing)
     : reduction(reduction), ignore_index(ignore_index < 0 ? -1 : ignore_index), label_smoothing(label_smoothing) {
     if (!(label_smoothing >= 0.0 && label_smoothing < 1.0)) panic("CrossEntropyLoss: label_smoothing must be in [0, 1), got " + std::to_string(label_smoothing));

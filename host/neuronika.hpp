@@ -252,6 +252,9 @@ struct BackwardEntry {
 };
 
 enum class Reduction { Sum = 0, Mean = 1 };  // lib.rs:29-36
+// The smooth activations of neuronika_hip.h (`enum nk_activation`, same values; ours: the reference has none of them): the gate of
+// `glu`, and what `gelu` / `silu` run
+enum class Activation { Gelu = 0, GeluTanh = 1, Silu = 2, Sigmoid = 3 };
 
 class VarDiff;
 
@@ -296,6 +299,13 @@ class Var {
     Var tanh() const;
     Var ln() const;
     Var exp() const;
+    // Smooth and gated activations (ours: the reference has none; semantics in neuronika_hip.h), ONE node each:
+    // gelu: x Phi(x) (torch's approximate="none"), or its tanh form; silu: x sigma(x);
+    // glu: a * gate(b) over the two halves (a, b) of the last axis, which must be even - Sigmoid is torch's F.glu, Gelu is GeGLU,
+    // Silu is SwiGLU
+    Var gelu(bool tanh_approx = false) const;
+    Var silu() const;
+    Var glu(Activation gate = Activation::Sigmoid) const;
     Var unsqueeze(int axis) const;
     // Pooling over the spatial axes of an (N, C, spatial...) input (ours: the reference has none; semantics in neuronika_hip.h):
     // nd = rank - 2 = the length of `kernel`, `stride` (empty: stride = kernel) and `padding` (empty: zeros); floor mode, dilation 1.
@@ -429,6 +439,11 @@ class VarDiff {
     VarDiff tanh() const;
     VarDiff ln() const;
     VarDiff exp() const;
+    // ONE forward node and ONE backward entry each, which keeps the INPUT and recomputes from it; a gradient's first writer assigns,
+    // a later one accumulates
+    VarDiff gelu(bool tanh_approx = false) const;
+    VarDiff silu() const;
+    VarDiff glu(Activation gate = Activation::Sigmoid) const;
     VarDiff unsqueeze(int axis) const;
     // the differentiable max-pool node owns the int32 offsets of the selected elements (4 bytes per output)
     VarDiff max_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding) const;
@@ -674,6 +689,25 @@ struct Embedding {
     Embedding(DevicePtr dev, size_t num_embeddings, size_t embedding_dim, long padding_idx = -1, uint64_t seed = 0);
     Embedding(VarDiff weight, long padding_idx = -1);  // a table built elsewhere (deserialised, or shared with another module)
     VarDiff forward(const Var& indices) const;
+};
+
+// Activation modules (ours: the reference has none; `Var / VarDiff::gelu / silu / glu`).  No parameters.
+struct GELU {
+    bool approximate_tanh = false;
+    explicit GELU(bool approximate_tanh = false) : approximate_tanh(approximate_tanh) {}
+    Var forward(const Var& input) const;
+    VarDiff forward(const VarDiff& input) const;
+};
+struct SiLU {
+    Var forward(const Var& input) const;
+    VarDiff forward(const VarDiff& input) const;
+};
+// forward(x) = x.glu(gate): the last axis (even) is halved
+struct GLU {
+    Activation gate = Activation::Sigmoid;
+    explicit GLU(Activation gate = Activation::Sigmoid) : gate(gate) {}
+    Var forward(const Var& input) const;
+    VarDiff forward(const VarDiff& input) const;
 };
 
 // Cross entropy criterion (ours: the reference has no such layer): forward(logits, target) = logits.cross_entropy(target, reduction,

@@ -44,6 +44,8 @@ PYBIND11_MODULE(_tape, m) {
         .def("raw", [](const Device& d) { return (uintptr_t)d.raw(); });
 
     py::enum_<Reduction>(m, "Reduction").value("Sum", Reduction::Sum).value("Mean", Reduction::Mean);
+    py::enum_<Activation>(m, "Activation")
+        .value("Gelu", Activation::Gelu).value("GeluTanh", Activation::GeluTanh).value("Silu", Activation::Silu).value("Sigmoid", Activation::Sigmoid);
 
     py::class_<Status>(m, "Status")  // `Rc<Cell<bool>>` train/eval switch of the Dropout nodes
         .def(py::init([](bool v) { return Status{std::make_shared<bool>(v)}; }), py::arg("train") = true)
@@ -63,6 +65,7 @@ PYBIND11_MODULE(_tape, m) {
         .def("history_len", [](const Var& v) { return v.history.len(); })
         .def("sum", &Var::sum).def("mean", &Var::mean).def("relu", &Var::relu)
         .def("__neg__", &Var::neg).def("pow", &Var::pow).def("sqrt", &Var::sqrt).def("leaky_relu", &Var::leaky_relu)
+        .def("gelu", &Var::gelu, py::arg("tanh_approx") = false).def("silu", &Var::silu).def("glu", &Var::glu, py::arg("gate") = Activation::Sigmoid)
         .def("softplus", &Var::softplus).def("sigmoid", &Var::sigmoid).def("tanh", &Var::tanh).def("ln", &Var::ln)
         .def("exp", &Var::exp).def("unsqueeze", &Var::unsqueeze)
         .def("max_pool", &Var::max_pool, py::arg("kernel"), py::arg("stride") = std::vector<int>{}, py::arg("padding") = std::vector<int>{})
@@ -142,6 +145,7 @@ PYBIND11_MODULE(_tape, m) {
             return Py_REFCNT(self.ptr()) <= 1 ? std::move(v).relu() : v.relu();
         })
         .def("__neg__", &VarDiff::neg).def("pow", &VarDiff::pow).def("sqrt", &VarDiff::sqrt).def("leaky_relu", &VarDiff::leaky_relu)
+        .def("gelu", &VarDiff::gelu, py::arg("tanh_approx") = false).def("silu", &VarDiff::silu).def("glu", &VarDiff::glu, py::arg("gate") = Activation::Sigmoid)
         .def("softplus", &VarDiff::softplus).def("sigmoid", &VarDiff::sigmoid).def("tanh", &VarDiff::tanh).def("ln", &VarDiff::ln)
         .def("exp", &VarDiff::exp).def("unsqueeze", &VarDiff::unsqueeze)
         .def("max_pool", &VarDiff::max_pool, py::arg("kernel"), py::arg("stride") = std::vector<int>{}, py::arg("padding") = std::vector<int>{})
@@ -314,6 +318,20 @@ PYBIND11_MODULE(_tape, m) {
         .def_readonly("elementwise_affine", &nn::LayerNorm::elementwise_affine)
         .def("forward", py::overload_cast<const Var&>(&nn::LayerNorm::forward, py::const_))
         .def("forward", py::overload_cast<const VarDiff&>(&nn::LayerNorm::forward, py::const_));
+    py::class_<nn::GELU>(nn, "GELU")
+        .def(py::init<bool>(), py::arg("approximate_tanh") = false)
+        .def_readonly("approximate_tanh", &nn::GELU::approximate_tanh)
+        .def("forward", py::overload_cast<const Var&>(&nn::GELU::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::GELU::forward, py::const_));
+    py::class_<nn::SiLU>(nn, "SiLU")
+        .def(py::init<>())
+        .def("forward", py::overload_cast<const Var&>(&nn::SiLU::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::SiLU::forward, py::const_));
+    py::class_<nn::GLU>(nn, "GLU")
+        .def(py::init<Activation>(), py::arg("gate") = Activation::Sigmoid)
+        .def_readonly("gate", &nn::GLU::gate)
+        .def("forward", py::overload_cast<const Var&>(&nn::GLU::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::GLU::forward, py::const_));
     py::class_<nn::CrossEntropyLoss>(nn, "CrossEntropyLoss")
         .def(py::init<Reduction, long, double>(), py::arg("reduction") = Reduction::Mean, py::arg("ignore_index") = -1, py::arg("label_smoothing") = 0.0)
         .def_readonly("reduction", &nn::CrossEntropyLoss::reduction)

@@ -505,6 +505,41 @@ int nk_cross_entropy_bwd(nk_device* dev, float* dx, const float* g, const float*
 int nk_cross_entropy_bwd_assign(nk_device* dev, float* dx, const float* g, const float* x, const float* target, const float* lse,
                                 const int* shape, int nd, int reduction, long long ignore_index, double label_smoothing);
 
+/* ------------------------------------------------------------------ smooth and gated activations */
+/* GELU, SiLU and the gated (GLU) family: the activation of a transformer's feed-forward block.  Ours: the reference has no such
+ * node (its pointwise set is the nk_unary_op one above).  Each is ONE streaming pass forward and ONE backward; the backward keeps
+ * the INPUT x and recomputes from it, so nothing but x is saved.
+ *   GELU       y = x Phi(x), Phi(x) = 0.5 erfc(-x / sqrt 2)                  y' = Phi(x) + x phi(x), phi(x) = exp(-x^2 / 2) / sqrt(2 pi)
+ *              (torch's approximate="none"; the erfc form, so the negative tail does not cancel)
+ *   GELU_TANH  y = 0.5 x (1 + tanh u), u = sqrt(2 / pi) (x + 0.044715 x^3)   y' = the derivative of that expression
+ *              (torch's approximate="tanh"; evaluated as x sigma(2 u), which is the same function without the cancellation)
+ *   SILU       y = x sigma(x), sigma(x) = 1 / (1 + exp(-x))                  y' = sigma(x) (1 + x (1 - sigma(x)))
+ *   SIGMOID    y = sigma(x)                                                  y' = sigma(x) (1 - sigma(x))
+ *              (here so that torch's plain `glu` is expressible; the tape's sigmoid() stays the NK_SIGMOID unary node)
+ * A NaN stays in its own element.  For every finite f32 x, y and y' are finite and no inf * 0 is formed: sigma is taken from
+ * exp(-|v|), x^3 may overflow into it, x^2 is clamped where y' has already reached its limit, exp(-x^2 / 2) underflows to 0.
+ *   fwd: y = act(x), n elements.   bwd: dx += g act'(x).   bwd_assign: what bwd leaves in an all-zero dx, written without
+ *   reading it (see "first-write variants").
+ * Gated form over the two halves of the last axis: x is (rows, 2 H) contiguous, y and g are (rows, H);
+ *       y[r, j] = x[r, j] act(x[r, H + j])          (a = x[r, j], b = x[r, H + j])
+ *       dx[r, j] (+)= g[r, j] act(b)                dx[r, H + j] (+)= g[r, j] a act'(b)
+ *   act = SIGMOID is torch's F.glu, GELU is GeGLU, SILU is SwiGLU.  The products are ordinary f32 products: a and act(b) both
+ *   near the top of the range overflow as a * b would.
+ * Refused with NK_ERR_INVALID, the message naming the argument, before anything else is looked at: an unknown activation; H <= 0;
+ * rows < 0; rows * 2 H beyond the index type of the gated kernels (2^31 - 1 elements); a null pointer or one that is not 16-byte
+ * aligned (every allocation of this library is; an offset view must keep the alignment).  The device handle is looked at last.
+ * n == 0 and rows == 0 succeed and launch nothing (pointers are then not looked at).
+ * Kernels (documented because tests choose shapes against them): 16-byte accesses with a scalar tail of n % 4; the gated form
+ * walks (row, j / 4) with 16-byte accesses when H % 4 == 0 and (row, j) with scalars for any other H.  No atomics: two calls on
+ * the same data give the same bits. */
+enum nk_activation { NK_ACT_GELU = 0, NK_ACT_GELU_TANH = 1, NK_ACT_SILU = 2, NK_ACT_SIGMOID = 3 };
+int nk_activation_fwd(nk_device* dev, int act, const float* x, float* y, size_t n);
+int nk_activation_bwd(nk_device* dev, int act, float* dx, const float* g, const float* x, size_t n);
+int nk_activation_bwd_assign(nk_device* dev, int act, float* dx, const float* g, const float* x, size_t n);
+int nk_glu_fwd(nk_device* dev, int act, const float* x, float* y, long long rows, int H);
+int nk_glu_bwd(nk_device* dev, int act, float* dx, const float* g, const float* x, long long rows, int H);
+int nk_glu_bwd_assign(nk_device* dev, int act, float* dx, const float* g, const float* x, long long rows, int H);
+
 /* ------------------------------------------------------------------ GEMV / dot ---------- */
 /* MatrixVectorMul node/matrix_vector_mul/mod.rs:31-41  y(n) = A(n,m).x(m);  BackwardLeft :63-69  dA += g (x) x;
  * BackwardRight :92-102  dx += A^T.g */

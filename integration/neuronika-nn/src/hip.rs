@@ -18,7 +18,7 @@ use std::{cell::Cell, rc::Rc};
 
 use ndarray::{Array, Dimension, Ix0, Ix1, Ix2, Ix3, Ix4, Ix5, RemoveAxis};
 use neuronika_variable::{
-    hip::{Device, HipVar, HipVarDiff, PaddingMode},
+    hip::{Device, Gate, HipVar, HipVarDiff, PaddingMode},
     Reduction,
 };
 use rand::distributions::{Distribution, Uniform};
@@ -225,6 +225,51 @@ impl Embedding {
     /// ONE forward node (`nk_embedding_fwd`) and ONE backward entry (`nk_embedding_bwd`).
     pub fn forward<E: Dimension + 'static>(&self, indices: HipVar<E>) -> HipVarDiff<E::Larger> {
         self.weight.clone().embedding(indices, self.padding_idx)
+    }
+}
+
+/// GELU (the reference has no such layer; semantics in `include/neuronika_hip.h`): `x Phi(x)`, or its tanh form when
+/// `approximate_tanh` is set.  No parameters; ONE forward node and ONE backward entry.
+pub struct GELU {
+    pub approximate_tanh: bool,
+}
+
+impl GELU {
+    pub fn new(approximate_tanh: bool) -> Self {
+        Self { approximate_tanh }
+    }
+
+    pub fn forward<D: Dimension + 'static>(&self, input: HipVarDiff<D>) -> HipVarDiff<D> {
+        if self.approximate_tanh {
+            input.gelu_tanh()
+        } else {
+            input.gelu()
+        }
+    }
+}
+
+/// SiLU `x sigma(x)` (the reference has no such layer).  No parameters.
+pub struct SiLU;
+
+impl SiLU {
+    pub fn forward<D: Dimension + 'static>(&self, input: HipVarDiff<D>) -> HipVarDiff<D> {
+        input.silu()
+    }
+}
+
+/// Gated linear unit (the reference has no such layer): `a * gate(b)` over the two halves of the input's last axis.
+/// `Gate::Sigmoid` is GLU, `Gate::Gelu` GeGLU, `Gate::Silu` SwiGLU.  No parameters.
+pub struct GLU {
+    pub gate: Gate,
+}
+
+impl GLU {
+    pub fn new(gate: Gate) -> Self {
+        Self { gate }
+    }
+
+    pub fn forward<D: Dimension + 'static>(&self, input: HipVarDiff<D>) -> HipVarDiff<D> {
+        input.glu(self.gate)
     }
 }
 

@@ -16,6 +16,7 @@ use super::{
     dp::GradientSync,
     hiparray::HipArray,
     node::{
+        Activation, ActivationBackward, Glu, GluBackward,
         AttentionState, BinaryOp, BinaryOperation, BinaryOperationBackwardLeft, BinaryOperationBackwardRight, Chunk, ChunkBackward,
         Convolution, ConvolutionBackwardInput, ConvolutionBackwardKernel, ConvolutionBackwardKernelBias, ConvolutionBackwardPadded, ConvolutionBias,
         ConvolutionBiasPadded, CrossEntropy, CrossEntropyBackward, Dropout, Embedding, EmbeddingBackward,
@@ -87,6 +88,16 @@ pub enum PaddingMode {
     Constant(f32),
     Reflective,
     Replicative,
+}
+
+/// The gate of `glu` (ours: the reference has no gated activation): a value of `enum nk_activation` in `include/neuronika_hip.h`.
+/// `Sigmoid` is GLU (torch's `F.glu`), `Gelu` / `GeluTanh` are GeGLU, `Silu` is SwiGLU.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Gate {
+    Gelu = 0,
+    GeluTanh = 1,
+    Silu = 2,
+    Sigmoid = 3,
 }
 
 impl From<PaddingMode> for PadMode {
@@ -200,6 +211,39 @@ where
     pub fn relu(self) -> HipVar<D> {
         let data = shared(self.data.borrow().dimension(), &self.device());
         let op = ReLU::new(self.data, data.clone());
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    /// GELU `x Phi(x)` in the erfc form (ours: the reference has none; semantics in `include/neuronika_hip.h`): ONE node.
+    pub fn gelu(self) -> HipVar<D> {
+        self.activation(Gate::Gelu)
+    }
+
+    /// GELU in the tanh form, `0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3)))`: ONE node.
+    pub fn gelu_tanh(self) -> HipVar<D> {
+        self.activation(Gate::GeluTanh)
+    }
+
+    /// SiLU `x sigma(x)`: ONE node.
+    pub fn silu(self) -> HipVar<D> {
+        self.activation(Gate::Silu)
+    }
+
+    fn activation(self, act: Gate) -> HipVar<D> {
+        let data = shared(self.data.borrow().dimension(), &self.device());
+        let op = Activation::new(self.data, data.clone(), act as i32);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    /// `a * gate(b)` over the two halves `(a, b)` of the last axis, which must be even: ONE node (`nk_glu_fwd`).
+    pub fn glu(self, gate: Gate) -> HipVar<D> {
+        let mut dim = self.data.borrow().dimension();
+        let last = dim.ndim().checked_sub(1).expect("glu: a scalar has no last axis");
+        assert!(dim[last] % 2 == 0 && dim[last] > 0, "glu: the last axis must have an even extent");
+        dim[last] /= 2;
+        let half = dim[last];
+        let data = shared(dim, &self.device());
+        let op = Glu::new(self.data, data.clone(), gate as i32, half);
         HipVar::node(data, Rc::new(op), self.history)
     }
 
@@ -679,6 +723,41 @@ where
         let grad = self.new_grad(self.grad.shape());
         let op = ReLUBackward::new(self.grad.clone(), self.var.data.clone(), grad.clone());
         let var = self.var.relu();
+        HipVarDiff::node(var, grad.clone(), (Rc::new(op), grad), self.history)
+    }
+
+    /// GELU in the erfc form: ONE forward node and ONE backward entry, which keeps the input and recomputes from it.
+    pub fn gelu(self) -> HipVarDiff<D> {
+        self.activation(Gate::Gelu)
+    }
+
+    /// GELU in the tanh form: ONE forward node and ONE backward entry.
+    pub fn gelu_tanh(self) -> HipVarDiff<D> {
+        self.activation(Gate::GeluTanh)
+    }
+
+    /// SiLU: ONE forward node and ONE backward entry.
+    pub fn silu(self) -> HipVarDiff<D> {
+        self.activation(Gate::Silu)
+    }
+
+    fn activation(self, act: Gate) -> HipVarDiff<D> {
+        let grad = self.new_grad(self.grad.shape());
+        let op = ActivationBackward::new(self.grad.clone(), self.var.data.clone(), grad.clone(), act as i32);
+        let var = self.var.activation(act);
+        HipVarDiff::node(var, grad.clone(), (Rc::new(op), grad), self.history)
+    }
+
+    /// `a * gate(b)` over the two halves of the last axis: ONE forward node and ONE backward entry (`GluBackward`).
+    pub fn glu(self, gate: Gate) -> HipVarDiff<D> {
+        let mut dim = self.var.data.borrow().dimension();
+        let last = dim.ndim().checked_sub(1).expect("glu: a scalar has no last axis");
+        assert!(dim[last] % 2 == 0 && dim[last] > 0, "glu: the last axis must have an even extent");
+        dim[last] /= 2;
+        let half = dim[last];
+        let grad = self.new_grad(dim);
+        let op = GluBackward::new(self.grad.clone(), self.var.data.clone(), grad.clone(), gate as i32, half);
+        let var = self.var.glu(gate);
         HipVarDiff::node(var, grad.clone(), (Rc::new(op), grad), self.history)
     }
 

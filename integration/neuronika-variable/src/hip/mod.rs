@@ -12,6 +12,6 @@ pub use {
     device::Device,
     dp::{Communicator, GradientSync, SyncEntry},
     hiparray::HipArray,
-    hipvar::{manual_seed, HipVar, HipVarDiff, PaddingMode},
+    hipvar::{manual_seed, Gate, HipVar, HipVarDiff, PaddingMode},
     optimizer::SGD,
 };

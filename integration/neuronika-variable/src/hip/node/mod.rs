@@ -4,6 +4,7 @@
 //! the BASELINE configurations (MatMul / MatMulT, Convolution, broadcast binaries, ReLU, Softmax, Dropout, Sum,
 //! SquaredError, the fused attention core of the composed MHA) and their glue (LogSoftmax, Mean, Pad in all four modes, Chunk,
 //! MultiConcatenate, Transpose, the SGD / Adam steps) and the layer and batch normalisation and the max / average pooling the reference lacks.  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
+mod activation;
 mod attention;
 mod binary_op;
 mod convolution;
@@ -19,6 +20,7 @@ mod pointwise;
 mod pooling;
 mod reduction;
 
+pub(crate) use activation::*;
 pub(crate) use attention::*;
 pub(crate) use binary_op::*;
 pub(crate) use convolution::*;

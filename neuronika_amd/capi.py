@@ -152,6 +152,12 @@ _SIGS = {
     "nk_cross_entropy_fwd": [VP, VP, VP, c_intp, C.c_int, C.c_int, C.c_longlong, C.c_double, VP, VP],
     "nk_cross_entropy_bwd": [VP, VP, VP, VP, VP, VP, c_intp, C.c_int, C.c_int, C.c_longlong, C.c_double],
     "nk_cross_entropy_bwd_assign": [VP, VP, VP, VP, VP, VP, c_intp, C.c_int, C.c_int, C.c_longlong, C.c_double],
+    "nk_activation_fwd": [VP, C.c_int, VP, VP, C.c_size_t],
+    "nk_activation_bwd": [VP, C.c_int, VP, VP, VP, C.c_size_t],
+    "nk_activation_bwd_assign": [VP, C.c_int, VP, VP, VP, C.c_size_t],
+    "nk_glu_fwd": [VP, C.c_int, VP, VP, C.c_longlong, C.c_int],
+    "nk_glu_bwd": [VP, C.c_int, VP, VP, VP, C.c_longlong, C.c_int],
+    "nk_glu_bwd_assign": [VP, C.c_int, VP, VP, VP, C.c_longlong, C.c_int],
     "nk_mv_fwd": [VP, VP, VP, VP, C.c_int, C.c_int],
     "nk_mv_bwd_left": [VP, VP, VP, VP, C.c_int, C.c_int],
     "nk_mv_bwd_right": [VP, VP, VP, VP, C.c_int, C.c_int],
@@ -741,6 +747,30 @@ def cross_entropy_bwd(dev, dx, g, x, t, lse, shape, reduction="mean", ignore_ind
     """dx += (or, `assign`, =) g[0] * d(loss) / dx, softmax recomputed from x and the forward's lse"""
     check((lib.nk_cross_entropy_bwd_assign if assign else lib.nk_cross_entropy_bwd)(
         dev.h, _p(dx), _p(g), _p(x), _p(t), _p(lse), ints(shape), len(shape), REDUCTION[reduction], int(ignore_index), float(label_smoothing)))
+
+
+ACTIVATION = {"gelu": 0, "gelu_tanh": 1, "silu": 2, "sigmoid": 3}
+
+
+def activation_fwd(dev, act, x, y, n=None):
+    """y = act(x) over n elements (default: all of x); act in ACTIVATION"""
+    check(lib.nk_activation_fwd(dev.h, ACTIVATION[act], _p(x), _p(y), x.size if n is None else n))
+
+
+def activation_bwd(dev, act, dx, g, x, n=None, assign=False):
+    """dx += (or, `assign`, =) g * act'(x), recomputed from the input x"""
+    check((lib.nk_activation_bwd_assign if assign else lib.nk_activation_bwd)(dev.h, ACTIVATION[act], _p(dx), _p(g), _p(x),
+                                                                             x.size if n is None else n))
+
+
+def glu_fwd(dev, act, x, y, rows, H):
+    """y[r, j] = x[r, j] * act(x[r, H + j]); x is (rows, 2 H), y (rows, H) (arrays may be flat or offset views: the geometry is given)"""
+    check(lib.nk_glu_fwd(dev.h, ACTIVATION[act], _p(x), _p(y), int(rows), int(H)))
+
+
+def glu_bwd(dev, act, dx, g, x, rows, H, assign=False):
+    """dx[r, j] += g * act(b), dx[r, H + j] += g * a * act'(b) (or, `assign`, =), recomputed from the input x"""
+    check((lib.nk_glu_bwd_assign if assign else lib.nk_glu_bwd)(dev.h, ACTIVATION[act], _p(dx), _p(g), _p(x), int(rows), int(H)))
 
 
 def mv_fwd(dev, A, x, y):

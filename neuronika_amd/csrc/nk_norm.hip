@@ -10,6 +10,7 @@
 #include "nk_common.h"
 #include "nk_embedding.h"
 #include "nk_cross_entropy.h"
+#include "nk_activation.h"
 
 namespace {
 
