@@ -3073,6 +3073,67 @@ void Adam::optimize(const VarDiff& p, std::vector<Shared<HipArray>>& st, int ste
                        amsgrad_ ? st[2]->ptr() : nullptr, g.len(), lr_, beta1_, beta2_, eps_, step, penalty_.l1, penalty_.l2));
 }
 
+AdamW::AdamW(float lr, float beta1, float beta2, float eps, float weight_decay, bool amsgrad)
+    : Optimizer(lr, Penalty{}, amsgrad ? 3 : 2), beta1_(beta1), beta2_(beta2), eps_(eps), weight_decay_(weight_decay), amsgrad_(amsgrad) {}
+void AdamW::step() {
+    // one call per device for all registered parameters, as SGD::step; the 1-based step number travels per parameter (a
+    // parameter registered late is at an earlier step than its neighbours in the same launch)
+    std::vector<float*> w, m, v, vmax;
+    std::vector<const float*> g;
+    std::vector<size_t> n, launched;
+    std::vector<int> step;
+    std::vector<bool> done(params_.size(), false);
+    for (size_t i = 0; i < params_.size(); ++i) {
+        if (done[i]) continue;
+        const DevicePtr dev = params_[i].device();
+        w.clear(); g.clear(); m.clear(); v.clear(); vmax.clear(); n.clear(); step.clear(); launched.clear();
+        for (size_t k = i; k < params_.size(); ++k) {
+            if (done[k] || params_[k].device().get() != dev.get()) continue;
+            // registered twice: the second update waits for a later call (nk_adamw_step_multi refuses one w twice)
+            if (std::find(w.begin(), w.end(), params_[k].var.data->ptr()) != w.end()) continue;
+            done[k] = true;
+            launched.push_back(k);
+            HipArray& gr = params_[k].grad->borrow();
+            w.push_back(params_[k].var.data->ptr()); g.push_back(gr.ptr());
+            m.push_back(state_[k][0]->ptr()); v.push_back(state_[k][1]->ptr());
+            vmax.push_back(amsgrad_ ? state_[k][2]->ptr() : nullptr);
+            n.push_back(gr.len()); step.push_back(steps_[k] + 1);
+        }
+        check(nk_adamw_step_multi(dev->raw(), (int)w.size(), w.data(), g.data(), m.data(), v.data(), vmax.data(), n.data(), step.data(),
+                                  lr_, beta1_, beta2_, eps_, weight_decay_));
+        for (size_t k : launched) ++steps_[k];  // only once issued: a refused capture leaves the bias corrections on schedule
+    }
+}
+void AdamW::optimize(const VarDiff& p, std::vector<Shared<HipArray>>& st, int step) {
+    HipArray& g = p.grad->borrow();
+    check(nk_adamw_step(p.device()->raw(), p.var.data->ptr(), g.ptr(), st[0]->ptr(), st[1]->ptr(), amsgrad_ ? st[2]->ptr() : nullptr,
+                        g.len(), lr_, beta1_, beta2_, eps_, step, weight_decay_));
+}
+
+// {total_norm, coef} of `params` into out[0..2) and the gradients scaled; returns the 0-d view of out[0]
+static Var clip_into(const std::vector<VarDiff>& params, float max_norm, const Shared<HipArray>& out) {
+    std::vector<float*> g;
+    std::vector<size_t> n;
+    for (const VarDiff& p : params) {
+        if (p.device().get() != out->device().get())
+            panic("clip_grad_norm: the parameters live on more than one device (a cross-device norm is not offered)");
+        HipArray& gr = p.grad->borrow();
+        if (std::find(g.begin(), g.end(), gr.ptr()) != g.end()) continue;  // listed twice: counted once
+        g.push_back(gr.ptr()); n.push_back(gr.len());
+    }
+    check(nk_clip_grad_norm_multi(out->device()->raw(), (int)g.size(), g.data(), n.data(), max_norm, out->ptr()));
+    return Var::leaf(std::make_shared<HipArray>(out, 0, Shape{}));
+}
+Var clip_grad_norm(const std::vector<VarDiff>& params, float max_norm) {
+    if (params.empty()) panic("clip_grad_norm: no parameters");
+    return clip_into(params, max_norm, std::make_shared<HipArray>(params[0].device(), Shape{2}, HipArray::Uninit{}));
+}
+Var Optimizer::clip_grad_norm(float max_norm) {
+    if (params_.empty()) panic("clip_grad_norm: no parameters registered");
+    if (!clip_out_) clip_out_ = std::make_shared<HipArray>(params_[0].device(), Shape{2}, HipArray::Uninit{});
+    return clip_into(params_, max_norm, clip_out_);
+}
+
 Adagrad::Adagrad(float lr, float lr_decay, float eps, Penalty penalty)
     : Optimizer(lr, penalty, 1), lr_decay_(lr_decay), eps_(eps) {}
 void Adagrad::optimize(const VarDiff& p, std::vector<Shared<HipArray>>& st, int step) {

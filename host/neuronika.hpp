@@ -907,6 +907,10 @@ class Optimizer {
     float get_lr() const { return lr_; }
     void set_lr(float lr) { lr_ = lr; }
     const std::vector<VarDiff>& params() const { return params_; }
+    // `optim::clip_grad_norm` over the registered parameters, whatever the optimizer.  The norm lands in a buffer the optimizer
+    // keeps (allocated by the first call), so a later call allocates nothing and can be captured; the returned Var aliases that
+    // buffer and holds the norm of the LATEST call.
+    Var clip_grad_norm(float max_norm);
 
    protected:
     Optimizer(float lr, Penalty penalty, int nstate) : lr_(lr), penalty_(penalty), nstate_(nstate) {}
@@ -921,7 +925,16 @@ class Optimizer {
 
    private:
     int nstate_;
+    Shared<HipArray> clip_out_;  // {total_norm, coef} of the latest clip_grad_norm
 };
+
+// Global-norm gradient clipping (ours; nk_clip_grad_norm_multi): every gradient of `params` is scaled by
+// min(1, max_norm / (norm + 1e-6)), `norm` the L2 norm over ALL of them, summed in f64 on the device.  Returns a 0-d Var on the
+// device that holds the norm before clipping; nothing synchronises with the host (`item()` is the caller's synchronisation).
+// A parameter listed twice counts once; max_norm = +inf measures only.  The parameters must live on one device (a cross-device
+// norm is not offered).  Under data parallelism call it after `dp::GradientSync::join()`: before that the buffers hold this
+// rank's share, and every rank must clip the summed gradient by the same coefficient.
+Var clip_grad_norm(const std::vector<VarDiff>& params, float max_norm);
 
 class SGD : public Optimizer {  // sgd/mod.rs
    public:
@@ -941,6 +954,19 @@ class Adam : public Optimizer {  // adam/mod.rs ; amsgrad/mod.rs when amsgrad = 
    private:
     void optimize(const VarDiff& p, std::vector<Shared<HipArray>>& state, int step) override;
     float beta1_, beta2_, eps_;
+    bool amsgrad_;
+};
+
+// AdamW (ours: decoupled weight decay, w *= 1 - lr * weight_decay before the Adam update; no `Penalty` - the coupled L2 of
+// `Adam` is rescaled by the Adam denominator and is a different rule).  weight_decay = 0 is `Adam` without a penalty.
+class AdamW : public Optimizer {
+   public:
+    AdamW(float lr, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, float weight_decay = 1e-2f, bool amsgrad = false);
+    void step() override;  // every registered parameter of a device in one nk_adamw_step_multi call (32 parameters a launch)
+
+   private:
+    void optimize(const VarDiff& p, std::vector<Shared<HipArray>>& state, int step) override;
+    float beta1_, beta2_, eps_, weight_decay_;
     bool amsgrad_;
 };
 

@@ -504,7 +504,14 @@ PYBIND11_MODULE(_tape, m) {
         .def("step", &optim::Optimizer::step)
         .def("zero_grad", &optim::Optimizer::zero_grad)
         .def("get_lr", &optim::Optimizer::get_lr)
-        .def("set_lr", &optim::Optimizer::set_lr);
+        .def("set_lr", &optim::Optimizer::set_lr)
+        .def("clip_grad_norm", &optim::Optimizer::clip_grad_norm, py::arg("max_norm"),
+             "Clip the registered parameters' gradients to the global L2 norm max_norm; returns the norm before clipping as a 0-d Var "
+             "on the device (item() synchronises). The Var ALIASES a buffer the optimizer keeps, which is what lets the call be "
+             "captured: it holds the norm of the LATEST call. Read it with item() before the next call if norms are collected.");
+    optim.def("clip_grad_norm", &optim::clip_grad_norm, py::arg("params"), py::arg("max_norm"),
+              "Clip the gradients of params to the global L2 norm max_norm; returns the norm before clipping as a 0-d Var on the "
+              "device in a buffer of its own (item() synchronises). A parameter listed twice counts once; +inf measures only.");
     py::class_<optim::SGD, optim::Optimizer>(optim, "SGD")
         .def(py::init([](float lr, float l1, float l2, float momentum, float dampening, bool nesterov) {
                  return new optim::SGD(lr, optim::Penalty{l1, l2}, momentum, dampening, nesterov);
@@ -517,6 +524,9 @@ PYBIND11_MODULE(_tape, m) {
              }),
              py::arg("lr"), py::arg("beta1") = 0.9f, py::arg("beta2") = 0.999f, py::arg("eps") = 1e-8f, py::arg("l1") = 0.f,
              py::arg("l2") = 0.f, py::arg("amsgrad") = false);
+    py::class_<optim::AdamW, optim::Optimizer>(optim, "AdamW")
+        .def(py::init<float, float, float, float, float, bool>(), py::arg("lr"), py::arg("beta1") = 0.9f, py::arg("beta2") = 0.999f,
+             py::arg("eps") = 1e-8f, py::arg("weight_decay") = 1e-2f, py::arg("amsgrad") = false);
     py::class_<optim::Adagrad, optim::Optimizer>(optim, "Adagrad")
         .def(py::init([](float lr, float lr_decay, float eps, float l1, float l2) {
                  return new optim::Adagrad(lr, lr_decay, eps, optim::Penalty{l1, l2});

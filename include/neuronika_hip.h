@@ -154,10 +154,10 @@ int nk_stream_wait_event(nk_device* dev, int on_comm_stream, nk_event* ev);
  * time.  A captured SGD / RMSProp / undecayed-Adagrad step therefore keeps the rate it was captured with: `set_lr` or an
  * lr_scheduler step after the capture changes the host's value, not what a replay applies - capture again after
  * changing the rate (tests/test_gpu_tape_optim.py pins this).  Calls whose kernel arguments must change from call to
- * call REFUSE to be captured (NK_ERR_INVALID) instead of freezing them: optimizer steps that depend on the step count (nk_adam_step: 1 - beta^step; nk_adagrad_step with
+ * call REFUSE to be captured (NK_ERR_INVALID) instead of freezing them: optimizer steps that depend on the step count (nk_adam_step, nk_adamw_step, nk_adamw_step_multi: 1 - beta^step; nk_adagrad_step with
  * lr_decay != 0), and the forwards that draw a dropout mask (nk_dropout_fwd / nk_scale_softmax_dropout_fwd /
  * nk_attention_fwd with train != 0 and 0 < p < 1: the Philox offset - every replay would drop the same elements).
- * SGD / RMSProp steps, evaluation-mode and p = 0 dropout capture fine.  A workspace the
+ * SGD / RMSProp steps, nk_clip_grad_norm_multi, evaluation-mode and p = 0 dropout capture fine.  A workspace the
  * device outgrows later stays allocated while any nk_graph of that device exists (captured kernels keep its address);
  * destroy a device's graphs before the device. */
 typedef struct nk_graph nk_graph;
@@ -867,6 +867,41 @@ int nk_sgd_step_multi(nk_device* dev, int count, float* const* w, float* const* 
 int nk_adam_step(nk_device* dev, float* w, float* grad, float* exp_avg, float* exp_avg_sq,
                  float* max_exp_avg_sq, size_t n, float lr, float beta1, float beta2, float eps, int step,
                  float l1, float l2);
+/* AdamW (ours: the reference has only the coupled `Penalty`, which the Adam denominator rescales) for `count` parameters in
+ * as few launches as the parameter table allows (32 entries per launch).  Per element, in f32, in this order:
+ *     w   = w * (1 - lr * weight_decay)                 skipped when weight_decay == 0
+ *     m   = m * beta1 + g * (1 - beta1)
+ *     v   = v * beta2 + g * g * (1 - beta2)
+ *     den = vmax ? (vmax = max(vmax, v)) : v
+ *     w   = w - m / (sqrt(den) / sqrt(bc2) + eps) * (lr / bc1)
+ * with bc1 = 1 - beta1^step[i], bc2 = 1 - beta2^step[i] formed on the host as nk_adam_step forms them; step[i] is the 1-based
+ * step number of parameter i.  The Adam part is the expression of nk_adam_step: weight_decay == 0 is the project's Adam
+ * without a penalty.  The gradient is read, never written.  max_exp_avg_sq == NULL, or max_exp_avg_sq[i] == NULL: no
+ * AMSGrad maximum (for that parameter).  Entries of length 0 are skipped; count == 0 does nothing.  NK_ERR_INVALID: a null
+ * table with count > 0, a null pointer in an entry of non-zero length, step[i] < 1, the same w pointer twice in one call (a
+ * caller that registers a parameter twice issues the second update in a later call).  Refuses capture like nk_adam_step:
+ * the bias corrections are kernel arguments. */
+int nk_adamw_step_multi(nk_device* dev, int count, float* const* w, const float* const* grad, float* const* exp_avg,
+                        float* const* exp_avg_sq, float* const* max_exp_avg_sq, const size_t* n, const int* step,
+                        float lr, float beta1, float beta2, float eps, float weight_decay);
+/* One parameter through the multi-parameter kernel. */
+int nk_adamw_step(nk_device* dev, float* w, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                  size_t n, float lr, float beta1, float beta2, float eps, int step, float weight_decay);
+/* Global-norm gradient clipping over a list of gradients, on the device, without a host synchronisation:
+ *     total_norm = (float)sqrt(sum over every element of (double)g^2)      every square and the whole sum in f64
+ *     coef       = max_norm / (total_norm + 1e-6f), replaced by 1.0f when it exceeds 1
+ *     g         *= coef                                                    for every gradient of the list
+ * out (device, 2 floats) receives {total_norm, coef}.  The sum has a fixed order that depends on the lengths alone (one f64
+ * partial per 4096-element chunk, the partials added in a fixed order by one block; no atomics): the result repeats bit for
+ * bit and does not depend on pointer alignment.  A coefficient of exactly 1 leaves the gradients untouched (the scaling
+ * kernel returns before it reads them); max_norm == +inf measures only (no scaling launch).  Entries of length 0 are
+ * skipped; count == 0 or all lengths 0: out = {0, 1}.  Non-finite gradients propagate as the arithmetic produces them: a NaN
+ * anywhere makes total_norm, coef and every scaled gradient NaN; an infinite norm gives coef = 0 (inf * 0 = NaN in the
+ * infinite elements).  NK_ERR_INVALID: a null table with count > 0, a null pointer in an entry of non-zero length, out ==
+ * NULL, max_norm NaN or <= 0, the same grad pointer twice in one call (a caller lists a parameter once).  Takes nothing
+ * step-dependent from the host and allocates nothing beyond the workspace: it CAN be captured, after one eager call of the
+ * same sizes (which grows the workspace). */
+int nk_clip_grad_norm_multi(nk_device* dev, int count, float* const* grad, const size_t* n, float max_norm, float* out);
 /* AdagradParam::optimize adagrad/mod.rs:113-140: clr = lr / (1 + (step-1)*lr_decay). */
 int nk_adagrad_step(nk_device* dev, float* w, float* grad, float* grad_sq, size_t n, float lr,
                     float lr_decay, float eps, int step, float l1, float l2);

@@ -13,5 +13,6 @@ pub use {
     dp::{Communicator, GradientSync, SyncEntry},
     hiparray::HipArray,
     hipvar::{manual_seed, Gate, HipVar, HipVarDiff, PaddingMode},
+    optimizer::AdamW,
     optimizer::SGD,
 };

@@ -46,3 +46,34 @@ pub(crate) fn sgd_step_multi(device: &crate::hip::device::Device, params: &[(*mu
                                nesterov as i32, l1, l2)
     });
 }
+
+/// AdamW over ALL listed parameters in as few launches as the library's parameter table allows (`nk_adamw_step_multi`, 32
+/// parameters a launch): decoupled decay `w *= 1 - lr * weight_decay`, then the Adam / AMSGrad update of `adam_step`.
+/// `params`: (weights, gradient, exp_avg, exp_avg_sq, max_exp_avg_sq or null, element count, 1-based step number) per
+/// parameter; the caller lists a parameter once per call (the library refuses the same weights twice).
+#[allow(clippy::too_many_arguments, clippy::type_complexity)]
+pub(crate) fn adamw_step_multi(device: &crate::hip::device::Device, params: &[(*mut f32, *mut f32, *mut f32, *mut f32, *mut f32, usize, i32)],
+                               lr: f32, beta1: f32, beta2: f32, eps: f32, weight_decay: f32) {
+    let w: Vec<*mut f32> = params.iter().map(|p| p.0).collect();
+    let g: Vec<*const f32> = params.iter().map(|p| p.1 as *const f32).collect();
+    let m: Vec<*mut f32> = params.iter().map(|p| p.2).collect();
+    let v: Vec<*mut f32> = params.iter().map(|p| p.3).collect();
+    let vmax: Vec<*mut f32> = params.iter().map(|p| p.4).collect();
+    let n: Vec<usize> = params.iter().map(|p| p.5).collect();
+    let step: Vec<i32> = params.iter().map(|p| p.6).collect();
+    ffi::check(unsafe {
+        ffi::nk_adamw_step_multi(device.as_raw(), w.len() as i32, w.as_ptr(), g.as_ptr(), m.as_ptr(), v.as_ptr(), vmax.as_ptr(), n.as_ptr(),
+                                 step.as_ptr(), lr, beta1, beta2, eps, weight_decay)
+    });
+}
+
+/// Global-norm clipping of the listed gradients (`nk_clip_grad_norm_multi`): `out` (device, 2 floats) receives the L2 norm
+/// over all of them (summed in f64) and the coefficient `min(1, max_norm / (norm + 1e-6))` every gradient was scaled by.  No
+/// host synchronisation.  `grads`: (gradient, element count); a gradient listed twice counts once.
+pub(crate) fn clip_grad_norm_multi(device: &crate::hip::device::Device, grads: &[(*mut f32, usize)], max_norm: f32, out: *mut f32) {
+    let mut seen = std::collections::HashSet::new();
+    let unique: Vec<&(*mut f32, usize)> = grads.iter().filter(|p| seen.insert(p.0 as usize)).collect();
+    let g: Vec<*mut f32> = unique.iter().map(|p| p.0).collect();
+    let n: Vec<usize> = unique.iter().map(|p| p.1).collect();
+    ffi::check(unsafe { ffi::nk_clip_grad_norm_multi(device.as_raw(), g.len() as i32, g.as_ptr(), n.as_ptr(), max_norm, out) });
+}

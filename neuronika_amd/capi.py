@@ -220,6 +220,9 @@ _SIGS = {
     "nk_sgd_step": [VP, VP, VP, VP, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float],
     "nk_sgd_step_multi": [VP, C.c_int, VP, VP, VP, VP, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float],
     "nk_adam_step": [VP, VP, VP, VP, VP, VP, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float],
+    "nk_adamw_step_multi": [VP, C.c_int, VP, VP, VP, VP, VP, VP, VP, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float],
+    "nk_adamw_step": [VP, VP, VP, VP, VP, VP, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float],
+    "nk_clip_grad_norm_multi": [VP, C.c_int, VP, VP, C.c_float, VP],
     "nk_adagrad_step": [VP, VP, VP, VP, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float],
     "nk_rmsprop_step": [VP, VP, VP, VP, VP, VP, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float],
     "nk_comm_unique_id": [C.c_char_p],
@@ -1034,6 +1037,31 @@ def adam_step(dev, w, grad, exp_avg, exp_avg_sq, max_exp_avg_sq=None, lr=1e-3, b
               step=1, l1=0.0, l2=0.0):
     check(lib.nk_adam_step(dev.h, w.p, grad.p, exp_avg.p, exp_avg_sq.p, _p(max_exp_avg_sq), w.size, lr, beta1, beta2,
                            eps, step, l1, l2))
+
+
+def adamw_step(dev, w, grad, exp_avg, exp_avg_sq, max_exp_avg_sq=None, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, step=1,
+               weight_decay=1e-2):
+    check(lib.nk_adamw_step(dev.h, w.p, grad.p, exp_avg.p, exp_avg_sq.p, _p(max_exp_avg_sq), w.size, lr, beta1, beta2, eps, step,
+                            weight_decay))
+
+
+def adamw_step_multi(dev, ws, grads, exp_avgs, exp_avg_sqs, max_exp_avg_sqs=None, steps=None, lr=1e-3, beta1=0.9, beta2=0.999,
+                     eps=1e-8, weight_decay=1e-2):
+    """steps: the 1-based step number of every parameter (default: 1 for all); max_exp_avg_sqs: None, or a list with None entries"""
+    n = len(ws)
+    PA = C.c_void_p * n
+    vmax = PA(*[_p(v) for v in max_exp_avg_sqs]) if max_exp_avg_sqs is not None else None
+    steps = [1] * n if steps is None else steps
+    check(lib.nk_adamw_step_multi(dev.h, n, PA(*[w.p for w in ws]), PA(*[g.p for g in grads]), PA(*[m.p for m in exp_avgs]),
+                                  PA(*[v.p for v in exp_avg_sqs]), vmax, (C.c_size_t * n)(*[w.size for w in ws]),
+                                  (C.c_int * n)(*[int(k) for k in steps]), lr, beta1, beta2, eps, weight_decay))
+
+
+def clip_grad_norm_multi(dev, grads, max_norm, out):
+    """out: a device array of 2 floats, receives {total_norm, coef}; no host synchronisation"""
+    n = len(grads)
+    check(lib.nk_clip_grad_norm_multi(dev.h, n, (C.c_void_p * n)(*[g.p for g in grads]), (C.c_size_t * n)(*[g.size for g in grads]),
+                                      max_norm, out.p))
 
 
 def adagrad_step(dev, w, grad, grad_sq, lr=1e-2, lr_decay=0.0, eps=1e-10, step=1, l1=0.0, l2=0.0):

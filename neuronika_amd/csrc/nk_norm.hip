@@ -11,6 +11,7 @@
 #include "nk_embedding.h"
 #include "nk_cross_entropy.h"
 #include "nk_activation.h"
+#include "nk_optim_multi.h"
 
 namespace {
 
