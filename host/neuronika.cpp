@@ -884,6 +884,42 @@ struct QkvAttentionBwd : Backward {
     }
 };
 
+// nn::MultiheadAttention::forward_step: one slice of T new positions per sample against the layer's key / value cache, in
+// inference.  Projections (one GEMM into qkv (n, 3d) when packed, three into q / k / v (n, d) otherwise), append, attention,
+// output projection.  `start` is the int32 image of the lengths the cache had when the node was built: a second forward() writes
+// the same rows again.
+struct DecodeStepFwd : Forward {
+    int B, T, H, dh, cap;
+    Shared<HipArray> x, w[3], b[3], wo, bo;  // packed: w[0] / b[0] are the (3d, d) / (3d) storage, the others null
+    Shared<HipArray> qkv, q, k, v, ctx, out;
+    Shared<HipArray> kc, vc, ws, start;
+    float scale;
+    bool core = false;  // every start 0, T >= 2, head size of the fused core
+    void forward() const override {
+        nk_device* dev = D(x);
+        const int n = B * T, d = H * dh;
+        const float *Q, *K, *V;
+        int ld;
+        if (qkv) {
+            check(nk_linear_fwd(dev, x->ptr(), w[0]->ptr(), b[0]->ptr(), qkv->ptr(), n, d, 3 * d));
+            Q = qkv->ptr(); K = Q + d; V = Q + 2 * d; ld = 3 * d;
+        } else {
+            Shared<HipArray> y[3] = {q, k, v};
+            for (int i = 0; i < 3; ++i) check(nk_linear_fwd(dev, x->ptr(), w[i]->ptr(), b[i]->ptr(), y[i]->ptr(), n, d, d));
+            Q = q->ptr(); K = k->ptr(); V = v->ptr(); ld = d;
+        }
+        const int* st = reinterpret_cast<const int*>(start->ptr());
+        check(nk_kv_cache_append(dev, kc->ptr(), vc->ptr(), K, V, ld, st, B, T, H, dh, cap));
+        if (core && qkv)
+            check(nk_attention_qkv_causal_fwd(dev, qkv->ptr(), nullptr, nullptr, nullptr, ctx->ptr(), B, T, H, dh, scale, 0.0, 0, 0, 0));
+        else if (core)
+            check(nk_attention_causal_fwd(dev, Q, K, V, nullptr, nullptr, nullptr, ctx->ptr(), B, T, H, dh, scale, 0.0, 0, 0, 0));
+        else
+            check(nk_attention_decode_fwd(dev, Q, ld, kc->ptr(), vc->ptr(), st, ctx->ptr(), ws->ptr(), B, T, H, dh, cap, scale));
+        check(nk_linear_fwd(dev, ctx->ptr(), wo->ptr(), bo->ptr(), out->ptr(), n, d, d));
+    }
+};
+
 // Scalar criteria: node/{absolute_error,bce,bce_with_logits,kldiv,nll}/mod.rs.  kind -1 = NLL.
 struct LossFwd : Forward {
     int kind;
@@ -2771,22 +2807,23 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     bw->g = g; bw->scale = scale; bw->p = m.drop.p; bw->status = m.drop.status; bw->causal = m.causal;
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(hb));
 }
+// q / k / v are public members: the packed path is only valid while they still ARE the views of the packed storage
+// (after `mha.q = Linear(...)` or a swap with deserialised layers the three-node path runs on the new layers)
+bool MultiheadAttention::still_packed() const {
+    if (!wqkv_) return false;
+    const Linear* ls[3] = {&q, &k, &v};
+    const size_t dd = (size_t)d_model * d_model;
+    for (int i = 0; i < 3; ++i) {
+        if (ls[i]->weight.var.data->ptr() != wqkv_->ptr() + i * dd || ls[i]->bias.var.data->ptr() != bqkv_->ptr() + (size_t)i * d_model) return false;
+        if (ls[i]->weight.shape() != Shape{d_model, d_model} || ls[i]->bias.shape() != Shape{d_model}) return false;
+        if (!ls[i]->weight.grad->is_view_of(gwqkv_, i * dd) || !ls[i]->bias.grad->is_view_of(gbqkv_, (size_t)i * d_model)) return false;
+    }
+    return true;
+}
 VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
     const int rows = x.shape()[0], S = rows / batch, dh = d_model / heads;
     if (rows % batch != 0 || x.shape()[1] != d_model) panic("MultiheadAttention: bad input shape");
     const float scale = 1.f / std::sqrt((float)dh);
-    // q / k / v are public members: the packed path is only valid while they still ARE the views of the packed storage
-    // (after `mha.q = Linear(...)` or a swap with deserialised layers the three-node path below runs on the new layers)
-    auto still_packed = [&]() {
-        const Linear* ls[3] = {&q, &k, &v};
-        const size_t dd = (size_t)d_model * d_model;
-        for (int i = 0; i < 3; ++i) {
-            if (ls[i]->weight.var.data->ptr() != wqkv_->ptr() + i * dd || ls[i]->bias.var.data->ptr() != bqkv_->ptr() + (size_t)i * d_model) return false;
-            if (ls[i]->weight.shape() != Shape{d_model, d_model} || ls[i]->bias.shape() != Shape{d_model}) return false;
-            if (!ls[i]->weight.grad->is_view_of(gwqkv_, i * dd) || !ls[i]->bias.grad->is_view_of(gbqkv_, (size_t)i * d_model)) return false;
-        }
-        return true;
-    };
     // Causal, where the fused core does not apply: the composition spelled out - one Addition node (broadcast over B*H) of a
     // constant (S, S) leaf, 0 on and below the diagonal and -inf above, in front of the Softmax, whose -inf lanes come out exactly 0.
     // Uploaded once per graph build; the fused `attention_probs` node has no mask operand and is not used.
@@ -2817,6 +2854,97 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
                                                            : drop.forward((Q.bmm_t(K) * scale).softmax(2));
     const VarDiff O = P.bmm(V).merge_heads(batch, S, heads, dh);
     return o.forward(O);
+}
+
+
+KvCache::KvCache(DevicePtr dev, int batch_, int heads_, int head_dim_, int capacity_)
+    : batch(batch_), heads(heads_), head_dim(head_dim_), capacity(capacity_) {
+    if (batch <= 0 || heads <= 0 || head_dim <= 0 || capacity <= 0) panic("KvCache: batch, heads, head_dim and capacity must be positive");
+    if ((unsigned long long)batch * heads * capacity * head_dim > (unsigned long long)INT_MAX)
+        panic("KvCache: batch * heads * capacity * head_dim must fit 31 bits");
+    const Shape s{batch, heads, capacity, head_dim};
+    k = std::make_shared<HipArray>(dev, s, HipArray::Uninit{});
+    v = std::make_shared<HipArray>(dev, s, HipArray::Uninit{});
+    lens_.assign((size_t)batch, 0);
+    (void)workspace(1);
+}
+Shared<HipArray> KvCache::workspace(int T) {
+    if (T > ws_T_) {
+        const size_t n = nk_attention_decode_workspace(batch, T, heads, head_dim, capacity);
+        if (n == 0 || n > (size_t)INT_MAX) panic("KvCache: the decode workspace for " + std::to_string(T) + " rows per sample does not fit 31 bits");
+        ws_ = std::make_shared<HipArray>(k->device(), Shape{(int)n}, HipArray::Uninit{});
+        ws_T_ = T;
+    }
+    return ws_;
+}
+void KvCache::advance(int T) {
+    for (int& l : lens_) l += T;
+}
+void KvCache::reset() { lens_.assign((size_t)batch, 0); }
+void KvCache::truncate(const std::vector<int>& lens) {
+    if ((int)lens.size() != batch) panic("KvCache::truncate: " + std::to_string(lens.size()) + " lengths for a batch of " + std::to_string(batch));
+    for (int b = 0; b < batch; ++b)
+        if (lens[b] < 0 || lens[b] > lens_[b])
+            panic("KvCache::truncate: sample " + std::to_string(b) + " holds " + std::to_string(lens_[b]) + " positions, asked for " +
+                  std::to_string(lens[b]));
+    lens_ = lens;
+}
+
+Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) const {
+    if (!causal) panic("MultiheadAttention::forward_step is the incremental form of the CAUSAL forward: set causal = true");
+    if (*drop.status && drop.p > 0.0) panic("MultiheadAttention::forward_step runs in inference: dropout is active (p > 0 in train mode), call drop.eval() first");
+    if (x.shape().size() != 2 || batch <= 0 || x.shape()[0] % batch != 0 || x.shape()[0] == 0 || x.shape()[1] != d_model)
+        panic("MultiheadAttention::forward_step: bad input shape");
+    const int T = x.shape()[0] / batch, dh = d_model / heads;
+    if (cache.batch != batch || cache.heads != heads || cache.head_dim != dh)
+        panic("MultiheadAttention::forward_step: the cache was built for batch " + std::to_string(cache.batch) + ", " + std::to_string(cache.heads) +
+              " heads of " + std::to_string(cache.head_dim) + ", the step has batch " + std::to_string(batch) + ", " + std::to_string(heads) +
+              " heads of " + std::to_string(dh));
+    if (cache.k->device().get() != x.device().get()) panic("MultiheadAttention::forward_step: the cache lives on another device");
+    bool fresh = true;
+    for (int b = 0; b < batch; ++b) {
+        if (cache.lens()[b] + T > cache.capacity)
+            panic("MultiheadAttention::forward_step: sample " + std::to_string(b) + " holds " + std::to_string(cache.lens()[b]) + " positions, " +
+                  std::to_string(T) + " more exceed the cache's capacity of " + std::to_string(cache.capacity));
+        fresh = fresh && cache.lens()[b] == 0;
+    }
+    auto fw = std::make_shared<DecodeStepFwd>();
+    fw->B = batch; fw->T = T; fw->H = heads; fw->dh = dh; fw->cap = cache.capacity;
+    fw->x = x.data;
+    History<ForwardEntry> hf = x.history;
+    for (const Linear* l : {&q, &k, &v, &o}) { hf.merge(l->weight.var.history); hf.merge(l->bias.var.history); }
+    const int n = batch * T;
+    if (packed_qkv && still_packed()) {
+        fw->w[0] = wqkv_; fw->b[0] = bqkv_;
+        fw->qkv = zeros_like(x.data, Shape{n, 3 * d_model});
+    } else {
+        const Linear* ls[3] = {&q, &k, &v};
+        for (int i = 0; i < 3; ++i) {
+            if (ls[i]->weight.shape() != Shape{d_model, d_model} || ls[i]->bias.shape() != Shape{d_model})
+                panic("MultiheadAttention::forward_step: the projections must be (d_model, d_model) with a (d_model) bias");
+            fw->w[i] = ls[i]->weight.var.data; fw->b[i] = ls[i]->bias.var.data;
+        }
+        fw->q = zeros_like(x.data, Shape{n, d_model}); fw->k = zeros_like(x.data, Shape{n, d_model}); fw->v = zeros_like(x.data, Shape{n, d_model});
+    }
+    if (o.weight.shape() != Shape{d_model, d_model} || o.bias.shape() != Shape{d_model})
+        panic("MultiheadAttention::forward_step: the output projection must be (d_model, d_model) with a (d_model) bias");
+    fw->wo = o.weight.var.data; fw->bo = o.bias.var.data;
+    fw->ctx = zeros_like(x.data, Shape{n, d_model});
+    fw->out = zeros_like(x.data, Shape{n, d_model});
+    fw->kc = cache.k; fw->vc = cache.v;
+    fw->scale = 1.f / std::sqrt((float)dh);
+    // the core's own size guards (nk_attention.hip: mask words and projection elements below 2^31): past them the decode kernels
+    // take the prefill instead of a refused call
+    const long long tiles = (T + 31) / 32;
+    const bool core_fits = (long long)batch * heads * tiles * tiles < (1ll << 31) / 32 && (long long)n * 3 * d_model < (1ll << 31);
+    fw->core = fresh && T >= 2 && core_fits && nk_attention_supported(T, dh, 0.0, 0) != 0;
+    if (!fw->core) fw->ws = cache.workspace(T);
+    static_assert(sizeof(int) == sizeof(float), "the start positions travel in an f32 array");
+    fw->start = std::make_shared<HipArray>(x.device(), Shape{batch}, HipArray::Uninit{});
+    fw->start->upload(reinterpret_cast<const float*>(cache.lens().data()));
+    cache.advance(T);
+    auto y = fw->out;
+    return Var::node(y, fw, std::move(hf));
 }
 
 }  // namespace nn

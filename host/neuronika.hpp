@@ -811,6 +811,32 @@ struct Dropout {
     VarDiff forward(const VarDiff& x) const { return x.dropout(p, status); }
 };
 
+// The keys and values of one causal attention layer, kept on the device between the steps of incremental decoding (ours: the
+// reference has no such thing; semantics at nk_kv_cache_append / nk_attention_decode_fwd in neuronika_hip.h).  Kc, Vc are
+// (batch, heads, capacity, head_dim), head-major, allocated once and never initialised: nothing past a sample's length is read
+// into a result.  The lengths live on the host; `MultiheadAttention::forward_step` advances them when it BUILDS its node.
+//   reset()      every length back to 0 (the buffers are kept)
+//   truncate(l)  every sample to a length no longer than its current one.  This is what makes ragged prompts work - prefill a
+//                right-padded batch, then truncate each sample to its true prompt length: under the causal rule the padding never
+//                influenced the real positions - and it gives roll-back.
+struct KvCache {
+    KvCache(DevicePtr dev, int batch, int heads, int head_dim, int capacity);
+    int batch, heads, head_dim, capacity;
+    const std::vector<int>& lens() const { return lens_; }
+    void reset();
+    void truncate(const std::vector<int>& lens);
+    // used by forward_step: the buffers, the scratch of nk_attention_decode_fwd (sized for T = 1 at construction, regrown when a
+    // larger T first arrives; a node keeps the one it was built with alive), and the lengths after a step of T rows
+    Shared<HipArray> k, v;
+    Shared<HipArray> workspace(int T);
+    void advance(int T);
+
+   private:
+    std::vector<int> lens_;
+    Shared<HipArray> ws_;
+    int ws_T_ = 0;
+};
+
 // Multi-head attention composed from reference ops (the module does not exist in the reference;
 // SURVEY.md 8a note): Q,K,V = x.mm_t(W)+b; per (b,h): P = dropout(softmax(Q.mm_t(K)*dh^-1/2, 1));
 // O = P.mm(V); out = cat(O).mm_t(Wo)+bo.
@@ -836,8 +862,20 @@ struct MultiheadAttention {
     // four Linear layers built elsewhere (e.g. deserialised): their weights are NOT packed, `packed_qkv` is off
     MultiheadAttention(Linear q, Linear k, Linear v, Linear o, int heads, double p);
     VarDiff forward(const VarDiff& x, int batch) const;  // x: (batch*seq, d_model)
+    // Incremental decoding: the causal forward, one slice of T = rows / batch positions at a time, in inference.  x holds the NEW
+    // positions only, (batch*T, d_model); the result, (batch*T, d_model) without a gradient, equals rows lens[b] .. lens[b] + T - 1
+    // of `forward` over each sample's whole prefix up to summation order.  ONE forward node: projections (the packed single GEMM
+    // while the module is still packed), the append to `cache`, the attention, the output projection.  The node captures its
+    // start positions when it is built (one upload of `batch` int32) and the cache's lengths advance right then, so running its
+    // forward() again writes the same rows to the same places.  Attention part: every start 0, T >= 2 and a head size the fused
+    // core takes -> the causal core in its inference form (no (T, T) tensor); otherwise the split-KV decode kernels over
+    // (b, h, t), which also covers chunked prefill (T > 1 at start > 0).
+    // Panics: causal == false; dropout active (train mode and p > 0: call drop.eval() first); any lens[b] + T > capacity; a
+    // batch / heads / head size that differs from the cache's.
+    Var forward_step(const Var& x, int batch, KvCache& cache) const;
 
    private:
+    bool still_packed() const;
     Shared<HipArray> wqkv_, bqkv_, gwqkv_, gbqkv_;  // packed storage (null when the layers were handed in)
 };
 

@@ -462,9 +462,24 @@ PYBIND11_MODULE(_tape, m) {
         .def("train", &nn::Dropout::train)
         .def("eval", &nn::Dropout::eval)
         .def("forward", &nn::Dropout::forward);
+    py::class_<nn::KvCache>(nn, "KvCache")
+        .def(py::init<DevicePtr, int, int, int, int>(), py::arg("dev"), py::arg("batch"), py::arg("heads"), py::arg("head_dim"),
+             py::arg("capacity"),
+             "Keys and values of one causal attention layer on the device, (batch, heads, capacity, head_dim) each, for "
+             "MultiheadAttention.forward_step.")
+        .def_readonly("batch", &nn::KvCache::batch)
+        .def_readonly("heads", &nn::KvCache::heads)
+        .def_readonly("head_dim", &nn::KvCache::head_dim)
+        .def_readonly("capacity", &nn::KvCache::capacity)
+        .def("lens", [](const nn::KvCache& c) { return c.lens(); }, "positions held per sample")
+        .def("reset", &nn::KvCache::reset, "every length back to 0")
+        .def("truncate", &nn::KvCache::truncate, py::arg("lens"),
+             "Give every sample a length no longer than its current one: ragged prompts after a right-padded prefill, roll-back.");
     py::class_<nn::MultiheadAttention>(nn, "MultiheadAttention")
         .def(py::init<DevicePtr, int, int, double, uint64_t>(), py::arg("dev"), py::arg("d_model"), py::arg("heads"),
              py::arg("p") = 0.0, py::arg("seed") = 0)
+        .def(py::init<nn::Linear, nn::Linear, nn::Linear, nn::Linear, int, double>(), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+             py::arg("heads"), py::arg("p") = 0.0)  // four layers built elsewhere: not packed
         .def_readwrite("q", &nn::MultiheadAttention::q)   // public, assignable members in the C++ mirror as well
         .def_readwrite("k", &nn::MultiheadAttention::k)
         .def_readwrite("v", &nn::MultiheadAttention::v)
@@ -475,7 +490,15 @@ PYBIND11_MODULE(_tape, m) {
         .def_readwrite("fused_core", &nn::MultiheadAttention::fused_core)
         .def_readwrite("packed_qkv", &nn::MultiheadAttention::packed_qkv)
         .def_readwrite("causal", &nn::MultiheadAttention::causal)
-        .def("forward", &nn::MultiheadAttention::forward);
+        .def_readonly("d_model", &nn::MultiheadAttention::d_model)
+        .def_readonly("heads", &nn::MultiheadAttention::heads)
+        .def("forward", &nn::MultiheadAttention::forward)
+        .def("forward_step", &nn::MultiheadAttention::forward_step, py::arg("x"), py::arg("batch"), py::arg("cache"),
+             "Incremental decoding: x holds the new positions only, (batch*T, d_model); returns (batch*T, d_model) without a gradient. "
+             "The cache's lengths advance when the node is built. Needs causal = True and inactive dropout (drop.eval()).")
+        // a differentiable input (what the other layers return) enters through its data and forward tape; still no gradient out
+        .def("forward_step", [](const nn::MultiheadAttention& m, const VarDiff& x, int batch, nn::KvCache& cache) {
+                 return m.forward_step(x.var, batch, cache); }, py::arg("x"), py::arg("batch"), py::arg("cache"));
 
     py::module_ optim = m.def_submodule("optim");
     {

@@ -805,6 +805,39 @@ int nk_attention_qkv_causal_fwd(nk_device* dev, const float* QKV, float* scores,
 int nk_attention_qkv_causal_bwd(nk_device* dev, float* dQKV, float* dS, float* dropped, const float* dO, const float* O,
                                 const float* scores, const float* stats, const uint32_t* mask_bits, const float* QKV, int B, int S, int H,
                                 int dh, float scale, double p, int train, int assign);
+/* ------------------------------------------------------------------ incremental decoding --
+ * The causal forward above, one slice of T positions at a time, in inference (no dropout, nothing kept for a backward pass): each
+ * layer's keys and values stay on the device and the new rows attend to them.  For sample b, head h and the t-th new row
+ * (0 <= t < T), with n = start[b] + t + 1:
+ *   o = softmax(q . K_bh[0:n]^T * scale) . V_bh[0:n]
+ * where keys start[b] .. start[b] + T - 1 are the rows appended in the same step.  As a composition this is row start[b] + t of the
+ * chain documented at nk_attention_causal_fwd (MatrixMatrixMulT node/matrix_matrix_mul_t/mod.rs:31-41, Multiplication
+ * node/multiplication/mod.rs:39-50, Addition node/addition/mod.rs:39-50 with the causal constant, Softmax node/softmax/mod.rs:37-53,
+ * MatrixMatrixMul node/matrix_matrix_mul/mod.rs:31-41) over the sample's first n positions, dropout inactive.
+ * Cache layout: Kc, Vc are (B, H, cap, dh) f32, head-major - the keys of one (b, h) are one contiguous stream; cap = capacity in
+ * positions.  `start`: a DEVICE array of B int32, each sample's length before this step (per sample: ragged batches).
+ * nk_kv_cache_append: row b*T + t of K / V (row stride ld floats) goes to position start[b] + t of every head of sample b, head h
+ *   taking columns h*dh .. h*dh + dh - 1 of the row.  K = QKV + d, V = QKV + 2d, ld = 3d addresses a packed projection output
+ *   (d = H*dh); ld = d separate projections.  A bit-exact copy.  A row whose position would be >= cap (or < 0) is NOT written -
+ *   never out of bounds; nothing else of the cache is touched.
+ * nk_attention_decode_fwd: Q row b*T + t has stride ldq; O is (B*T, H*dh).  Query (b, t) reads keys < min(start[b] + t + 1, cap)
+ *   (none, for a negative start: the output row is 0).  Split-KV: a problem (b, h, t) is cut into chunks of
+ *   nk_attention_decode_chunk(dh) keys - a compile-time constant per head size (dh in {32, 64, 128}: 16-byte loads; any other dh:
+ *   a scalar kernel), never derived from the CU count, B, H, T, cap or nk_dev_tune.  A partial leaves (m, l, unnormalised o[dh])
+ *   in `workspace`, a second launch merges a problem's partials in chunk order in the exp2 form of the fused core.  No atomics, no
+ *   reductions in arrival order: the bits of o for (b, h, t) depend on that problem's q, its n keys / values and scale ONLY - not
+ *   on the other samples, B, H, T, cap, the run, or on what the cache holds at positions >= n, which is never read into the
+ *   result (uninitialised memory in real use; NaN there is harmless).
+ *   `workspace`: caller-owned scratch of nk_attention_decode_workspace(B, T, H, dh, cap) floats; the library allocates nothing in
+ *   this call, so it can sit in a captured region.
+ * NK_ERR_INVALID: non-positive B / T / H / dh / cap, scale <= 0 (or not finite), a null pointer, a row stride below H*dh, caches
+ * not 16-byte aligned for dh in {32, 64, 128}, more than 65535 chunks in cap, B*T*H >= 2^24 (one block per problem and chunk). */
+int nk_kv_cache_append(nk_device* dev, float* Kc, float* Vc, const float* K, const float* V, int ld, const int* start, int B, int T,
+                       int H, int dh, int cap);
+int nk_attention_decode_fwd(nk_device* dev, const float* Q, int ldq, const float* Kc, const float* Vc, const int* start, float* O,
+                            float* workspace, int B, int T, int H, int dh, int cap, float scale);
+size_t nk_attention_decode_workspace(int B, int T, int H, int dh, int cap);
+int nk_attention_decode_chunk(int dh);
 /* ------------------------------------------------------------------ dropout ------------ */
 /* Dropout::forward node/dropout/mod.rs:53-79.  train && 0<p<1: noise ~ Bernoulli(1-p) in
  * {0,1} is (re)drawn from Philox4x32-10(seed, offset) and written to `noise` (f32, like the

@@ -14,11 +14,11 @@
 //! NOT COMPILED in the authoring image (no rustc / cargo); `tests/test_rust_binding.py` checks it structurally (balanced
 //! delimiters, every `use` path names an item that exists, every layer calls variable methods that exist with their
 //! arity).  The tested host mirror of the same layers is `host/neuronika.hpp` (`nn::*`) in this repository.
-use std::{cell::Cell, rc::Rc};
+use std::{cell::{Cell, RefCell}, rc::Rc};
 
 use ndarray::{Array, Dimension, Ix0, Ix1, Ix2, Ix3, Ix4, Ix5, RemoveAxis};
 use neuronika_variable::{
-    hip::{Device, Gate, HipVar, HipVarDiff, PaddingMode},
+    hip::{Device, Gate, HipVar, HipVarDiff, KvBuffers, PaddingMode},
     Reduction,
 };
 use rand::distributions::{Distribution, Uniform};
@@ -415,6 +415,47 @@ conv_layer!(Conv3d, GroupedConv3d, Ix5, Ix4, (usize, usize, usize),
             |o, i, k: (usize, usize, usize)| ndarray::Dim([o, i, k.0, k.1, k.2]), |o| ndarray::Dim([o, 1, 1, 1]),
             |k: (usize, usize, usize)| k.0 * k.1 * k.2, |v: (usize, usize, usize)| [v.0, v.1, v.2]);
 
+/// The keys and values of one causal attention layer between the steps of incremental decoding (ours; the tested mirror is
+/// `nn::KvCache` in `host/neuronika.hpp`): device buffers `(batch, heads, capacity, head_dim)` and the per-sample lengths on the
+/// host.  `MultiheadAttention::forward_step` advances the lengths when it builds its node.
+pub struct KvCache {
+    pub buffers: KvBuffers,
+    lens: RefCell<Vec<usize>>,
+}
+
+impl KvCache {
+    pub fn new(batch: usize, heads: usize, head_dim: usize, capacity: usize, device: &Device) -> Self {
+        Self { buffers: KvBuffers::new(batch, heads, head_dim, capacity, device), lens: RefCell::new(vec![0; batch]) }
+    }
+
+    pub fn capacity(&self) -> usize {
+        self.buffers.geometry().2
+    }
+
+    /// Positions held per sample.
+    pub fn lens(&self) -> Vec<usize> {
+        self.lens.borrow().clone()
+    }
+
+    /// Every length back to 0; the buffers are kept.
+    pub fn reset(&self) {
+        self.lens.borrow_mut().iter_mut().for_each(|l| *l = 0);
+    }
+
+    /// Every sample to a length no longer than its current one: ragged prompts after a right-padded prefill (under the causal
+    /// rule the padding never influenced the real positions), and roll-back.
+    pub fn truncate(&self, lens: &[usize]) {
+        let mut mine = self.lens.borrow_mut();
+        assert!(lens.len() == mine.len(), "KvCache::truncate: one length per sample");
+        assert!(lens.iter().zip(mine.iter()).all(|(new, old)| new <= old), "KvCache::truncate: a sample cannot grow");
+        mine.copy_from_slice(lens);
+    }
+
+    fn advance(&self, rows: usize) {
+        self.lens.borrow_mut().iter_mut().for_each(|l| *l += rows);
+    }
+}
+
 /// Multi-head self-attention composed from reference operations (module named by `src/lib.rs:783-797`; SURVEY.md 8a note):
 /// `Q, K, V = x.mm_t(W) + b`; per (sample, head): `P = dropout(softmax(Q K^T / sqrt(dh)))`, `O = P V`; `out = O.mm_t(Wo) + bo`.
 /// Input rows are `(batch * seq, d_model)`.
@@ -472,5 +513,29 @@ impl MultiheadAttention {
             packed.packed_heads_attention(batch, seq, self.heads, dh, scale, self.dropout.p, self.dropout.status.clone())
         };
         self.o.forward(context)
+    }
+
+    /// Incremental decoding: the causal forward one slice of positions at a time, in inference.  `input` holds the NEW positions
+    /// only, `(batch * rows, d_model)`; the packed projection, the append to `cache`, the single-query attention over the cached
+    /// keys and the output projection run without keeping anything for a backward pass.  The cache's lengths advance here, when
+    /// the graph is built.  Panics unless `causal` is set and dropout is inactive, or when the step exceeds the capacity.
+    /// Unlike the C++ mirror (`host/neuronika.cpp`), which sends a fresh prefill of two or more rows through the causal core in
+    /// its inference form, this method ALWAYS runs the append and the decode kernels, prefill included: the same values up to
+    /// summation order, one kernel per (sample, head, row) instead of the tiled core.
+    pub fn forward_step(&self, input: HipVar<Ix2>, batch: usize, cache: &KvCache) -> HipVar<Ix2> {
+        assert!(self.causal, "MultiheadAttention::forward_step is the incremental form of the causal forward");
+        assert!(!self.dropout.status.get() || self.dropout.p == 0., "MultiheadAttention::forward_step: dropout is active, call eval() first");
+        let rows = input.shape()[0];
+        assert!(batch > 0 && rows > 0 && rows % batch == 0, "MultiheadAttention: rows must be a multiple of batch");
+        let dh = self.d_model / self.heads;
+        let (cb, ch, capacity, cd) = cache.buffers.geometry();
+        assert!((cb, ch, cd) == (batch, self.heads, dh), "MultiheadAttention::forward_step: the cache was built for another geometry");
+        let start = cache.lens();
+        assert!(start.iter().all(|&l| l + rows / batch <= capacity), "MultiheadAttention::forward_step: the step exceeds the capacity");
+        let scale = 1. / (dh as f32).sqrt();
+        let packed = input.linear(self.qkv.weight.detached(), self.qkv.bias.detached(), false);
+        let context = packed.packed_decode_attention(&cache.buffers, &start, scale);
+        cache.advance(rows / batch);
+        context.linear(self.o.weight.detached(), self.o.bias.detached(), false)
     }
 }

@@ -8,7 +8,7 @@ use std::{
     rc::Rc,
 };
 
-use ndarray::{Axis, DimMax, Dimension, IntoDimension, Ix0, Ix1, Ix2, Ix3, RemoveAxis};
+use ndarray::{Axis, DimMax, Dimension, IntoDimension, Ix0, Ix1, Ix2, Ix3, Ix4, RemoveAxis};
 
 use super::{
     device::Device,
@@ -23,6 +23,7 @@ use super::{
         AvgPool, AvgPoolBackward, MaxPool, MaxPoolBackward,
         DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
+        decode_chunk, decode_workspace, PackedDecodeAttention,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
         ReLUBackward, ReluMask, Softmax, SoftmaxBackward,
         SquaredError, SquaredErrorBackward, Sum, SumBackward, Transpose, TransposeBackward,
@@ -527,6 +528,70 @@ impl HipVar<Ix2> {
     }
 }
 
+/// Device storage of one causal attention layer's keys and values for incremental decoding (ours; layout in
+/// `include/neuronika_hip.h`): `(batch, heads, capacity, dh)` each, head-major, plus the scratch of the split-KV kernels, sized
+/// for one new row per sample and regrown when a longer slice first arrives.  The lengths are the caller's
+/// (`neuronika_nn::hip::KvCache`).
+pub struct KvBuffers {
+    pub(crate) keys: Shared<HipArray<Ix4>>,
+    pub(crate) values: Shared<HipArray<Ix4>>,
+    workspace: RefCell<Shared<HipArray<Ix1>>>,
+    workspace_rows: Cell<usize>,
+    geometry: (usize, usize, usize, usize), // batch, heads, capacity, dh
+}
+
+impl KvBuffers {
+    pub fn new(batch: usize, heads: usize, dh: usize, capacity: usize, device: &Device) -> Self {
+        assert!(batch > 0 && heads > 0 && dh > 0 && capacity > 0, "KvBuffers: batch, heads, dh and capacity must be positive");
+        let dim = ndarray::Dim([batch, heads, capacity, dh]);
+        Self { keys: shared(dim, device), values: shared(dim, device),
+               workspace: RefCell::new(shared(ndarray::Dim([decode_workspace(batch, 1, heads, dh, capacity)]), device)),
+               workspace_rows: Cell::new(1), geometry: (batch, heads, capacity, dh) }
+    }
+
+    /// `(batch, heads, capacity, dh)`
+    pub fn geometry(&self) -> (usize, usize, usize, usize) {
+        self.geometry
+    }
+
+    /// Keys per partial problem at this head size: where a length crosses into the next chunk.
+    pub fn chunk(&self) -> usize {
+        decode_chunk(self.geometry.3)
+    }
+
+    fn workspace_for(&self, rows: usize, device: &Device) -> Shared<HipArray<Ix1>> {
+        if rows > self.workspace_rows.get() {
+            let (batch, heads, capacity, dh) = self.geometry;
+            *self.workspace.borrow_mut() = shared(ndarray::Dim([decode_workspace(batch, rows, heads, dh, capacity)]), device);
+            self.workspace_rows.set(rows);
+        }
+        self.workspace.borrow().clone()
+    }
+}
+
+impl HipVar<Ix2> {
+    /// One step of incremental decoding: `self` is the `(batch*rows, 3*heads*dh)` packed projection of the NEW positions; its key
+    /// and value blocks are appended to `buffers` at `start[b] + t` and every new row attends to the keys `< start[b] + t + 1` of
+    /// its sample (`nk_kv_cache_append`, `nk_attention_decode_fwd`).  `start`: each sample's length before the step, captured
+    /// here.  Output `(batch*rows, heads*dh)`, no gradient.
+    pub fn packed_decode_attention(self, buffers: &KvBuffers, start: &[usize], scale: f32) -> HipVar<Ix2> {
+        let device = self.device();
+        let (batch, heads, capacity, dh) = buffers.geometry();
+        let total = self.data.borrow().dimension()[0];
+        assert!(start.len() == batch && total % batch == 0 && total > 0, "packed_decode_attention: rows must be a positive multiple of the batch");
+        assert!(self.data.borrow().dimension()[1] == 3 * heads * dh, "packed_decode_attention: the input must be (rows, 3 * heads * dh)");
+        let rows = total / batch;
+        assert!(start.iter().all(|&s| s + rows <= capacity), "packed_decode_attention: the step exceeds the capacity of the cache");
+        let cells: Vec<f32> = start.iter().map(|&s| f32::from_bits(s as u32)).collect();
+        let start = HipArray::from_slice(&cells, ndarray::Dim([batch]), device.clone());
+        let geometry = Heads { batch: batch as i32, seq: rows as i32, heads: heads as i32, dh: dh as i32 };
+        let data = shared(ndarray::Dim([total, heads * dh]), &device);
+        let op = PackedDecodeAttention::new(geometry, capacity as i32, self.data, buffers.keys.clone(), buffers.values.clone(), start,
+                                            buffers.workspace_for(rows, &device), data.clone(), scale);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+}
+
 impl HipVar<Ix2> {
     /// `Var::mm_t(VarDiff)` (`var.rs:1081-1094`): only the right operand is differentiable, so only
     /// `MatrixMatrixMulTBackwardRight` goes on the tape - the input layer of C4, whose input-gradient GEMM the reference never
@@ -596,6 +661,12 @@ where
     pub(crate) fn node(var: HipVar<D>, grad: Rc<Gradient<HipArray<D>, D>>, op: (Rc<dyn Backward>, Rc<dyn NoGrad>), mut history: Bwd) -> Self {
         history.insert(Rc::as_ptr(&op.0) as *const () as usize, op);
         Self { var, grad, history, relu_mask: None }
+    }
+
+    /// The variable without its gradient: the same data and forward tape (inference paths such as
+    /// `nn::MultiheadAttention::forward_step` run a parameter through nodes that keep nothing for a backward pass).
+    pub fn detached(&self) -> HipVar<D> {
+        self.var.clone()
     }
 
     fn new_grad<E: Dimension>(&self, dim: E) -> Rc<Gradient<HipArray<E>, E>> {

@@ -12,7 +12,7 @@ pub use {
     device::Device,
     dp::{Communicator, GradientSync, SyncEntry},
     hiparray::HipArray,
-    hipvar::{manual_seed, Gate, HipVar, HipVarDiff, PaddingMode},
+    hipvar::{manual_seed, Gate, HipVar, HipVarDiff, KvBuffers, PaddingMode},
     optimizer::AdamW,
     optimizer::SGD,
 };

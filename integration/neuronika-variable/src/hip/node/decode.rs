@@ -1,0 +1,66 @@
+use ndarray::{Ix1, Ix2, Ix4};
+
+use super::attention::Heads;
+use crate::{
+    autograd::Forward,
+    hip::{ffi, hiparray::HipArray},
+    utils::Shared,
+};
+
+/// Keys one partial problem of the split-KV decode kernel covers (`nk_attention_decode_chunk`): a constant of the library per
+/// head size, never a function of the device or the batch.
+pub(crate) fn decode_chunk(dh: usize) -> usize {
+    (unsafe { ffi::nk_attention_decode_chunk(dh as i32) }) as usize
+}
+
+/// Floats of scratch `nk_attention_decode_fwd` needs for `rows` new positions per sample (`nk_attention_decode_workspace`).
+pub(crate) fn decode_workspace(batch: usize, rows: usize, heads: usize, dh: usize, capacity: usize) -> usize {
+    unsafe { ffi::nk_attention_decode_workspace(batch as i32, rows as i32, heads as i32, dh as i32, capacity as i32) }
+}
+
+/// One step of incremental decoding over PACKED projections (ours: the reference has no such node; semantics in
+/// `include/neuronika_hip.h`): `packed` is the `(batch*rows, 3*heads*dh)` output of one `Linear` over `[Wq; Wk; Wv]` for the NEW
+/// positions only.  The forward appends its key and value blocks to the `(batch, heads, capacity, dh)` caches at
+/// `start[b] + t` (`nk_kv_cache_append`) and lets every new row attend to the keys `< start[b] + t + 1` of its sample
+/// (`nk_attention_decode_fwd`: split-KV partials merged in chunk order, no atomics).  `start` is fixed when the node is built,
+/// so a second `forward()` writes the same rows to the same places.  Inference only: there is no backward node.
+pub(crate) struct PackedDecodeAttention {
+    geometry: Heads, // `seq` = new rows per sample
+    capacity: i32,
+    packed: Shared<HipArray<Ix2>>,
+    keys: Shared<HipArray<Ix4>>,
+    values: Shared<HipArray<Ix4>>,
+    start: HipArray<Ix1>, // `batch` int32 lengths in f32 cells
+    workspace: Shared<HipArray<Ix1>>,
+    data: Shared<HipArray<Ix2>>,
+    scale: f32,
+}
+
+impl PackedDecodeAttention {
+    #[allow(clippy::too_many_arguments)]
+    pub(crate) fn new(geometry: Heads, capacity: i32, packed: Shared<HipArray<Ix2>>, keys: Shared<HipArray<Ix4>>, values: Shared<HipArray<Ix4>>,
+                      start: HipArray<Ix1>, workspace: Shared<HipArray<Ix1>>, data: Shared<HipArray<Ix2>>, scale: f32) -> Self {
+        Self { geometry, capacity, packed, keys, values, start, workspace, data, scale }
+    }
+}
+
+impl Forward for PackedDecodeAttention {
+    fn forward(&self) {
+        let qkv = self.packed.borrow();
+        let (mut kc, mut vc) = (self.keys.borrow_mut(), self.values.borrow_mut());
+        let mut ws = self.workspace.borrow_mut();
+        let mut out = self.data.borrow_mut();
+        let h = self.geometry;
+        let d = (h.heads * h.dh) as usize;
+        let start = self.start.as_ptr() as *const i32;
+        let dev = qkv.device().as_raw();
+        ffi::check(unsafe {
+            ffi::nk_kv_cache_append(dev, kc.as_mut_ptr(), vc.as_mut_ptr(), qkv.as_ptr().add(d), qkv.as_ptr().add(2 * d), 3 * d as i32, start,
+                                    h.batch, h.seq, h.heads, h.dh, self.capacity)
+        });
+        ffi::check(unsafe {
+            ffi::nk_attention_decode_fwd(dev, qkv.as_ptr(), 3 * d as i32, kc.as_ptr(), vc.as_ptr(), start, out.as_mut_ptr(), ws.as_mut_ptr(),
+                                         h.batch, h.seq, h.heads, h.dh, self.capacity, self.scale)
+        });
+    }
+}

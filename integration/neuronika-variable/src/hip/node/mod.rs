@@ -9,6 +9,7 @@ mod attention;
 mod binary_op;
 mod convolution;
 mod cross_entropy;
+mod decode;
 mod embedding;
 mod layout;
 mod linear;
@@ -25,6 +26,7 @@ pub(crate) use attention::*;
 pub(crate) use binary_op::*;
 pub(crate) use convolution::*;
 pub(crate) use cross_entropy::*;
+pub(crate) use decode::*;
 pub(crate) use embedding::*;
 pub(crate) use layout::*;
 pub(crate) use linear::*;

@@ -203,6 +203,10 @@ _SIGS = {
                          C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_attention_qkv_causal_fwd": [VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_attention_qkv_causal_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_int],
+    "nk_kv_cache_append": [VP, VP, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_attention_decode_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float],
+    "nk_attention_decode_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_attention_decode_chunk": [C.c_int],
     "nk_scale_softmax_dropout_fwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_scale_softmax_dropout_bwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_dropout_fwd": [VP, VP, VP, VP, C.c_size_t, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
@@ -239,7 +243,8 @@ _SIGS = {
     "nk_comm_rank": [VP],
     "nk_comm_size": [VP],
 }
-_RESTYPES = {"nk_last_error": C.c_char_p, "nk_version": C.c_char_p, "nk_stream_compute": VP, "nk_stream_comm": VP}
+_RESTYPES = {"nk_last_error": C.c_char_p, "nk_version": C.c_char_p, "nk_stream_compute": VP, "nk_stream_comm": VP,
+             "nk_attention_decode_workspace": C.c_size_t}
 EXPORTED = tuple(_SIGS)
 
 for _name, _args in _SIGS.items():
@@ -948,6 +953,28 @@ def attention_fwd(dev, Q, K, V, scores, stats, mask_bits, out, B, S, H, dh, scal
     check((lib.nk_attention_causal_fwd if causal else lib.nk_attention_fwd)(dev.h, Q.p, K.p, V.p, scores.p if scores is not None else None, stats.p if stats is not None else None,
                                mask_bits.p if mask_bits is not None else None, out.p,
                                B, S, H, dh, scale, float(p), int(train), seed, offset))
+
+
+def attention_decode_chunk(dh) -> int:
+    """Keys one partial problem of the split-KV decode kernel covers: a constant of the library per head size."""
+    return int(lib.nk_attention_decode_chunk(int(dh)))
+
+
+def attention_decode_workspace(B, T, H, dh, cap) -> int:
+    """Floats of caller-owned scratch nk_attention_decode_fwd needs for this geometry."""
+    return int(lib.nk_attention_decode_workspace(B, T, H, dh, cap))
+
+
+def kv_cache_append(dev, Kc, Vc, K, V, ld, start, B, T, H, dh, cap):
+    """Row b*T + t of K / V (row stride ld floats; `view_offset` addresses the column blocks of a packed projection output) ->
+    position start[b] + t of every head of sample b in the (B, H, cap, dh) caches.  start: int32 device array of B lengths."""
+    check(lib.nk_kv_cache_append(dev.h, _p(Kc), _p(Vc), _p(K), _p(V), ld, _p(start), B, T, H, dh, cap))
+
+
+def attention_decode_fwd(dev, Q, ldq, Kc, Vc, start, out, workspace, B, T, H, dh, cap, scale):
+    """Single-query attention over the caches: query (b, t) reads keys < min(start[b] + t + 1, cap); out is (B*T, H*dh);
+    workspace: `attention_decode_workspace(B, T, H, dh, cap)` floats."""
+    check(lib.nk_attention_decode_fwd(dev.h, _p(Q), ldq, _p(Kc), _p(Vc), _p(start), _p(out), _p(workspace), B, T, H, dh, cap, scale))
 
 
 def attention_bwd(dev, dQ, dK, dV, dS, dropped, dO, out, scores, stats, mask_bits, Q, K, V, B, S, H, dh, scale, p, train=True,

@@ -12,6 +12,7 @@
 #include "nk_cross_entropy.h"
 #include "nk_activation.h"
 #include "nk_optim_multi.h"
+#include "nk_attention_decode.h"
 
 namespace {
 
