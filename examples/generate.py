@@ -5,6 +5,7 @@ new token runs through the layers alone and attends to the keys and values each 
 K and V per token instead of the causal forward over the whole prefix.
 
     python examples/generate.py [new_tokens]      # needs an MI355X; prints the prompt and the generated ids
+    python examples/generate.py [new_tokens] --rope   # rotary positions: no position table, one shared RotaryEmbedding on every block
 
 The weights are random (fixed seeds): the text means nothing, the mechanics are the point.  The last lines compare every step's
 logits with those of the full causal forward over the same prefix."""
@@ -20,11 +21,12 @@ VOCAB, D_MODEL, HEADS, LAYERS, CONTEXT = 64, 64, 2, 2, 64
 
 
 class Block:
-    def __init__(self, nk, dev, seed):
+    def __init__(self, nk, dev, seed, rope=None):
         self.ln1, self.ln2 = nk.nn.LayerNorm(dev, [D_MODEL]), nk.nn.LayerNorm(dev, [D_MODEL])
         self.mha = nk.nn.MultiheadAttention(dev, D_MODEL, HEADS, 0.0, seed)
         self.mha.causal = True
         self.mha.drop.eval()
+        self.mha.rope = rope                                             # None: the learned position table below carries the positions
         self.up, self.down = nk.nn.Linear(dev, D_MODEL, 4 * D_MODEL, seed + 20), nk.nn.Linear(dev, 4 * D_MODEL, D_MODEL, seed + 22)
         self.act = nk.nn.GELU()
 
@@ -41,10 +43,13 @@ class Block:
 
 
 class Decoder:
-    def __init__(self, nk, dev):
+    def __init__(self, nk, dev, rope=False):
         self.nk, self.dev = nk, dev
         self.tok, self.pos = nk.nn.Embedding(dev, VOCAB, D_MODEL, seed=1), nk.nn.Embedding(dev, CONTEXT, D_MODEL, seed=2)
-        self.blocks = [Block(nk, dev, 100 * (i + 1)) for i in range(LAYERS)]
+        # rotary mode: the queries and keys of every layer are rotated by their position (at lens[b] + t in a step, so the caches
+        # hold rotated keys) and nothing is added to the token embedding
+        self.rope = nk.nn.RotaryEmbedding(dev, D_MODEL // HEADS, CONTEXT) if rope else None
+        self.blocks = [Block(nk, dev, 100 * (i + 1), self.rope) for i in range(LAYERS)]
         self.ln, self.head = nk.nn.LayerNorm(dev, [D_MODEL]), nk.nn.Linear(dev, D_MODEL, VOCAB, 7)
 
     def embed(self, ids, first):
@@ -52,6 +57,8 @@ class Decoder:
         batch, T = ids.shape
         where = np.tile(np.arange(first, first + T, dtype=np.float32), batch)
         up = lambda a: self.nk.from_ndarray(self.dev, np.ascontiguousarray(a, dtype=np.float32).reshape(-1))
+        if self.rope is not None:
+            return self.tok.forward(up(ids))
         return self.tok.forward(up(ids)) + self.pos.forward(up(where))
 
     def logits_step(self, ids, first, caches):
@@ -71,11 +78,11 @@ class Decoder:
         return out.data().reshape(ids.shape[0], ids.shape[1], VOCAB)
 
 
-def main(new_tokens=16):
+def main(new_tokens=16, rope=False):
     import neuronika_amd
     nk = neuronika_amd.tape
     dev = nk.Device(0)
-    model = Decoder(nk, dev)
+    model = Decoder(nk, dev, rope)
     prompt = np.array([[3, 14, 15, 9, 26, 5, 35, 8]])
     batch, n = prompt.shape
     assert n + new_tokens <= CONTEXT
@@ -95,4 +102,5 @@ def main(new_tokens=16):
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 16)
+    args = [a for a in sys.argv[1:] if a != "--rope"]
+    main(int(args[0]) if args else 16, rope="--rope" in sys.argv[1:])

@@ -812,6 +812,21 @@ struct HeadsAttentionBwd : Backward {
     }
 };
 
+// The geometry of one rotary launch (nk_rope_*), shared by the rope node and the attention nodes that rotate Q and K in place.
+struct RopeGeom {
+    int B = 0, T = 0, NH = 0, dh = 0, rot = 0, max_pos = 0, interleaved = 0;
+};
+static RopeGeom rope_geom(const nn::RotaryEmbedding& r, int B, int T, int NH) {
+    RopeGeom g;
+    g.B = B; g.T = T; g.NH = NH; g.dh = r.head_dim; g.rot = r.rot; g.max_pos = r.max_pos; g.interleaved = r.interleaved ? 1 : 0;
+    return g;
+}
+// in place over `NH` heads from column 0 of a buffer with row stride ld; start: device int32[B] or null
+static void rope_inplace(nk_device* dev, float* x, int ld, const Shared<HipArray>& table, const int* start, const RopeGeom& g, bool inverse) {
+    if (inverse) check(nk_rope_bwd_assign(dev, x, ld, x, ld, table->ptr(), start, g.B, g.T, g.NH, g.dh, g.rot, g.max_pos, g.interleaved));
+    else check(nk_rope_fwd(dev, x, ld, x, ld, table->ptr(), start, g.B, g.T, g.NH, g.dh, g.rot, g.max_pos, g.interleaved));
+}
+
 // nn::MultiheadAttention with PACKED projections: x -> [Q | K | V] = x . [Wq; Wk; Wv]^T + [bq; bk; bv] (ONE GEMM, N = 3d) -> the
 // fused attention core reading Q, K, V as column blocks of that output -> context.  One forward and one backward node for what
 // the unpacked module runs as three Linear nodes + the attention node (same values bit for bit in the forward; the backward's
@@ -825,9 +840,12 @@ struct QkvAttentionFwd : Forward {
     uint64_t seed;
     Shared<uint64_t> calls;
     bool causal = false;
+    Shared<HipArray> rope;  // the rotary table or null; rg: 2 H heads over the Q|K blocks
+    RopeGeom rg;
     void forward() const override {
         const int n = hg.B * hg.S, d = hg.d();
         check(nk_linear_fwd(D(x), x->ptr(), w->ptr(), b->ptr(), qkv->ptr(), n, d, 3 * d));
+        if (rope) rope_inplace(D(x), qkv->ptr(), 3 * d, rope, nullptr, rg, false);
         const uint64_t sp = ((uint64_t)hg.S + 31) / 32 * 32;
         const uint64_t offset = (*calls) * (((uint64_t)hg.B * hg.H * sp * sp + 7) / 8);
         check((causal ? nk_attention_qkv_causal_fwd : nk_attention_qkv_fwd)(D(x), qkv->ptr(), scores ? scores->ptr() : nullptr, stats ? stats->ptr() : nullptr,
@@ -846,6 +864,8 @@ struct QkvAttentionBwd : Backward {
     double p;
     Shared<bool> status;
     bool causal = false;
+    Shared<HipArray> rope;  // as in the forward node: [dQ | dK] of the rotated rows go back through R^T in place
+    RopeGeom rg;
     // the three views are written by ONE kernel: it may assign only when all three still wait for their zero fill
     static float packed_beta(const Shared<Gradient> (&v)[3]) {
         bool all = true;
@@ -864,6 +884,7 @@ struct QkvAttentionBwd : Backward {
         check((causal ? nk_attention_qkv_causal_bwd : nk_attention_qkv_bwd)(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
                                    reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
                                    *status ? 1 : 0, 1));
+        if (rope) rope_inplace(dev, dqkv->ptr(), 3 * d, rope, nullptr, rg, true);
         float beta;
         if (dx) {  // dX (+)= [dQ | dK | dV] . [Wq; Wk; Wv]: one NN product, K = 3d
             float* q = first_write(dx, beta);
@@ -895,6 +916,8 @@ struct DecodeStepFwd : Forward {
     Shared<HipArray> kc, vc, ws, start;
     float scale;
     bool core = false;  // every start 0, T >= 2, head size of the fused core
+    Shared<HipArray> rope;  // the rotary table or null: the new Q and K rows are rotated at start[b] + t before the append
+    RopeGeom rg;            // NH = 2 H when packed (Q|K in one launch), H otherwise (two launches)
     void forward() const override {
         nk_device* dev = D(x);
         const int n = B * T, d = H * dh;
@@ -909,6 +932,10 @@ struct DecodeStepFwd : Forward {
             Q = q->ptr(); K = k->ptr(); V = v->ptr(); ld = d;
         }
         const int* st = reinterpret_cast<const int*>(start->ptr());
+        if (rope) {
+            rope_inplace(dev, const_cast<float*>(Q), ld, rope, st, rg, false);
+            if (!qkv) rope_inplace(dev, const_cast<float*>(K), ld, rope, st, rg, false);
+        }
         check(nk_kv_cache_append(dev, kc->ptr(), vc->ptr(), K, V, ld, st, B, T, H, dh, cap));
         if (core && qkv)
             check(nk_attention_qkv_causal_fwd(dev, qkv->ptr(), nullptr, nullptr, nullptr, ctx->ptr(), B, T, H, dh, scale, 0.0, 0, 0, 0));
@@ -966,6 +993,32 @@ struct ActivationBwd : Backward {
         HipArray& d = dx->borrow_first_write(assign);
         if (H == 0) check((assign ? nk_activation_bwd_assign : nk_activation_bwd)(D(x), act, d.ptr(), G.ptr(), x->ptr(), d.len()));
         else check((assign ? nk_glu_bwd_assign : nk_glu_bwd)(D(x), act, d.ptr(), G.ptr(), x->ptr(), (long long)(G.len() / (size_t)H), H));
+    }
+    void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
+};
+
+// Rotary position embedding (ours; the reference has no such node; semantics in neuronika_hip.h) of a (B*T, NH*dh) value at positions
+// 0 .. T-1.  The rotation is orthogonal: the backward is the same kernel with the sign of the sine flipped and holds the table and
+// the geometry, nothing of the input.  The first writer of the input's gradient takes the assign form.
+struct RopeFwd : Forward {
+    RopeGeom rg;
+    Shared<HipArray> x, y, table;
+    void forward() const override {
+        const int ld = rg.NH * rg.dh;
+        check(nk_rope_fwd(D(x), x->ptr(), ld, y->ptr(), ld, table->ptr(), nullptr, rg.B, rg.T, rg.NH, rg.dh, rg.rot, rg.max_pos, rg.interleaved));
+    }
+};
+struct RopeBwd : Backward {
+    RopeGeom rg;
+    Shared<HipArray> table;
+    Shared<Gradient> dx, g;
+    void backward() const override {
+        const HipArray& G = g->borrow();
+        bool assign = false;
+        HipArray& d = dx->borrow_first_write(assign);
+        const int ld = rg.NH * rg.dh;
+        check((assign ? nk_rope_bwd_assign : nk_rope_bwd)(D(table), d.ptr(), ld, G.ptr(), ld, table->ptr(), nullptr, rg.B, rg.T, rg.NH, rg.dh, rg.rot,
+                                                          rg.max_pos, rg.interleaved));
     }
     void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
 };
@@ -1620,6 +1673,23 @@ static VarDiff activation_diff(const VarDiff& x, Activation act, bool gated) {
 Var Var::gelu(bool tanh_approx) const { return activation_var(*this, tanh_approx ? Activation::GeluTanh : Activation::Gelu, false); }
 Var Var::silu() const { return activation_var(*this, Activation::Silu, false); }
 Var Var::glu(Activation gate) const { return activation_var(*this, gate, true); }
+static Shared<RopeFwd> rope_fwd_node(const Var& x, const nn::RotaryEmbedding& r, int batch, int heads) {
+    const Shape& s = x.shape();
+    if (s.size() != 2 || batch <= 0 || heads <= 0 || s[0] == 0 || s[0] % batch != 0 || s[1] != heads * r.head_dim)
+        panic("rope: the input must be (batch*T, heads*head_dim) with head_dim = " + std::to_string(r.head_dim));
+    if (s[0] / batch > r.max_pos)
+        panic("rope: " + std::to_string(s[0] / batch) + " positions exceed the table's " + std::to_string(r.max_pos));
+    if (r.table->device().get() != x.device().get()) panic("rope: the table lives on another device");
+    auto n = std::make_shared<RopeFwd>();
+    n->rg = rope_geom(r, batch, s[0] / batch, heads);
+    n->x = x.data; n->table = r.table; n->y = zeros_like(x.data, s);
+    return n;
+}
+Var Var::rope(const nn::RotaryEmbedding& rotary, int batch, int heads) const {
+    auto n = rope_fwd_node(*this, rotary, batch, heads);
+    auto y = n->y;
+    return Var::node(y, n, history);
+}
 Var Var::neg() const { return pointwise_var(NK_NEG, 0, *this); }
 Var Var::pow(int e) const { return pointwise_var(NK_POW, e, *this); }
 Var Var::sqrt() const { return pointwise_var(NK_SQRT, 0, *this); }
@@ -2098,6 +2168,15 @@ VarDiff VarDiff::sigmoid() const { return pointwise_diff(NK_SIGMOID, 0, *this); 
 VarDiff VarDiff::gelu(bool tanh_approx) const { return activation_diff(*this, tanh_approx ? Activation::GeluTanh : Activation::Gelu, false); }
 VarDiff VarDiff::silu() const { return activation_diff(*this, Activation::Silu, false); }
 VarDiff VarDiff::glu(Activation gate) const { return activation_diff(*this, gate, true); }
+VarDiff VarDiff::rope(const nn::RotaryEmbedding& rotary, int batch, int heads) const {
+    auto n = rope_fwd_node(var, rotary, batch, heads);
+    auto y = n->y;
+    Var v = Var::node(y, n, var.history);
+    auto g = std::make_shared<Gradient>(v.device(), v.shape());
+    auto bw = std::make_shared<RopeBwd>();
+    bw->rg = n->rg; bw->table = n->table; bw->dx = grad; bw->g = g;
+    return VarDiff::node(std::move(v), g, entry(bw, g), history);
+}
 VarDiff VarDiff::tanh() const { return pointwise_diff(NK_TANH, 0, *this); }
 VarDiff VarDiff::ln() const { return pointwise_diff(NK_LN, 0, *this); }
 VarDiff VarDiff::exp() const { return pointwise_diff(NK_EXP, 0, *this); }
@@ -2791,6 +2870,7 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     fw->scale = scale; fw->p = m.drop.p; fw->status = m.drop.status; fw->causal = m.causal;
     fw->seed = next_node_seed();
     fw->calls = std::make_shared<uint64_t>(0);
+    if (m.rope) { fw->rope = m.rope->table; fw->rg = rope_geom(*m.rope, B, S, 2 * H); }
     Var out = Var::node(fw->o, fw, std::move(hf));
     History<BackwardEntry> hb = x.history;
     for (const Linear* l : {&m.q, &m.k, &m.v}) { hb.merge(l->weight.history); hb.merge(l->bias.history); }
@@ -2805,6 +2885,7 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     const Linear* ls[3] = {&m.q, &m.k, &m.v};
     for (int i = 0; i < 3; ++i) { bw->gw[i] = ls[i]->weight.grad; bw->gb[i] = ls[i]->bias.grad; }
     bw->g = g; bw->scale = scale; bw->p = m.drop.p; bw->status = m.drop.status; bw->causal = m.causal;
+    bw->rope = fw->rope; bw->rg = fw->rg;
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(hb));
 }
 // q / k / v are public members: the packed path is only valid while they still ARE the views of the packed storage
@@ -2824,6 +2905,13 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
     const int rows = x.shape()[0], S = rows / batch, dh = d_model / heads;
     if (rows % batch != 0 || x.shape()[1] != d_model) panic("MultiheadAttention: bad input shape");
     const float scale = 1.f / std::sqrt((float)dh);
+    if (rope) {
+        if (rope->head_dim != dh)
+            panic("MultiheadAttention: rope was built for heads of " + std::to_string(rope->head_dim) + ", the module has heads of " + std::to_string(dh));
+        if (S > rope->max_pos) panic("MultiheadAttention: " + std::to_string(S) + " positions exceed rope's table of " + std::to_string(rope->max_pos));
+    }
+    // the projections of the unpacked paths: queries and keys rotated when `rope` is set
+    auto rotated = [&](const Linear& l) { return rope ? l.forward(x).rope(*rope, batch, heads) : l.forward(x); };
     // Causal, where the fused core does not apply: the composition spelled out - one Addition node (broadcast over B*H) of a
     // constant (S, S) leaf, 0 on and below the diagonal and -inf above, in front of the Softmax, whose -inf lanes come out exactly 0.
     // Uploaded once per graph build; the fused `attention_probs` node has no mask operand and is not used.
@@ -2837,7 +2925,7 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
         still_packed())
         return o.forward(qkv_attention_node(*this, wqkv_, bqkv_, gwqkv_, gbqkv_, x, batch, S, heads, dh, scale));
     if (strided_heads && dh % 4 == 0) {  // attention GEMMs address the heads inside the projection layout: no copies
-        const VarDiff Qf = q.forward(x), Kf = k.forward(x), Vf = v.forward(x);
+        const VarDiff Qf = rotated(q), Kf = rotated(k), Vf = v.forward(x);
         if (fused && fused_core && Var::attention_core_supported(S, dh, drop.p))
             return o.forward(Qf.heads_attention(Kf, Vf, batch, S, heads, dh, scale, drop.p, drop.status, causal));
         const VarDiff scores = Qf.heads_scores(Kf, batch, S, heads, dh);
@@ -2846,8 +2934,8 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
                                                                : drop.forward((scores * scale).softmax(2));
         return o.forward(P.heads_context(Vf, batch, S, heads, dh));
     }
-    const VarDiff Q = q.forward(x).split_heads(batch, S, heads, dh);
-    const VarDiff K = k.forward(x).split_heads(batch, S, heads, dh);
+    const VarDiff Q = rotated(q).split_heads(batch, S, heads, dh);
+    const VarDiff K = rotated(k).split_heads(batch, S, heads, dh);
     const VarDiff V = v.forward(x).split_heads(batch, S, heads, dh);
     const VarDiff P = causal ? drop.forward((Q.bmm_t(K) * scale + causal_mask(S)).softmax(2))
                       : (fused && S % 4 == 0 && S <= 2048) ? Q.bmm_t(K).attention_probs(scale, drop.p, drop.status)
@@ -2856,6 +2944,17 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
     return o.forward(O);
 }
 
+
+RotaryEmbedding::RotaryEmbedding(DevicePtr dev, int head_dim_, int max_pos_, double base_, int rot_, bool interleaved_)
+    : head_dim(head_dim_), max_pos(max_pos_), rot(rot_ == 0 ? head_dim_ : rot_), base(base_), interleaved(interleaved_) {
+    if (head_dim <= 0 || max_pos <= 0) panic("RotaryEmbedding: head_dim and max_pos must be positive");
+    if (rot < 2 || rot > head_dim || rot % 2 != 0)
+        panic("RotaryEmbedding: rot must be even and in [2, head_dim = " + std::to_string(head_dim) + "], got " + std::to_string(rot));
+    if (!(base > 0.0) || !std::isfinite(base)) panic("RotaryEmbedding: base must be positive and finite");
+    if ((unsigned long long)max_pos * rot > (unsigned long long)INT_MAX) panic("RotaryEmbedding: max_pos * rot must fit 31 bits");
+    table = std::make_shared<HipArray>(dev, Shape{max_pos, rot / 2, 2}, HipArray::Uninit{});
+    check(nk_rope_table(dev->raw(), table->ptr(), max_pos, rot, base));
+}
 
 KvCache::KvCache(DevicePtr dev, int batch_, int heads_, int head_dim_, int capacity_)
     : batch(batch_), heads(heads_), head_dim(head_dim_), capacity(capacity_) {
@@ -2901,6 +3000,14 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
               " heads of " + std::to_string(cache.head_dim) + ", the step has batch " + std::to_string(batch) + ", " + std::to_string(heads) +
               " heads of " + std::to_string(dh));
     if (cache.k->device().get() != x.device().get()) panic("MultiheadAttention::forward_step: the cache lives on another device");
+    if (rope) {
+        if (rope->head_dim != dh)
+            panic("MultiheadAttention::forward_step: rope was built for heads of " + std::to_string(rope->head_dim) + ", the module has heads of " +
+                  std::to_string(dh));
+        if (cache.capacity > rope->max_pos)
+            panic("MultiheadAttention::forward_step: the cache's capacity of " + std::to_string(cache.capacity) + " exceeds rope's table of " +
+                  std::to_string(rope->max_pos));
+    }
     bool fresh = true;
     for (int b = 0; b < batch; ++b) {
         if (cache.lens()[b] + T > cache.capacity)
@@ -2932,6 +3039,7 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
     fw->ctx = zeros_like(x.data, Shape{n, d_model});
     fw->out = zeros_like(x.data, Shape{n, d_model});
     fw->kc = cache.k; fw->vc = cache.v;
+    if (rope) { fw->rope = rope->table; fw->rg = rope_geom(*rope, batch, T, fw->qkv ? 2 * heads : heads); }
     fw->scale = 1.f / std::sqrt((float)dh);
     // the core's own size guards (nk_attention.hip: mask words and projection elements below 2^31): past them the decode kernels
     // take the prefill instead of a refused call

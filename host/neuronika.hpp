@@ -257,6 +257,9 @@ enum class Reduction { Sum = 0, Mean = 1 };  // lib.rs:29-36
 enum class Activation { Gelu = 0, GeluTanh = 1, Silu = 2, Sigmoid = 3 };
 
 class VarDiff;
+namespace nn {
+struct RotaryEmbedding;
+}
 
 // ---------------------------------------------------------------------------------------------
 // var.rs — non-differentiable variable
@@ -306,6 +309,10 @@ class Var {
     Var gelu(bool tanh_approx = false) const;
     Var silu() const;
     Var glu(Activation gate = Activation::Sigmoid) const;
+    // Rotary position embedding (ours; semantics in neuronika_hip.h) of a (batch*T, heads*head_dim) value at positions 0 .. T-1: the
+    // first `rot` columns of every head rotated by the angles of the row's position, ONE node.  Panics on a shape mismatch or
+    // T > max_pos.
+    Var rope(const nn::RotaryEmbedding& rotary, int batch, int heads) const;
     Var unsqueeze(int axis) const;
     // Pooling over the spatial axes of an (N, C, spatial...) input (ours: the reference has none; semantics in neuronika_hip.h):
     // nd = rank - 2 = the length of `kernel`, `stride` (empty: stride = kernel) and `padding` (empty: zeros); floor mode, dilation 1.
@@ -444,6 +451,9 @@ class VarDiff {
     VarDiff gelu(bool tanh_approx = false) const;
     VarDiff silu() const;
     VarDiff glu(Activation gate = Activation::Sigmoid) const;
+    // one forward and one backward node; the rotation is orthogonal, so the backward (the same kernel with the sign of the sine
+    // flipped) holds the table and the geometry only
+    VarDiff rope(const nn::RotaryEmbedding& rotary, int batch, int heads) const;
     VarDiff unsqueeze(int axis) const;
     // the differentiable max-pool node owns the int32 offsets of the selected elements (4 bytes per output)
     VarDiff max_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding) const;
@@ -811,6 +821,19 @@ struct Dropout {
     VarDiff forward(const VarDiff& x) const { return x.dropout(p, status); }
 };
 
+// Rotary position embedding (ours: the reference has no position encoding; semantics at nk_rope_fwd in neuronika_hip.h).  Owns the
+// (max_pos, rot/2, 2) table of (cos, sin) of p * base^(-2j/rot), made in f64 at construction; no parameters, nothing trainable.
+// `rot` (even, 2 <= rot <= head_dim; 0 = head_dim) columns of every head are rotated, the others pass through; `interleaved`
+// pairs (2j, 2j+1) (GPT-J / RoFormer) instead of (j, j + rot/2) (NeoX / LLaMA-HF).  Shared between the layers of a model:
+// `MultiheadAttention::rope`, `Var / VarDiff::rope`.
+struct RotaryEmbedding {
+    RotaryEmbedding(DevicePtr dev, int head_dim, int max_pos, double base = 10000.0, int rot = 0, bool interleaved = false);
+    int head_dim, max_pos, rot;
+    double base;
+    bool interleaved;
+    Shared<HipArray> table;
+};
+
 // The keys and values of one causal attention layer, kept on the device between the steps of incremental decoding (ours: the
 // reference has no such thing; semantics at nk_kv_cache_append / nk_attention_decode_fwd in neuronika_hip.h).  Kc, Vc are
 // (batch, heads, capacity, head_dim), head-major, allocated once and never initialised: nothing past a sample's length is read
@@ -858,6 +881,13 @@ struct MultiheadAttention {
     // path: the fused core runs its causal kernels (which skip the key tiles above the diagonal); the node-by-node paths add M, a
     // constant (S, S) leaf, on the broadcast Addition node.  Dropout draws keep their positions either way.
     bool causal = false;
+    // Rotary position embedding of the queries and keys: null (the default) builds exactly the graph built without it.  Read when
+    // forward() / forward_step() build their nodes, like `causal`, and honoured on every path, causal or not: the packed node rotates
+    // Q|K in place in its (n, 3d) projection output (one launch, 2*heads heads, stride 3d) and applies the inverse to the first 2d
+    // columns of its gradient in front of the three products that read it; the other paths rotate q.forward(x) and k.forward(x)
+    // through `VarDiff::rope`.  forward_step rotates the new Q and K rows at lens[b] + t before the append: the cache holds ROTATED
+    // keys.  Panics: rope->head_dim != d_model / heads, S > max_pos (forward), cache.capacity > max_pos (forward_step).
+    Shared<RotaryEmbedding> rope;
     MultiheadAttention(DevicePtr dev, int d_model, int heads, double p, uint64_t seed);
     // four Linear layers built elsewhere (e.g. deserialised): their weights are NOT packed, `packed_qkv` is off
     MultiheadAttention(Linear q, Linear k, Linear v, Linear o, int heads, double p);

@@ -475,6 +475,23 @@ PYBIND11_MODULE(_tape, m) {
         .def("reset", &nn::KvCache::reset, "every length back to 0")
         .def("truncate", &nn::KvCache::truncate, py::arg("lens"),
              "Give every sample a length no longer than its current one: ragged prompts after a right-padded prefill, roll-back.");
+    py::class_<nn::RotaryEmbedding, std::shared_ptr<nn::RotaryEmbedding>>(nn, "RotaryEmbedding")
+        .def(py::init<DevicePtr, int, int, double, int, bool>(), py::arg("dev"), py::arg("head_dim"), py::arg("max_pos"), py::arg("base") = 10000.0,
+             py::arg("rot") = 0, py::arg("interleaved") = false,
+             "Rotary position embedding: owns the (max_pos, rot/2, 2) table of (cos, sin) of p * base^(-2j/rot), made in f64. rot = 0 means "
+             "head_dim; interleaved pairs (2j, 2j+1) instead of (j, j + rot/2). No parameters.")
+        .def_readonly("head_dim", &nn::RotaryEmbedding::head_dim)
+        .def_readonly("max_pos", &nn::RotaryEmbedding::max_pos)
+        .def_readonly("rot", &nn::RotaryEmbedding::rot)
+        .def_readonly("base", &nn::RotaryEmbedding::base)
+        .def_readonly("interleaved", &nn::RotaryEmbedding::interleaved)
+        .def("table", [](const nn::RotaryEmbedding& r) { return to_numpy(*r.table); }, "the table as a (max_pos, rot/2, 2) array");
+    // registered here, after the class they take: the signatures in the docstrings name it
+    py::reinterpret_borrow<py::class_<Var>>(m.attr("Var"))
+        .def("rope", &Var::rope, py::arg("rotary"), py::arg("batch"), py::arg("heads"),
+             "Rotate the first `rot` columns of every head of a (batch*T, heads*head_dim) value by the angles of positions 0 .. T-1.");
+    py::reinterpret_borrow<py::class_<VarDiff>>(m.attr("VarDiff"))
+        .def("rope", &VarDiff::rope, py::arg("rotary"), py::arg("batch"), py::arg("heads"));
     py::class_<nn::MultiheadAttention>(nn, "MultiheadAttention")
         .def(py::init<DevicePtr, int, int, double, uint64_t>(), py::arg("dev"), py::arg("d_model"), py::arg("heads"),
              py::arg("p") = 0.0, py::arg("seed") = 0)
@@ -490,6 +507,7 @@ PYBIND11_MODULE(_tape, m) {
         .def_readwrite("fused_core", &nn::MultiheadAttention::fused_core)
         .def_readwrite("packed_qkv", &nn::MultiheadAttention::packed_qkv)
         .def_readwrite("causal", &nn::MultiheadAttention::causal)
+        .def_readwrite("rope", &nn::MultiheadAttention::rope)  // a shared RotaryEmbedding; None clears it
         .def_readonly("d_model", &nn::MultiheadAttention::d_model)
         .def_readonly("heads", &nn::MultiheadAttention::heads)
         .def("forward", &nn::MultiheadAttention::forward)

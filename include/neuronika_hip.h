@@ -838,6 +838,36 @@ int nk_attention_decode_fwd(nk_device* dev, const float* Q, int ldq, const float
                             float* workspace, int B, int T, int H, int dh, int cap, float scale);
 size_t nk_attention_decode_workspace(int B, int T, int H, int dh, int cap);
 int nk_attention_decode_chunk(int dh);
+/* ------------------------------------------------------------------ rotary position embedding --
+ * Ours (the reference has no position encoding of any kind): RoPE, Su et al. 2021 (RoFormer), as LLaMA / Mistral / Qwen / GPT-NeoX /
+ * Phi apply it to the query and key rows in front of the attention scores.
+ * Geometry: a buffer of B*T rows with row stride ld floats; a row holds NH heads of dh floats from column 0 (NH = 2*heads, ld = 3*d
+ * addresses the Q|K blocks of a packed projection output; its V block, like every column >= NH*dh, is never read or written).
+ * Row b*T + t sits at position p = (start ? start[b] : 0) + t; `start` is a DEVICE array of B int32 or NULL - the array
+ * nk_kv_cache_append takes.  The first `rot` columns of each head are rotated (rot even, 2 <= rot <= dh), columns [rot, dh) pass
+ * through.  Pairing: interleaved == 0 half-split pairs (j, j + rot/2) (NeoX / LLaMA-HF), otherwise interleaved pairs (2j, 2j+1)
+ * (GPT-J / RoFormer), j < rot/2.  With (c, s) = table[p][j], the arithmetic is fixed to the bit:
+ *     y1 = fmaf(x1, c, -(x2 * s));   y2 = fmaf(x2, c, x1 * s)          (backward / inverse: s -> -s)
+ * by every kernel family: the bits of an output element depend on its pair, its position and the table only - not on the kernel
+ * family (16-byte or scalar accesses), B, T, NH, the strides, in place or not, or on how p splits into start[b] + t.
+ * Table: (max_pos, rot/2, 2) f32, (cos, sin) interleaved; entry (p, j) is the f32 rounding of the f64 cos / sin of
+ * p * base^(-2j/rot), frequency, product and function all in f64 (an f32 angle is 1e-3 rad off at position 16 384).
+ * nk_rope_table fills it on the host and uploads it (one synchronising call at model construction; refuses capture).
+ * A position outside [0, max_pos) is clamped into the table by the kernel: no `start` can make it read outside the table.
+ * nk_rope_fwd: y = R x.  y == x with ldy == ldx is the in-place form (a thread owns both members of each pair it touches; no other
+ *   overlap of x and y is allowed).  Out of place the pass-through columns are copied.
+ * nk_rope_bwd: dx += R^T g; nk_rope_bwd_assign: dx = R^T g (dx == g with lddx == ldg legal for the assign form only);
+ *   pass-through columns dx (+)= g.  R is orthogonal: the backward keeps nothing of the input.
+ * No atomics, no LDS.  Row offsets are 64-bit (rows * ld may exceed 2^31); B*T itself must fit 31 bits.
+ * NK_ERR_INVALID, nothing written: rot odd or outside [2, dh], NH*dh > ld (either stride), non-positive B / T / NH / dh / max_pos,
+ * T > max_pos with start == NULL, a null pointer, dx == g in nk_rope_bwd, x == y with different strides. */
+int nk_rope_table(nk_device* dev, float* table, int max_pos, int rot, double base);
+int nk_rope_fwd(nk_device* dev, const float* x, int ldx, float* y, int ldy, const float* table, const int* start, int B, int T, int NH,
+                int dh, int rot, int max_pos, int interleaved);
+int nk_rope_bwd(nk_device* dev, float* dx, int lddx, const float* g, int ldg, const float* table, const int* start, int B, int T, int NH,
+                int dh, int rot, int max_pos, int interleaved);
+int nk_rope_bwd_assign(nk_device* dev, float* dx, int lddx, const float* g, int ldg, const float* table, const int* start, int B, int T,
+                       int NH, int dh, int rot, int max_pos, int interleaved);
 /* ------------------------------------------------------------------ dropout ------------ */
 /* Dropout::forward node/dropout/mod.rs:53-79.  train && 0<p<1: noise ~ Bernoulli(1-p) in
  * {0,1} is (re)drawn from Philox4x32-10(seed, offset) and written to `noise` (f32, like the

@@ -18,7 +18,7 @@ use std::{cell::{Cell, RefCell}, rc::Rc};
 
 use ndarray::{Array, Dimension, Ix0, Ix1, Ix2, Ix3, Ix4, Ix5, RemoveAxis};
 use neuronika_variable::{
-    hip::{Device, Gate, HipVar, HipVarDiff, KvBuffers, PaddingMode},
+    hip::{Device, Gate, HipVar, HipVarDiff, KvBuffers, PaddingMode, RotaryTable},
     Reduction,
 };
 use rand::distributions::{Distribution, Uniform};
@@ -456,6 +456,26 @@ impl KvCache {
     }
 }
 
+/// Rotary position embedding (ours; the tested mirror is `nn::RotaryEmbedding` in `host/neuronika.hpp`): owns the table of
+/// `(cos, sin)` of `p * base^(-2j/rot)`, no parameters.  Shared between the layers of a model through `Rc`:
+/// `MultiheadAttention::rope`, `HipVar / HipVarDiff::rope`.
+pub struct RotaryEmbedding {
+    pub table: RotaryTable,
+}
+
+impl RotaryEmbedding {
+    /// `rot`: the rotated columns of every head (even, at most `head_dim`); `interleaved`: pairs `(2j, 2j+1)` instead of
+    /// `(j, j + rot/2)`.
+    pub fn new(head_dim: usize, max_pos: usize, base: f64, rot: usize, interleaved: bool, device: &Device) -> Self {
+        Self { table: RotaryTable::new(head_dim, max_pos, base, rot, interleaved, device) }
+    }
+
+    /// `input`: `(batch * seq, heads * head_dim)` at positions `0 .. seq - 1`.
+    pub fn forward(&self, input: HipVarDiff<Ix2>, batch: usize, heads: usize) -> HipVarDiff<Ix2> {
+        input.rope(&self.table, batch, heads)
+    }
+}
+
 /// Multi-head self-attention composed from reference operations (module named by `src/lib.rs:783-797`; SURVEY.md 8a note):
 /// `Q, K, V = x.mm_t(W) + b`; per (sample, head): `P = dropout(softmax(Q K^T / sqrt(dh)))`, `O = P V`; `out = O.mm_t(Wo) + bo`.
 /// Input rows are `(batch * seq, d_model)`.
@@ -475,6 +495,11 @@ pub struct MultiheadAttention {
     /// Causal self-attention: query `r` of a sample attends to the keys `<= r` of that sample (`P = dropout(softmax(scores * scale +
     /// M))`, `M` = 0 on and below the diagonal, -inf above).  Read by `forward` when it builds the graph; `false` after `new`.
     pub causal: bool,
+    /// Rotary position embedding of the queries and keys: `None` after `new`, and then every graph is the one built without it.
+    /// Read by `forward` / `forward_step` when they build their nodes: the Q|K blocks of the packed projection are rotated in place
+    /// right behind the projection (one launch, `2 * heads` heads, stride `3 * d_model`), at `lens[b] + t` in `forward_step`, so the
+    /// cache holds rotated keys; the backward applies the inverse in place to `[dQ | dK]` in front of the projection's products.
+    pub rope: Option<Rc<RotaryEmbedding>>,
 }
 
 impl MultiheadAttention {
@@ -484,7 +509,7 @@ impl MultiheadAttention {
         // each of the three row blocks is initialised as its own Linear(d_model, d_model): U(-k, k), k = 1 / sqrt(d_model) -
         // the fan-in of the packed layer is d_model too, so one draw over (3 d, d) follows the same law
         Self { qkv: Linear::new(d_model, 3 * d_model, device), o: Linear::new(d_model, d_model, device), d_model, heads, dropout: Dropout::new(p),
-               causal: false }
+               causal: false, rope: None }
     }
 
     /// Row range of the packed weight (and element range of the packed bias) holding the query / key / value projection.
@@ -507,6 +532,13 @@ impl MultiheadAttention {
         let (seq, dh) = (rows / batch, self.d_model / self.heads);
         let scale = 1. / (dh as f32).sqrt();
         let packed = self.qkv.forward(input);
+        let packed = match &self.rope {
+            Some(r) => {
+                assert!(r.table.head_dim() == dh && seq <= r.table.max_pos(), "MultiheadAttention: rope does not fit the head size or the sequence");
+                packed.rope_in_place(&r.table, batch, 2 * self.heads)
+            }
+            None => packed,
+        };
         let context = if self.causal {
             packed.packed_heads_attention_causal(batch, seq, self.heads, dh, scale, self.dropout.p, self.dropout.status.clone())
         } else {
@@ -534,6 +566,13 @@ impl MultiheadAttention {
         assert!(start.iter().all(|&l| l + rows / batch <= capacity), "MultiheadAttention::forward_step: the step exceeds the capacity");
         let scale = 1. / (dh as f32).sqrt();
         let packed = input.linear(self.qkv.weight.detached(), self.qkv.bias.detached(), false);
+        let packed = match &self.rope {
+            Some(r) => {
+                assert!(r.table.head_dim() == dh && capacity <= r.table.max_pos(), "MultiheadAttention::forward_step: rope does not fit the head size or the capacity");
+                packed.rope_in_place(&r.table, batch, 2 * self.heads, Some(&start))
+            }
+            None => packed,
+        };
         let context = packed.packed_decode_attention(&cache.buffers, &start, scale);
         cache.advance(rows / batch);
         context.linear(self.o.weight.detached(), self.o.bias.detached(), false)

@@ -24,6 +24,7 @@ use super::{
         DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
         decode_chunk, decode_workspace, PackedDecodeAttention,
+        rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
         ReLUBackward, ReluMask, Softmax, SoftmaxBackward,
         SquaredError, SquaredErrorBackward, Sum, SumBackward, Transpose, TransposeBackward,
@@ -589,6 +590,106 @@ impl HipVar<Ix2> {
         let op = PackedDecodeAttention::new(geometry, capacity as i32, self.data, buffers.keys.clone(), buffers.values.clone(), start,
                                             buffers.workspace_for(rows, &device), data.clone(), scale);
         HipVar::node(data, Rc::new(op), self.history)
+    }
+}
+
+/// The table of a rotary position embedding (ours; semantics at `nk_rope_fwd` in `include/neuronika_hip.h`): `(max_pos, rot / 2, 2)`
+/// f32 `(cos, sin)` of `p * base^(-2j/rot)`, made in f64 by `nk_rope_table` at construction.  The first `rot` columns of every head
+/// are rotated (even, `2 <= rot <= head_dim`), pairs `(j, j + rot/2)` or, `interleaved`, `(2j, 2j+1)`.  Nothing trainable; shared by
+/// the layers of a model (`neuronika_nn::hip::RotaryEmbedding`).
+pub struct RotaryTable {
+    table: Shared<HipArray<Ix3>>,
+    head_dim: usize,
+    max_pos: usize,
+    rot: usize,
+    interleaved: bool,
+}
+
+impl RotaryTable {
+    pub fn new(head_dim: usize, max_pos: usize, base: f64, rot: usize, interleaved: bool, device: &Device) -> Self {
+        assert!(head_dim > 0 && max_pos > 0, "RotaryTable: head_dim and max_pos must be positive");
+        assert!(rot >= 2 && rot <= head_dim && rot % 2 == 0, "RotaryTable: rot must be even and in [2, head_dim]");
+        assert!(base > 0. && base.is_finite(), "RotaryTable: base must be positive and finite");
+        Self { table: Rc::new(RefCell::new(rope_table(max_pos, rot, base, device))), head_dim, max_pos, rot, interleaved }
+    }
+
+    pub fn head_dim(&self) -> usize {
+        self.head_dim
+    }
+
+    pub fn max_pos(&self) -> usize {
+        self.max_pos
+    }
+
+    pub fn rot(&self) -> usize {
+        self.rot
+    }
+
+    pub fn interleaved(&self) -> bool {
+        self.interleaved
+    }
+
+    /// The launch geometry of `heads` heads per row of stride `ld` over `batch * rows` rows, after the shape checks.
+    fn geometry(&self, total: usize, width: usize, batch: usize, heads: usize, ld: usize) -> RopeGeometry {
+        assert!(batch > 0 && total > 0 && total % batch == 0, "rope: rows must be a positive multiple of the batch");
+        assert!(heads > 0 && heads * self.head_dim <= width && width == ld, "rope: the input must hold heads * head_dim columns");
+        RopeGeometry { batch: batch as i32, rows: (total / batch) as i32, heads: heads as i32, dh: self.head_dim as i32, rot: self.rot as i32,
+                       max_pos: self.max_pos as i32, interleaved: self.interleaved as i32, ld: ld as i32 }
+    }
+}
+
+impl HipVar<Ix2> {
+    /// Rotary position embedding of a `(batch*rows, heads*head_dim)` value at positions `0 .. rows - 1`: ONE node (`nk_rope_fwd`).
+    pub fn rope(self, rotary: &RotaryTable, batch: usize, heads: usize) -> HipVar<Ix2> {
+        let dim = self.data.borrow().dimension();
+        assert!(dim[1] == heads * rotary.head_dim, "rope: the input must be (batch*rows, heads*head_dim)");
+        assert!(dim[0] / batch.max(1) <= rotary.max_pos, "rope: the positions exceed the table");
+        let geometry = rotary.geometry(dim[0], dim[1], batch, heads, dim[1]);
+        let data = shared(dim, &self.device());
+        let op = Rope::new(geometry, rotary.table.clone(), self.data, data.clone());
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    /// The rotation IN PLACE over the first `heads * head_dim` columns of `self` - `heads = 2 * H` on a `(rows, 3 * H * head_dim)`
+    /// packed projection rotates its Q|K blocks and leaves V alone - at positions `start[b] + t` (`None`: `t`).  The result shares
+    /// its buffer with `self`; ONE node right behind the one that wrote the buffer.
+    pub fn rope_in_place(self, rotary: &RotaryTable, batch: usize, heads: usize, start: Option<&[usize]>) -> HipVar<Ix2> {
+        let dim = self.data.borrow().dimension();
+        let geometry = rotary.geometry(dim[0], dim[1], batch, heads, dim[1]);
+        let device = self.device();
+        let start = start.map(|s| {
+            assert!(s.len() == batch && s.iter().all(|&l| l + dim[0] / batch <= rotary.max_pos), "rope_in_place: the positions exceed the table");
+            let cells: Vec<f32> = s.iter().map(|&l| f32::from_bits(l as u32)).collect();
+            HipArray::from_slice(&cells, ndarray::Dim([batch]), device.clone())
+        });
+        assert!(start.is_some() || dim[0] / batch <= rotary.max_pos, "rope_in_place: the positions exceed the table");
+        let data = self.data.clone();
+        let op = RopeInPlace::new(geometry, rotary.table.clone(), self.data, start);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+}
+
+impl HipVarDiff<Ix2> {
+    /// `HipVar::rope` with its backward entry (`RopeBackward`: `dx += R^T g`, the same kernel with the sign of the sine flipped).
+    pub fn rope(self, rotary: &RotaryTable, batch: usize, heads: usize) -> HipVarDiff<Ix2> {
+        let dim = self.var.data.borrow().dimension();
+        let geometry = rotary.geometry(dim[0], dim[1], batch, heads, dim[1]);
+        let var = self.var.rope(rotary, batch, heads);
+        let grad = Rc::new(Gradient::hip_zeros(dim, var.device()));
+        let op: Rc<dyn Backward> = Rc::new(RopeBackward::new(geometry, rotary.table.clone(), self.grad, grad.clone()));
+        HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
+    }
+
+    /// `HipVar::rope_in_place` at positions `0 .. rows - 1` with its backward entry: the inverse rotation in place in the gradient
+    /// `self` already owns (`RopeInPlaceBackward`), between the consumer that writes it and the producer's backward that reads it.
+    /// The buffer must have ONE consumer.
+    pub fn rope_in_place(self, rotary: &RotaryTable, batch: usize, heads: usize) -> HipVarDiff<Ix2> {
+        let dim = self.var.data.borrow().dimension();
+        let geometry = rotary.geometry(dim[0], dim[1], batch, heads, dim[1]);
+        let var = self.var.rope_in_place(rotary, batch, heads, None);
+        let grad = self.grad;
+        let op: Rc<dyn Backward> = Rc::new(RopeInPlaceBackward::new(geometry, rotary.table.clone(), grad.clone()));
+        HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
     }
 }
 

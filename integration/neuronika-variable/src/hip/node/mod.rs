@@ -20,6 +20,7 @@ mod optim;
 mod pointwise;
 mod pooling;
 mod reduction;
+mod rope;
 
 pub(crate) use activation::*;
 pub(crate) use attention::*;
@@ -37,6 +38,7 @@ pub(crate) use optim::*;
 pub(crate) use pointwise::*;
 pub(crate) use pooling::*;
 pub(crate) use reduction::*;
+pub(crate) use rope::*;
 
 use std::rc::Rc;
 

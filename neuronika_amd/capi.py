@@ -207,6 +207,10 @@ _SIGS = {
     "nk_attention_decode_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float],
     "nk_attention_decode_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_attention_decode_chunk": [C.c_int],
+    "nk_rope_table": [VP, VP, C.c_int, C.c_int, C.c_double],
+    "nk_rope_fwd": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_rope_bwd": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_rope_bwd_assign": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_scale_softmax_dropout_fwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_scale_softmax_dropout_bwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_dropout_fwd": [VP, VP, VP, VP, C.c_size_t, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
@@ -975,6 +979,23 @@ def attention_decode_fwd(dev, Q, ldq, Kc, Vc, start, out, workspace, B, T, H, dh
     """Single-query attention over the caches: query (b, t) reads keys < min(start[b] + t + 1, cap); out is (B*T, H*dh);
     workspace: `attention_decode_workspace(B, T, H, dh, cap)` floats."""
     check(lib.nk_attention_decode_fwd(dev.h, _p(Q), ldq, _p(Kc), _p(Vc), _p(start), _p(out), _p(workspace), B, T, H, dh, cap, scale))
+
+
+def rope_table(dev, table, max_pos, rot, base=10000.0):
+    """Fill the (max_pos, rot/2, 2) table of (cos, sin) of p * base^(-2j/rot): f64 on the host, rounded to f32 once, one upload."""
+    check(lib.nk_rope_table(dev.h, _p(table), max_pos, rot, float(base)))
+
+
+def rope_fwd(dev, x, ldx, y, ldy, table, start, B, T, NH, dh, rot, max_pos, interleaved=False):
+    """y = R x over the first `rot` columns of NH heads of dh floats per row (row b*T + t at position start[b] + t; start: int32
+    device array of B or None); y is x with ldy == ldx: in place.  `view_offset` addresses the Q|K blocks of a packed buffer."""
+    check(lib.nk_rope_fwd(dev.h, _p(x), ldx, _p(y), ldy, _p(table), _p(start), B, T, NH, dh, rot, max_pos, int(bool(interleaved))))
+
+
+def rope_bwd(dev, dx, lddx, g, ldg, table, start, B, T, NH, dh, rot, max_pos, interleaved=False, assign=False):
+    """dx (+)= R^T g: the same pass with the sign of the sine flipped; dx is g legal with assign=True only."""
+    fn = lib.nk_rope_bwd_assign if assign else lib.nk_rope_bwd
+    check(fn(dev.h, _p(dx), lddx, _p(g), ldg, _p(table), _p(start), B, T, NH, dh, rot, max_pos, int(bool(interleaved))))
 
 
 def attention_bwd(dev, dQ, dK, dV, dS, dropped, dO, out, scores, stats, mask_bits, Q, K, V, B, S, H, dh, scale, p, train=True,
