@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
-"""Greedy generation from a two-layer toy decoder (token + position Embedding, pre-LayerNorm blocks of causal MultiheadAttention
+"""Generation (greedy, or sampled on the device) from a two-layer toy decoder (token + position Embedding, pre-LayerNorm blocks of causal MultiheadAttention
 and a GELU MLP, a LayerNorm and a Linear head) with incremental decoding: the prompt is prefilled in one `forward_step`, then every
 new token runs through the layers alone and attends to the keys and values each layer's `KvCache` kept on the device - one read of
 K and V per token instead of the causal forward over the whole prefix.
 
     python examples/generate.py [new_tokens]      # needs an MI355X; prints the prompt and the generated ids
     python examples/generate.py [new_tokens] --rope   # rotary positions: no position table, one shared RotaryEmbedding on every block
+    python examples/generate.py [new_tokens] --device-sample [--temperature 0.8] [--top-k 8] [--top-p 0.95] [--seed 1]
+                                                      # the loop stays on the device: `nn.Sampler` draws the next ids from the logits
+                                                      # where the head left them, the ids Var feeds `Embedding.forward`, and the host
+                                                      # reads the ids once, after the last step.  Temperature 0 (the default) is greedy
+                                                      # and generates the ids of the host path token for token
 
 The weights are random (fixed seeds): the text means nothing, the mechanics are the point.  The last lines compare every step's
 logits with those of the full causal forward over the same prefix."""
+import argparse
 import os
 import sys
 
@@ -52,22 +58,29 @@ class Decoder:
         self.blocks = [Block(nk, dev, 100 * (i + 1), self.rope) for i in range(LAYERS)]
         self.ln, self.head = nk.nn.LayerNorm(dev, [D_MODEL]), nk.nn.Linear(dev, D_MODEL, VOCAB, 7)
 
-    def embed(self, ids, first):
-        """ids (batch, T) at positions first .. first + T - 1 -> (batch * T, d_model)"""
-        batch, T = ids.shape
+    def embed(self, ids, first, shape=None):
+        """ids (batch, T) at positions first .. first + T - 1 -> (batch * T, d_model); a device Var of batch * T ids comes with its
+        `shape` = (batch, T) and is gathered where it is"""
+        batch, T = ids.shape if shape is None else shape
         where = np.tile(np.arange(first, first + T, dtype=np.float32), batch)
         up = lambda a: self.nk.from_ndarray(self.dev, np.ascontiguousarray(a, dtype=np.float32).reshape(-1))
+        tokens = self.tok.forward(up(ids) if shape is None else ids)
         if self.rope is not None:
-            return self.tok.forward(up(ids))
-        return self.tok.forward(up(ids)) + self.pos.forward(up(where))
+            return tokens
+        return tokens + self.pos.forward(up(where))
 
-    def logits_step(self, ids, first, caches):
-        h = self.embed(ids, first)
+    def step(self, ids, first, caches, shape=None):
+        """the logits of the new positions as a (batch * T, vocab) variable on the device, computed"""
+        batch = ids.shape[0] if shape is None else shape[0]
+        h = self.embed(ids, first, shape)
         for block, cache in zip(self.blocks, caches):
-            h = block.step(h, ids.shape[0], cache)
+            h = block.step(h, batch, cache)
         out = self.head.forward(self.ln.forward(h))
         out.forward()
-        return out.data().reshape(ids.shape[0], ids.shape[1], VOCAB)
+        return out
+
+    def logits_step(self, ids, first, caches):
+        return self.step(ids, first, caches).data().reshape(ids.shape[0], ids.shape[1], VOCAB)
 
     def logits_full(self, ids):
         h = self.embed(ids, 0)
@@ -78,7 +91,26 @@ class Decoder:
         return out.data().reshape(ids.shape[0], ids.shape[1], VOCAB)
 
 
-def main(new_tokens=16, rope=False):
+def generate_on_device(nk, dev, model, prompt, new_tokens, caches, temperature, top_k, top_p, seed):
+    """The loop without the host: every step's logits stay where the head wrote them, `nn.Sampler` draws the next id of each sample
+    from their last row, and that (batch,) Var is the next step's input.  One read of the ids behind the last step.  (Each step's
+    graph keeps the earlier steps' nodes in its history; they were computed once and are not run again.)"""
+    batch, n = prompt.shape
+    sampler = nk.nn.Sampler(dev, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+    logits = model.step(prompt, 0, caches)                               # prefill
+    drawn = []
+    for i in range(new_tokens):
+        nxt = sampler.forward(logits, batch)                             # (batch,) ids as f32, no gradient
+        drawn.append(nxt)
+        logits = model.step(nxt, n + i, caches, shape=(batch, 1))
+    assert sampler.offset == new_tokens                                  # one Philox offset per executed draw
+    new = np.stack([v.data() for v in drawn], axis=1).astype(prompt.dtype)
+    ids = np.concatenate([prompt, new], axis=1)
+    worst = float(np.abs(logits.data().reshape(batch, VOCAB) - model.logits_full(ids)[:, -1]).max())
+    return ids, worst
+
+
+def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=0, top_p=1.0, seed=0):
     import neuronika_amd
     nk = neuronika_amd.tape
     dev = nk.Device(0)
@@ -87,13 +119,16 @@ def main(new_tokens=16, rope=False):
     batch, n = prompt.shape
     assert n + new_tokens <= CONTEXT
     caches = [nk.nn.KvCache(dev, batch, HEADS, D_MODEL // HEADS, CONTEXT) for _ in range(LAYERS)]
-    logits = model.logits_step(prompt, 0, caches)                        # prefill: every prompt position in one step
-    ids, worst = prompt, 0.0
-    for _ in range(new_tokens):
-        nxt = logits[:, -1].argmax(axis=1).reshape(batch, 1)
-        ids = np.concatenate([ids, nxt], axis=1)
-        logits = model.logits_step(nxt, ids.shape[1] - 1, caches)        # one token through the layers, K and V from the caches
-        worst = max(worst, float(np.abs(logits[:, -1] - model.logits_full(ids)[:, -1]).max()))
+    if device_sample:
+        ids, worst = generate_on_device(nk, dev, model, prompt, new_tokens, caches, temperature, top_k, top_p, seed)
+    else:
+        logits = model.logits_step(prompt, 0, caches)                    # prefill: every prompt position in one step
+        ids, worst = prompt, 0.0
+        for _ in range(new_tokens):
+            nxt = logits[:, -1].argmax(axis=1).reshape(batch, 1)
+            ids = np.concatenate([ids, nxt], axis=1)
+            logits = model.logits_step(nxt, ids.shape[1] - 1, caches)    # one token through the layers, K and V from the caches
+            worst = max(worst, float(np.abs(logits[:, -1] - model.logits_full(ids)[:, -1]).max()))
     assert caches[0].lens() == [n + new_tokens] * batch
     print("prompt   ", prompt[0].tolist())
     print("generated", ids[0, n:].tolist())
@@ -102,5 +137,13 @@ def main(new_tokens=16, rope=False):
 
 
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if a != "--rope"]
-    main(int(args[0]) if args else 16, rope="--rope" in sys.argv[1:])
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("new_tokens", nargs="?", type=int, default=16)
+    ap.add_argument("--rope", action="store_true", help="rotary positions instead of the learned position table")
+    ap.add_argument("--device-sample", action="store_true", help="draw the next ids on the device (nn.Sampler); the host reads them once")
+    ap.add_argument("--temperature", type=float, default=0.0, help="with --device-sample: 0 = greedy")
+    ap.add_argument("--top-k", type=int, default=0, help="with --device-sample: 0 = off")
+    ap.add_argument("--top-p", type=float, default=1.0, help="with --device-sample: 1 = off")
+    ap.add_argument("--seed", type=int, default=0, help="with --device-sample: the Philox key of the draws")
+    a = ap.parse_args()
+    main(a.new_tokens, rope=a.rope, device_sample=a.device_sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed)

@@ -1023,6 +1023,23 @@ struct RopeBwd : Backward {
     void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
 };
 
+// Token sampling (ours; the reference has no such node; semantics at nk_sample_fwd in neuronika_hip.h): the ids of the last of T rows
+// of every sample of (batch*T, V) logits, as f32.  No backward node: ids are data.  Every forward that was issued consumes one
+// offset of the sampler's counter, the way the dropout node consumes its calls (a refused capture throws before the increment).
+struct SampleFwd : Forward {
+    Shared<HipArray> logits, ids;
+    int batch = 0, T = 0, V = 0;
+    float temperature = 1.f, top_p = 1.f;
+    int top_k = 0;
+    uint64_t seed = 0;
+    Shared<uint64_t> offset;
+    void forward() const override {
+        check(nk_sample_fwd(D(logits), logits->ptr() + (size_t)(T - 1) * V, (long long)T * V, batch, V, ids->ptr(), temperature, top_k, top_p, seed,
+                            *offset));
+        ++(*offset);
+    }
+};
+
 // Cross entropy of class logits against integer targets (ours; the reference has no such node; semantics in neuronika_hip.h):
 // log-softmax and NLL in one forward node, which owns `lse` (one float per position); the backward recomputes the softmax from the
 // logits.  The first writer of the logits' gradient takes the assign form (no memset, no read; inactive rows written as zeros).
@@ -1688,6 +1705,21 @@ static Shared<RopeFwd> rope_fwd_node(const Var& x, const nn::RotaryEmbedding& r,
 Var Var::rope(const nn::RotaryEmbedding& rotary, int batch, int heads) const {
     auto n = rope_fwd_node(*this, rotary, batch, heads);
     auto y = n->y;
+    return Var::node(y, n, history);
+}
+Var Var::sample(const nn::Sampler& sp, int batch) const {
+    const Shape& s = shape();
+    if (s.size() != 2 || batch <= 0 || s[0] == 0 || s[0] % batch != 0 || s[1] <= 0)
+        panic("sample: the logits must be (batch*T, V) with batch = " + std::to_string(batch) + " dividing the rows");
+    if (s[1] > (1 << 20)) panic("sample: V = " + std::to_string(s[1]) + " exceeds 2^20");
+    if (!(sp.temperature >= 0.f) || !std::isfinite(sp.temperature)) panic("sample: temperature must be finite and not negative");
+    if (!(sp.top_p > 0.f)) panic("sample: top_p must be positive");
+    if (sp.dev.get() != device().get()) panic("sample: the sampler lives on another device");
+    auto n = std::make_shared<SampleFwd>();
+    n->logits = data; n->ids = zeros_like(data, Shape{batch});
+    n->batch = batch; n->T = s[0] / batch; n->V = s[1];
+    n->temperature = sp.temperature; n->top_k = sp.top_k; n->top_p = sp.top_p; n->seed = sp.seed; n->offset = sp.offset;
+    auto y = n->ids;
     return Var::node(y, n, history);
 }
 Var Var::neg() const { return pointwise_var(NK_NEG, 0, *this); }
@@ -2944,6 +2976,14 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
     return o.forward(O);
 }
 
+
+Sampler::Sampler(DevicePtr dev_, float temperature_, int top_k_, float top_p_, uint64_t seed_)
+    : dev(std::move(dev_)), temperature(temperature_), top_k(top_k_), top_p(top_p_), seed(seed_), offset(std::make_shared<uint64_t>(0)) {
+    if (!(temperature >= 0.f) || !std::isfinite(temperature)) panic("Sampler: temperature must be finite and not negative");
+    if (!(top_p > 0.f)) panic("Sampler: top_p must be positive");
+}
+Var Sampler::forward(const Var& logits, int batch) const { return logits.sample(*this, batch); }
+Var Sampler::forward(const VarDiff& logits, int batch) const { return logits.var.sample(*this, batch); }
 
 RotaryEmbedding::RotaryEmbedding(DevicePtr dev, int head_dim_, int max_pos_, double base_, int rot_, bool interleaved_)
     : head_dim(head_dim_), max_pos(max_pos_), rot(rot_ == 0 ? head_dim_ : rot_), base(base_), interleaved(interleaved_) {

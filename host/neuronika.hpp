@@ -259,6 +259,7 @@ enum class Activation { Gelu = 0, GeluTanh = 1, Silu = 2, Sigmoid = 3 };
 class VarDiff;
 namespace nn {
 struct RotaryEmbedding;
+struct Sampler;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -313,6 +314,9 @@ class Var {
     // first `rot` columns of every head rotated by the angles of the row's position, ONE node.  Panics on a shape mismatch or
     // T > max_pos.
     Var rope(const nn::RotaryEmbedding& rotary, int batch, int heads) const;
+    // The next token of every sample of (batch*T, V) logits (ours; semantics at nk_sample_fwd in neuronika_hip.h): a (batch,) value of
+    // ids in f32, drawn from the LAST row of each sample, ONE node, no gradient.  Panics when batch does not divide the rows.
+    Var sample(const nn::Sampler& sampler, int batch) const;
     Var unsqueeze(int axis) const;
     // Pooling over the spatial axes of an (N, C, spatial...) input (ours: the reference has none; semantics in neuronika_hip.h):
     // nd = rank - 2 = the length of `kernel`, `stride` (empty: stride = kernel) and `padding` (empty: zeros); floor mode, dilation 1.
@@ -699,6 +703,24 @@ struct Embedding {
     Embedding(DevicePtr dev, size_t num_embeddings, size_t embedding_dim, long padding_idx = -1, uint64_t seed = 0);
     Embedding(VarDiff weight, long padding_idx = -1);  // a table built elsewhere (deserialised, or shared with another module)
     VarDiff forward(const Var& indices) const;
+};
+
+// Token sampling on the device (ours: the reference has no generation loop; semantics at nk_sample_fwd in neuronika_hip.h): greedy at
+// temperature 0, else temperature, top-k (0: off) and top-p (1: off) in that order and one Philox draw per row.  forward(logits,
+// batch) takes (batch*T, V) logits and returns the (batch,) ids of the last position of every sample as f32 - the form
+// Embedding::forward takes, so a generation loop never leaves the device.  The members are read when forward builds its node; every
+// execution of a node's forward draws at (seed, *offset) and advances `offset`, the counter all nodes of one sampler share - the way
+// the dropout node consumes its calls.  No parameters, no gradient.
+struct Sampler {
+    Sampler(DevicePtr dev, float temperature = 1.0f, int top_k = 0, float top_p = 1.0f, uint64_t seed = 0);
+    DevicePtr dev;
+    float temperature;
+    int top_k;
+    float top_p;
+    uint64_t seed;
+    Shared<uint64_t> offset;
+    Var forward(const Var& logits, int batch) const;
+    Var forward(const VarDiff& logits, int batch) const;  // enters through `.var`: the ids carry no gradient
 };
 
 // Activation modules (ours: the reference has none; `Var / VarDiff::gelu / silu / glu`).  No parameters.

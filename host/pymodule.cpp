@@ -492,6 +492,24 @@ PYBIND11_MODULE(_tape, m) {
              "Rotate the first `rot` columns of every head of a (batch*T, heads*head_dim) value by the angles of positions 0 .. T-1.");
     py::reinterpret_borrow<py::class_<VarDiff>>(m.attr("VarDiff"))
         .def("rope", &VarDiff::rope, py::arg("rotary"), py::arg("batch"), py::arg("heads"));
+    py::class_<nn::Sampler>(nn, "Sampler")
+        .def(py::init<DevicePtr, float, int, float, uint64_t>(), py::arg("dev"), py::arg("temperature") = 1.0f, py::arg("top_k") = 0,
+             py::arg("top_p") = 1.0f, py::arg("seed") = 0,
+             "Token sampling on the device: greedy at temperature 0, else temperature, top-k (0: off) and top-p (1: off) and one Philox "
+             "draw per row at (seed, offset). The members are read when forward builds its node; every execution of a node advances offset.")
+        .def_readwrite("temperature", &nn::Sampler::temperature)
+        .def_readwrite("top_k", &nn::Sampler::top_k)
+        .def_readwrite("top_p", &nn::Sampler::top_p)
+        .def_readwrite("seed", &nn::Sampler::seed)
+        .def_property("offset", [](const nn::Sampler& s) { return *s.offset; }, [](nn::Sampler& s, uint64_t v) { *s.offset = v; },
+                      "the Philox offset the next execution draws at; shared by every node this sampler built")
+        .def("forward", py::overload_cast<const Var&, int>(&nn::Sampler::forward, py::const_), py::arg("logits"), py::arg("batch"),
+             "(batch*T, V) logits -> the (batch,) ids of the last position of every sample, f32, no gradient: what Embedding.forward takes.")
+        // a differentiable input (what the layers return) enters through its data and forward tape
+        .def("forward", py::overload_cast<const VarDiff&, int>(&nn::Sampler::forward, py::const_), py::arg("logits"), py::arg("batch"));
+    py::reinterpret_borrow<py::class_<Var>>(m.attr("Var"))
+        .def("sample", &Var::sample, py::arg("sampler"), py::arg("batch"),
+             "The ids of the last position of every sample of (batch*T, V) logits, drawn by `sampler` on the device.");
     py::class_<nn::MultiheadAttention>(nn, "MultiheadAttention")
         .def(py::init<DevicePtr, int, int, double, uint64_t>(), py::arg("dev"), py::arg("d_model"), py::arg("heads"),
              py::arg("p") = 0.0, py::arg("seed") = 0)

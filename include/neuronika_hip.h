@@ -868,6 +868,36 @@ int nk_rope_bwd(nk_device* dev, float* dx, int lddx, const float* g, int ldg, co
                 int dh, int rot, int max_pos, int interleaved);
 int nk_rope_bwd_assign(nk_device* dev, float* dx, int lddx, const float* g, int ldg, const float* table, const int* start, int B, int T,
                        int NH, int dh, int rot, int max_pos, int interleaved);
+/* ------------------------------------------------------------------ token sampling --
+ * Ours (the reference has no generation loop): the next token of each row of logits - greedy, temperature, top-k (Fan et al. 2018) and
+ * top-p / nucleus (Holtzman et al. 2020) - chosen on the device and written as f32, the form nk_embedding_fwd takes its ids in.
+ * Row r is logits + r*ld, ld >= V (the last of T positions per sample: logits + (T-1)*V, ld = T*V).  ids[r] receives the chosen index
+ * (V <= 2^20 keeps it exact).  logits is never written.  Per row, independently of every other row:
+ *  1. Order.  Tokens are ordered by value; -0 counts as +0; NaN sorts below -inf; equal values: the lower index first.  m is the
+ *     largest value.
+ *  2. Greedy.  temperature == 0 returns the lowest index that holds m.  So does a row whose m is not finite (+inf, or a row of only
+ *     -inf / NaN).  No draw is taken, top_k and top_p are ignored.
+ *  3. Top-k.  top_k <= 0 or top_k >= V turns it off.  Otherwise S = {i : x_i >= the top_k-th largest value}.  Ties at the threshold
+ *     all stay, as in the usual `logits < kth` filter.
+ *  4. Weights.  e_i = exp2f((x_i - m) * c) with c = 1.44269504f / temperature formed once in f32; w_i = (uint64)(e_i * 2^40),
+ *     truncated, for i in S; w_i = 0 for NaN and -inf.  The maximum has w = 2^40 exactly, so W = sum w_i >= 2^40.  All sums are 64-bit
+ *     integer sums: exact and independent of order (V <= 2^20 keeps W < 2^61).
+ *  5. Top-p.  top_p >= 1 turns it off.  Otherwise target = (uint64)((double)top_p * (double)W), at least 1, and the kept set shrinks
+ *     to {i in S : x_i >= t}, t the largest value for which the weights of {i in S : x_i >= t} sum to >= target.  Ties stay again.
+ *     W becomes that sum.
+ *  6. Draw.  One Philox4x32-10 call, counter (lo32(offset), hi32(offset), r, 0x53414D50), key (lo32(seed), hi32(seed)); the fourth
+ *     counter word keeps this stream apart from dropout, whose counters end in 0, 0.  r64 = word1 << 32 | word0, R = mulhi64(r64, W).
+ *     The id is the lowest kept index whose running weight sum in index order exceeds R.  A token of weight 0 is never drawn.
+ * Every decision is an integer comparison: the id of a row depends on its V logits and on (temperature, top_k, top_p, seed, offset, r)
+ * only - not on rows, ld, pointer alignment, the kernel family (16-byte or scalar loads) or whether the row was staged in LDS
+ * (V <= nk_sample_stage_limit(), a compile-time constant; longer rows are re-read from memory by the later passes).
+ * One workgroup per row; integer LDS atomics only; the library allocates nothing in the call.  With temperature > 0 the call refuses
+ * stream capture, as nk_dropout_fwd does (offset is a kernel argument); the greedy form can be captured.
+ * NK_ERR_INVALID, nothing written: a null pointer, rows <= 0, V <= 0 or V > 2^20, ld < V, temperature negative or not finite, top_p
+ * NaN or <= 0. */
+int nk_sample_fwd(nk_device* dev, const float* logits, long long ld, int rows, int V, float* ids, float temperature, int top_k, float top_p,
+                  uint64_t seed, uint64_t offset);
+int nk_sample_stage_limit(void);
 /* ------------------------------------------------------------------ dropout ------------ */
 /* Dropout::forward node/dropout/mod.rs:53-79.  train && 0<p<1: noise ~ Bernoulli(1-p) in
  * {0,1} is (re)drawn from Philox4x32-10(seed, offset) and written to `noise` (f32, like the

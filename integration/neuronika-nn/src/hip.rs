@@ -18,7 +18,7 @@ use std::{cell::{Cell, RefCell}, rc::Rc};
 
 use ndarray::{Array, Dimension, Ix0, Ix1, Ix2, Ix3, Ix4, Ix5, RemoveAxis};
 use neuronika_variable::{
-    hip::{Device, Gate, HipVar, HipVarDiff, KvBuffers, PaddingMode, RotaryTable},
+    hip::{Device, Gate, HipVar, HipVarDiff, KvBuffers, PaddingMode, RotaryTable, SamplerState},
     Reduction,
 };
 use rand::distributions::{Distribution, Uniform};
@@ -473,6 +473,25 @@ impl RotaryEmbedding {
     /// `input`: `(batch * seq, heads * head_dim)` at positions `0 .. seq - 1`.
     pub fn forward(&self, input: HipVarDiff<Ix2>, batch: usize, heads: usize) -> HipVarDiff<Ix2> {
         input.rope(&self.table, batch, heads)
+    }
+}
+
+/// Token sampling on the device (ours; the tested mirror is `nn::Sampler` in `host/neuronika.hpp`): greedy at `temperature == 0`, else
+/// temperature, top-k (`0`: off), top-p (`1.`: off) and one Philox draw per row.  The ids come back as f32 on the device, the form
+/// `Embedding::forward` takes: a generation loop never leaves the device.  No parameters, no gradient.
+pub struct Sampler {
+    pub state: SamplerState,
+}
+
+impl Sampler {
+    pub fn new(temperature: f32, top_k: usize, top_p: f32, seed: u64) -> Self {
+        Self { state: SamplerState::new(temperature, top_k, top_p, seed) }
+    }
+
+    /// `logits`: `(batch * seq, vocab)`; the `(batch,)` ids of the last position of every sample.  A differentiable input enters
+    /// through `HipVarDiff::detached`.
+    pub fn forward(&self, logits: HipVar<Ix2>, batch: usize) -> HipVar<Ix1> {
+        logits.sample(&self.state, batch)
     }
 }
 

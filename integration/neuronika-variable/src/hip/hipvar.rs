@@ -25,6 +25,7 @@ use super::{
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
         decode_chunk, decode_workspace, PackedDecodeAttention,
         rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
+        sample_stage_limit, Sample, SampleParams,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
         ReLUBackward, ReluMask, Softmax, SoftmaxBackward,
         SquaredError, SquaredErrorBackward, Sum, SumBackward, Transpose, TransposeBackward,
@@ -589,6 +590,46 @@ impl HipVar<Ix2> {
         let data = shared(ndarray::Dim([total, heads * dh]), &device);
         let op = PackedDecodeAttention::new(geometry, capacity as i32, self.data, buffers.keys.clone(), buffers.values.clone(), start,
                                             buffers.workspace_for(rows, &device), data.clone(), scale);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+}
+
+/// The settings and the offset counter of a token sampler (ours; semantics at `nk_sample_fwd` in `include/neuronika_hip.h`): greedy at
+/// `temperature == 0`, else temperature, top-k (`0`: off) and top-p (`1.`: off) and one Philox draw per row at `(seed, offset)`.
+/// Every execution of a node built from it advances the shared `offset` (`neuronika_nn::hip::Sampler`).
+#[derive(Clone)]
+pub struct SamplerState {
+    pub temperature: f32,
+    pub top_k: usize,
+    pub top_p: f32,
+    pub seed: u64,
+    pub offset: Rc<Cell<u64>>,
+}
+
+impl SamplerState {
+    pub fn new(temperature: f32, top_k: usize, top_p: f32, seed: u64) -> Self {
+        assert!(temperature >= 0. && temperature.is_finite(), "SamplerState: temperature must be finite and not negative");
+        assert!(top_p > 0., "SamplerState: top_p must be positive");
+        Self { temperature, top_k, top_p, seed, offset: Rc::new(Cell::new(0)) }
+    }
+
+    /// The largest vocabulary whose row the kernel keeps in LDS; longer rows are re-read from memory by the later passes.
+    pub fn stage_limit() -> usize {
+        sample_stage_limit()
+    }
+}
+
+impl HipVar<Ix2> {
+    /// The next token of every sample of `(batch * rows, vocab)` logits: the `(batch,)` ids, as f32, drawn from the LAST row of each
+    /// sample - what `embedding` takes.  ONE node (`nk_sample_fwd`), no gradient.
+    pub fn sample(self, sampler: &SamplerState, batch: usize) -> HipVar<Ix1> {
+        let dim = self.data.borrow().dimension();
+        assert!(batch > 0 && dim[0] > 0 && dim[0] % batch == 0, "sample: rows must be a positive multiple of the batch");
+        assert!(dim[1] > 0 && dim[1] <= 1 << 20, "sample: the vocabulary must be in [1, 2^20]");
+        let data = shared(ndarray::Dim([batch]), &self.device());
+        let params = SampleParams { temperature: sampler.temperature, top_k: sampler.top_k.min(i32::MAX as usize) as i32, top_p: sampler.top_p,
+                                    seed: sampler.seed };
+        let op = Sample::new(params, sampler.offset.clone(), batch as i32, dim[0] / batch, dim[1], self.data, data.clone());
         HipVar::node(data, Rc::new(op), self.history)
     }
 }

@@ -21,6 +21,7 @@ mod pointwise;
 mod pooling;
 mod reduction;
 mod rope;
+mod sample;
 
 pub(crate) use activation::*;
 pub(crate) use attention::*;
@@ -39,6 +40,7 @@ pub(crate) use pointwise::*;
 pub(crate) use pooling::*;
 pub(crate) use reduction::*;
 pub(crate) use rope::*;
+pub(crate) use sample::*;
 
 use std::rc::Rc;
 

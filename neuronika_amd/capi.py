@@ -211,6 +211,8 @@ _SIGS = {
     "nk_rope_fwd": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_rope_bwd": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_rope_bwd_assign": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_sample_fwd": [VP, VP, C.c_longlong, C.c_int, C.c_int, VP, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_uint64],
+    "nk_sample_stage_limit": [],
     "nk_scale_softmax_dropout_fwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_scale_softmax_dropout_bwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_dropout_fwd": [VP, VP, VP, VP, C.c_size_t, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
@@ -996,6 +998,18 @@ def rope_bwd(dev, dx, lddx, g, ldg, table, start, B, T, NH, dh, rot, max_pos, in
     """dx (+)= R^T g: the same pass with the sign of the sine flipped; dx is g legal with assign=True only."""
     fn = lib.nk_rope_bwd_assign if assign else lib.nk_rope_bwd
     check(fn(dev.h, _p(dx), lddx, _p(g), ldg, _p(table), _p(start), B, T, NH, dh, rot, max_pos, int(bool(interleaved))))
+
+
+def sample_fwd(dev, logits, ld, rows, V, ids, temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0):
+    """ids[r] = the token drawn from row r (logits + r*ld, V logits) as f32: greedy at temperature 0, else temperature, top-k and
+    top-p in that order and ONE Philox draw per row at (seed, offset, r).  `view_offset` enters at the last position of a sample."""
+    check(lib.nk_sample_fwd(dev.h, _p(logits), int(ld), int(rows), int(V), _p(ids), float(temperature), int(top_k), float(top_p),
+                            int(seed), int(offset)))
+
+
+def sample_stage_limit() -> int:
+    """The largest V whose row the sampling kernel keeps in LDS: a constant of the library."""
+    return int(lib.nk_sample_stage_limit())
 
 
 def attention_bwd(dev, dQ, dK, dV, dS, dropped, dO, out, scores, stats, mask_bits, Q, K, V, B, S, H, dh, scale, p, train=True,
