@@ -97,11 +97,23 @@ const char* nk_version(void);
  *                          never its tap-plane kernel (by rule only with 128 | output channels and eight or more blocks per CU) / 1 whenever the shape
  *                          allows (one group, even input extents, padding 0 or 1 alike on both axes, 64 | input channels, 16 | output
  *                          channels) / 2, 3: the same with narrow (two waves, 64 channels) / wide (four waves, 128 channels) blocks forced
+ *   NK_TUNE_GEMM_WINDOW    values[0] = 0 rule / W > 0: the aligned 128 x 128 GEMM launches (NN, NT, TN, 256-thread blocks) load their
+ *                          tiles through buffer descriptors - 32-bit byte offsets from the block's tile origin - only while the window
+ *                          a tile spans in EACH operand is at most W bytes: (127 ld + K) * 4 for an operand whose k runs along its
+ *                          rows, (K ld + 128) * 4 for one whose k runs down its columns.  Rule: W = 2^31 - 1.  A launch above the limit
+ *                          takes the kernels' 64-bit pointer path; both give the same bits.  A small W lets a test reach that fallback
+ *                          with small matrices.
  * For schedule sweeps (benchmarks/ab_*.py) and the tests that pit one schedule against another bit for bit; results never
  * depend on them beyond summation order (split-K, chain length, algorithm). */
 enum { NK_TUNE_GEMM_FORCE = 0, NK_TUNE_GEMM_KPAIR = 1, NK_TUNE_ATTENTION_OCC = 2, NK_TUNE_GEMM_PAIR = 3, NK_TUNE_CONV_NARROW = 4,
-       NK_TUNE_CONV_WINOGRAD = 5, NK_TUNE_GEMM_CHAIN = 6, NK_TUNE_CONV_S2DX = 7 };
+       NK_TUNE_CONV_WINOGRAD = 5, NK_TUNE_GEMM_CHAIN = 6, NK_TUNE_CONV_S2DX = 7, NK_TUNE_GEMM_WINDOW = 8 };
 int nk_dev_tune(nk_device* dev, int knob, const int* values, int n);
+/* How many GEMM launches on this handle took the buffer-addressed path of their kernel so far (NK_TUNE_GEMM_WINDOW decides per launch). */
+int nk_gemm_buffer_launches(nk_device* dev, uint64_t* count);
+/* The num_records (bytes) of the buffer descriptor a block on that path builds for one operand: the window of its R-row tile
+ * at (row0, k0) up to k = kend, clipped to the operand's extent (`rows` rows or columns, leading dimension ld, floats).
+ * k_contiguous: element (row, k) at X[row * ld + k], else at X[k * ld + row].  Host arithmetic only, shared with the kernels. */
+long long nk_gemm_buffer_records(int k_contiguous, int R, long long ld, int row0, int rows, int k0, int kend);
 /* How many convolution launches on this handle took the Winograd F(2x2, 3x3) kernels so far (forward + input gradient; the rule
  * of NK_TUNE_CONV_WINOGRAD decides per launch).  For harnesses that must say which algorithm produced a time: bench.py quotes the
  * C3 roofline on the DIRECT algorithmic flops of node/convolution/mod.rs:85-123,146-189 and states beside it what was executed. */

@@ -242,6 +242,8 @@ _SIGS = {
     "nk_dev_tune": [VP, C.c_int, C.POINTER(C.c_int), C.c_int],
     "nk_device_set_busy_slots": [VP, C.c_int],
     "nk_conv_winograd_launches": [VP, C.POINTER(C.c_uint64)],
+    "nk_gemm_buffer_launches": [VP, C.POINTER(C.c_uint64)],
+    "nk_gemm_buffer_records": [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_comm_destroy": [VP],
     "nk_allreduce_sum_async": [VP, VP, C.c_size_t, VP],
     "nk_allreduce_sum_group_async": [VP, C.POINTER(VP), C.POINTER(C.c_size_t), C.c_int, VP],
@@ -250,7 +252,7 @@ _SIGS = {
     "nk_comm_size": [VP],
 }
 _RESTYPES = {"nk_last_error": C.c_char_p, "nk_version": C.c_char_p, "nk_stream_compute": VP, "nk_stream_comm": VP,
-             "nk_attention_decode_workspace": C.c_size_t}
+             "nk_attention_decode_workspace": C.c_size_t, "nk_gemm_buffer_records": C.c_longlong}
 EXPORTED = tuple(_SIGS)
 
 for _name, _args in _SIGS.items():
@@ -311,6 +313,7 @@ class Event:
 
 
 TUNE_GEMM_FORCE, TUNE_GEMM_KPAIR, TUNE_ATTENTION_OCC, TUNE_GEMM_PAIR, TUNE_CONV_NARROW, TUNE_CONV_WINOGRAD, TUNE_GEMM_CHAIN, TUNE_CONV_S2DX = 0, 1, 2, 3, 4, 5, 6, 7   # include/neuronika_hip.h: nk_dev_tune knobs
+TUNE_GEMM_WINDOW = 8
 
 
 class Device:
@@ -328,7 +331,7 @@ class Device:
         # variables; it is THIS harness that reads them and calls nk_dev_tune - the library itself reads none.
         for var, knob in (("NK_GEMM_FORCE", TUNE_GEMM_FORCE), ("NK_GEMM_KPAIR", TUNE_GEMM_KPAIR), ("NK_ATTN_OCC", TUNE_ATTENTION_OCC),
                           ("NK_GEMM_PAIR", TUNE_GEMM_PAIR), ("NK_CONV_NARROW", TUNE_CONV_NARROW), ("NK_CONV_WINOGRAD", TUNE_CONV_WINOGRAD),
-                          ("NK_GEMM_CHAIN", TUNE_GEMM_CHAIN), ("NK_CONV_S2DX", TUNE_CONV_S2DX)):
+                          ("NK_GEMM_CHAIN", TUNE_GEMM_CHAIN), ("NK_CONV_S2DX", TUNE_CONV_S2DX), ("NK_GEMM_WINDOW", TUNE_GEMM_WINDOW)):
             if os.environ.get(var):
                 self.tune(knob, os.environ[var])
 
@@ -364,6 +367,17 @@ class Device:
 
     def conv_narrow(self, cost=None):
         self.tune(TUNE_CONV_NARROW, cost)
+
+    def gemm_window(self, nbytes=None):
+        """NK_TUNE_GEMM_WINDOW: None / 0 the rule (2^31 - 1), W > 0: aligned 128 x 128 GEMM launches take the buffer-addressed
+        kernels only while a tile's window in each operand is at most W bytes (above it: the 64-bit pointer path, same bits)"""
+        self.tune(TUNE_GEMM_WINDOW, nbytes)
+
+    def gemm_buffer_launches(self) -> int:
+        """nk_gemm_buffer_launches: GEMM launches on this handle that took the buffer-addressed path so far."""
+        n = C.c_uint64(0)
+        check(lib.nk_gemm_buffer_launches(self.h, C.byref(n)))
+        return int(n.value)
 
     def conv_winograd_launches(self) -> int:
         """nk_conv_winograd_launches: convolution launches on this handle that took the Winograd kernels so far."""
@@ -522,6 +536,11 @@ KERNEL_SGEMM, KERNEL_CONV, KERNEL_ATTENTION = 0, 1, 2
 # ------------------------------------------------------------------------------------------------
 # thin per-entry-point wrappers (argument order = C ABI order)
 # ------------------------------------------------------------------------------------------------
+
+def gemm_buffer_records(k_contiguous, R, ld, row0, rows, k0, kend) -> int:
+    """nk_gemm_buffer_records: num_records (bytes) of the descriptor a block builds for the R-row tile at (row0, k0) up to kend"""
+    return int(lib.nk_gemm_buffer_records(int(bool(k_contiguous)), R, ld, row0, rows, k0, kend))
+
 
 def sgemm(dev, ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, Cm, ldc):
     check(lib.nk_sgemm(dev.h, int(ta), int(tb), M, N, K, alpha, A.p, lda, B.p, ldb, beta, Cm.p, ldc))

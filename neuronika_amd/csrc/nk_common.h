@@ -51,6 +51,8 @@ struct nk_device {
     int tune_conv_wino_stagger = -1;         // staggered start of the Winograd blocks: -1 rule (a quarter of a tile block's MFMA time), 0 off, > 0 shader clocks
     int tune_conv_winograd = -1;             // 3x3 s1 d1 g1 forward / input gradient: -1 rule, 0 never Winograd, 1 whenever the shape allows
     int tune_attn_occ = 0;                   // attention forward: 2 = size the register budget for two blocks per CU
+    int tune_gemm_window = 0;                // buffer-addressed GEMM loads: largest operand window of a tile in bytes, 0 = the rule (2^31 - 1)
+    unsigned long long gemm_buf_launches = 0;  // GEMM launches that took the buffer-addressed kernels (nk_gemm_buffer_launches)
     // bench instrumentation (nk_profile_begin/end)
     bool prof_on = false;
     bool prof_window = false;           // between nk_profile_begin and the first nk_profile_end

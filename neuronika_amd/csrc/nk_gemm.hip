@@ -8,6 +8,7 @@
 // per k-tile), XCD-aware tile order, split-K with a deterministic second pass when M*N alone
 // cannot fill the chip.
 #include "nk_mma.h"
+#include <type_traits>
 #include <utility>
 
 using namespace nkmma;
@@ -30,6 +31,7 @@ struct GemmArgs {
     const float* B;
     float* C;
     int M, N, K;
+    int buf;          // sgemm_kernel, aligned 128 x 128, 256 threads, not TT: buffer-addressed tile loads (gemm_plan; sits in the padding in front of lda)
     long long lda, ldb, ldc;
     float alpha, beta;
     const float* bias;  // optional column bias (length N) added in the epilogue: C = alpha*A.B + bias + beta*C
@@ -148,8 +150,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[T
 // then MFMAs -> barrier, instead of MFMAs -> wait for this trip's own loads -> 8 LDS writes -> barrier.  Unrolled by
 // two so that P / Q and the LDS buffers are static (even tiles in buf0, odd tiles in buf1).
 // `skew` (k-pair blocks, group 1): the first half of a k-tile's MFMAs is issued BEFORE the trip's staging stores.
-template <bool AKC, bool BKC, bool ALIGNED, int TI, int TJ, int KG>
-__device__ __forceinline__ void gemm_loop_lookahead2(TileLoader<AKC, 64 * TI>& la, TileLoader<BKC, 64 * TJ>& lb, f32x16 (&acc)[TI][TJ],
+// (LA / LB: TileLoader or, on sgemm_kernel's buffer-addressed path, BufTileLoader - deduced)
+template <bool AKC, bool BKC, bool ALIGNED, int TI, int TJ, int KG, class LA, class LB>
+__device__ __forceinline__ void gemm_loop_lookahead2(LA& la, LB& lb, f32x16 (&acc)[TI][TJ],
                                                      float* smem, int nt, bool skew, int t, int wr, int wc, int lane) {
     constexpr int BM = 64 * TI, BN = 64 * TJ;
     constexpr int TA_FLOATS = tile_floats<AKC, BM>(), STAGE = TA_FLOATS + tile_floats<BKC, BN>();
@@ -235,6 +238,20 @@ __global__ __launch_bounds__(NT * KG, (min_waves<TI, TJ, !TA && TB>())) void sge
 #define NK_GEMM_BX blockIdx.x
 #define NK_GEMM_NBX gridDim.x
 #define NK_GEMM_SPLIT blockIdx.y
+    // The aligned 128 x 128 kernels of 256-thread blocks (NN, NT, TN) hold the block program twice: with buffer-addressed tile
+    // loads (BufTileLoader, nk_mma.h) for launches whose operand windows fit 32-bit byte offsets (gemm_plan sets `p.buf`, block-
+    // uniform), and with the 64-bit pointer loader for the rest.  The same MFMA feeding order and chains: bit-identical.  The
+    // buffer form frees the per-lane pointers of the k-loop.  Every other instantiation keeps the code it had.
+    if constexpr (ALIGNED && TI == 2 && TJ == 2 && KG == 1 && !(TA && TB)) {
+        if (p.buf) {
+            {
+                constexpr bool BUF = true;
+#include "nk_gemm_body.h"
+            }
+            return;
+        }
+    }
+    constexpr bool BUF = false;
 #include "nk_gemm_body.h"
 #undef NK_GEMM_BX
 #undef NK_GEMM_NBX
@@ -244,6 +261,7 @@ __global__ __launch_bounds__(NT * KG, (min_waves<TI, TJ, !TA && TB>())) void sge
 // one problem of sgemm_pair_kernel: the same block program for block `bx` of `nbx`
 template <bool TA, bool TB, bool ALIGNED, int TI, int TJ, int KG, bool EPX>
 __device__ __forceinline__ void sgemm_body(const GemmArgs& p, float* smem_all, int bx, int nbx) {
+    constexpr bool BUF = false;
 #define NK_GEMM_BX bx
 #define NK_GEMM_NBX nbx
 #define NK_GEMM_SPLIT blockIdx.y
@@ -255,6 +273,7 @@ __device__ __forceinline__ void sgemm_body(const GemmArgs& p, float* smem_all, i
 // ... and with the block's range of the reduction passed in (sgemm_tail_kernel)
 template <bool TA, bool TB, bool ALIGNED, int TI, int TJ, int KG, bool EPX>
 __device__ __forceinline__ void sgemm_body_split(const GemmArgs& p, float* smem_all, int bx, int nbx, int split_no) {
+    constexpr bool BUF = false;
 #define NK_GEMM_BX bx
 #define NK_GEMM_NBX nbx
 #define NK_GEMM_SPLIT split_no
@@ -414,6 +433,7 @@ struct GemmPlan {
     GemmArgs p;
     int ti, tj, kg, nbatch;
     bool aligned, empty;
+    bool buf;  // a launch of its own takes sgemm_kernel's buffer-addressed path (p.buf is set from it at the launch)
 };
 
 static int gemm_plan(nk_device* dev, int transA, int transB, int M, int N, int K, float alpha,
@@ -573,6 +593,16 @@ static int gemm_plan(nk_device* dev, int transA, int transB, int M, int N, int K
         if (can && want) kg = 2;
         if (kpair_tune == 1) p.kskew = 0;
     }
+    // Buffer-addressed tile loads (sgemm_kernel's `p.buf` path): the aligned 128 x 128 launch of 256-thread blocks, NN / NT / TN, when the
+    // window a tile spans in EACH operand - from the shape alone, the whole K - fits the limit (2^31 - 1 bytes by rule: the
+    // loads' 32-bit voffset + soffset never wraps and num_records is a positive int; NK_TUNE_GEMM_WINDOW lowers it so that a
+    // test reaches the pointer kernels with small matrices).  Same bits either way.
+    {
+        const long long limit = dev->tune_gemm_window > 0 ? dev->tune_gemm_window : 0x7fffffffLL;
+        const long long wa = !transA ? (127 * (long long)lda + K) * 4 : ((long long)K * lda + 128) * 4;
+        const long long wb = transB ? (127 * (long long)ldb + K) * 4 : ((long long)K * ldb + 128) * 4;
+        plan->buf = aligned && ti == 2 && tj == 2 && kg == 1 && !(transA && transB) && wa <= limit && wb <= limit;
+    }
     plan->p = p; plan->ti = ti; plan->tj = tj; plan->kg = kg; plan->aligned = aligned;
     return NK_OK;
 }
@@ -695,6 +725,8 @@ static int gemm_impl(nk_device* dev, int transA, int transB, int M, int N, int K
     }
     rc = nk_prof_start(dev, NK_KERNEL_SGEMM, 2.0 * M * N * (double)K * nbatch);
     if (rc) return rc;
+    p.buf = plan.buf ? 1 : 0;  // (the pair and tail kernels launch a plan's arguments with buf = 0: they hold the pointer loader only)
+    if (plan.buf) ++dev->gemm_buf_launches;
     if (!transA && !transB) rc = launch<false, false>(dev, p, nbatch, aligned, ti, tj, kg);
     else if (!transA && transB) rc = launch<false, true>(dev, p, nbatch, aligned, ti, tj, kg);
     else if (transA && !transB) rc = launch<true, false>(dev, p, nbatch, aligned, ti, tj, kg);
@@ -830,6 +862,15 @@ static int gemm_pair_impl(nk_device* dev, const GemmProblem& a, const GemmProble
 }
 
 extern "C" {
+
+int nk_gemm_buffer_launches(nk_device* dev, uint64_t* count) {
+    NK_CHECK(dev != nullptr && count != nullptr, "bad nk_gemm_buffer_launches arguments");
+    *count = dev->gemm_buf_launches;
+    return NK_OK;
+}
+long long nk_gemm_buffer_records(int k_contiguous, int R, long long ld, int row0, int rows, int k0, int kend) {
+    return tile_window_bytes(k_contiguous != 0, R, ld, row0, rows, k0, kend);
+}
 
 int nk_sgemm(nk_device* dev, int transA, int transB, int M, int N, int K, float alpha, const float* A,
              int lda, const float* B, int ldb, float beta, float* C, int ldc) {

@@ -5,7 +5,7 @@
 // that differs between the two uses is where a block's position in the tile sequence comes from:
 //   NK_GEMM_BX / NK_GEMM_NBX   this block's index among the blocks of ITS problem / their number
 //   NK_GEMM_SPLIT              which range of the reduction it takes (blockIdx.y, except in sgemm_tail_kernel's second problem)
-// In scope: template parameters TA, TB, ALIGNED, TI, TJ, KG, EPX; `const GemmArgs& p`; `float* smem_all` (the block's LDS).
+// In scope: template parameters (or constants) TA, TB, ALIGNED, TI, TJ, KG, EPX, BUF (buffer-addressed loader); `const GemmArgs& p`; `float* smem_all` (the block's LDS).
 // grid.z = batch in every use.  Not a stand-alone header.
     constexpr int BM = 64 * TI, BN = 64 * TJ;
     constexpr bool AKC = !TA;  // A (M x K): k-contiguous unless stored transposed
@@ -42,8 +42,8 @@
 
     f32x16 acc[TI][TJ];
     acc_zero<TI, TJ>(acc);
-    TileLoader<AKC, BM> la;
-    TileLoader<BKC, BN> lb;
+    std::conditional_t<BUF, BufTileLoader<AKC, BM>, TileLoader<AKC, BM>> la;
+    std::conditional_t<BUF, BufTileLoader<BKC, BN>, TileLoader<BKC, BN>> lb;
     // Two-k-tile look-ahead: aligned problems only (the guarded loader's state does not fit next to P and Q), every
     // layout, from the per-layout / per-tile k-tile threshold the host passes in `pf2_min` (rules and their same-box
     // sweeps: gemm_impl).  That loop handles exactly ONE tile: gemm_impl sets chunk = 1 whenever nt >= pf2_min.

@@ -83,7 +83,11 @@ __device__ __forceinline__ void stage_store(float* Xs, const Stage<R / 32>& r, i
 
 // Dense-matrix loader.  Element (row,k) of the operand lies at KC: X[row*ld + k],
 // RC: X[k*ld + row].  The fast path keeps ONE wave-uniform tile pointer (advanced per k-tile)
-// plus per-thread 32-bit element offsets, so each load is `global_load_dwordx4 v, voff, s[base]`.
+// plus per-thread 32-bit element offsets.  The source asks for `global_load_dwordx4 v, voff, s[base]`; what the compiler
+// emits in the GEMM k-loops is a per-lane 64-bit pointer per load (`v_lshl_add_u64 v[a:a+1], v[o:o+1], 0, s[base]`, then
+// `global_load_dwordx4 v, v[a:a+1], off`): two VGPRs of widened offset and two of current pointer per load, live across the
+// whole loop.  The convolution kernels and the unaligned / 64-wide GEMMs keep this loader; the aligned 128 x 128 GEMM takes
+// BufTileLoader below (a second copy of its block program, chosen per launch) where the host finds that the tile's window fits 32-bit offsets.
 template <bool KC, int R>
 struct TileLoader {
     const float* base;  // &X[tile origin] for the current k-tile (wave-uniform)
@@ -151,6 +155,54 @@ struct TileLoader {
             base += kstep;
             k0 += BK;
         }
+        return r;
+    }
+};
+
+// ---- buffer-addressed loader (aligned problems, the 128 x 128 GEMM) ------------------------------------------------------
+// Bytes of the window an R-row tile at (row0, k0) spans in its operand up to k = kend, measured from the tile's origin and
+// clipped to the operand's extent (`rows` rows).  This is the descriptor's num_records: a byte offset at or past it reads zero
+// instead of touching memory.  A whole tile's window always lies inside the extent, so the clip only matters for a caller that
+// breaks the loader's contract.  Shared by the kernels, the host's window rule and nk_gemm_buffer_records.
+__host__ __device__ inline long long tile_window_bytes(bool kc, int R, long long ld, int row0, int rows, int k0, int kend) {
+    const long long klen = kend - k0;
+    const long long win = kc ? ((R - 1) * ld + klen) * 4 : ((klen - 1) * ld + R) * 4;
+    const long long ext = kc ? ((rows - 1 - row0) * ld + klen) * 4 : ((klen - 1) * ld + (rows - row0)) * 4;
+    const long long b = win < ext ? win : ext;
+    return klen <= 0 || b < 0 ? 0 : b;
+}
+
+// Same interface as TileLoader<KC, R>::load<true>.  One descriptor per operand, based at the block's tile origin (SGPRs); the
+// four per-thread BYTE offsets are the only VGPR address state; the k advance is a scalar byte count in the loads' soffset
+// operand: `buffer_load_dwordx4 v, voff, s[rsrc], s_koff offen`.  The host (gemm_plan) takes this loader only when the window
+// fits 31 bits, so voffset + soffset never wraps.  The hardware checks voffset against num_records; soffset is the loader's own
+// count of whole k-tiles below kend.
+template <bool KC, int R>
+struct BufTileLoader {
+    __amdgpu_buffer_rsrc_t rs;
+    unsigned koff, kstep;  // bytes from the tile origin to the current k-tile / per k-tile (wave-uniform)
+    unsigned o0, o1, o2, o3;
+
+    __device__ __forceinline__ void init(const float* X_, long long ld_, int row0_, int k0_, int rows_, int kend_, int t) {
+        const float* origin = KC ? X_ + (long long)row0_ * ld_ + k0_ : X_ + (long long)k0_ * ld_ + row0_;
+        rs = __builtin_amdgcn_make_buffer_rsrc((void*)origin, 0, (int)tile_window_bytes(KC, R, ld_, row0_, rows_, k0_, kend_), 0x00020000);
+        koff = 0;
+        kstep = KC ? BK * 4u : (unsigned)(BK * ld_) * 4u;
+        o0 = TileLoader<KC, R>::off(t, ld_) * 4u; o1 = TileLoader<KC, R>::off(t + NT, ld_) * 4u;
+        o2 = TileLoader<KC, R>::off(t + 2 * NT, ld_) * 4u; o3 = TileLoader<KC, R>::off(t + 3 * NT, ld_) * 4u;
+    }
+    // loads the current k-tile and advances to the next one
+    template <bool ALIGNED>
+    __device__ __forceinline__ Stage<R / 32> load(int) {
+        static_assert(ALIGNED, "the buffer-addressed loader has no guarded path");
+        Stage<R / 32> r;
+        r.v0 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, o0, koff, 0));
+        r.v1 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, o1, koff, 0));
+        if constexpr (R == 128) {
+            r.v2 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, o2, koff, 0));
+            r.v3 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, o3, koff, 0));
+        }
+        koff += kstep;
         return r;
     }
 };

@@ -228,6 +228,10 @@ int nk_dev_tune(nk_device* dev, int knob, const int* values, int n) {
             NK_CHECK(n <= 1 && (n == 0 || values[0] == 0 || values[0] == 2), "NK_TUNE_ATTENTION_OCC: 0 or 2");
             dev->tune_attn_occ = n ? values[0] : 0;
             return NK_OK;
+        case NK_TUNE_GEMM_WINDOW:
+            NK_CHECK(n <= 1 && (n == 0 || values[0] >= 0), "NK_TUNE_GEMM_WINDOW: 0 (rule) or a window limit in bytes");
+            dev->tune_gemm_window = n ? values[0] : 0;
+            return NK_OK;
     }
     nk_set_error("unknown tuning knob %d", knob);
     return NK_ERR_INVALID;
