@@ -6,6 +6,7 @@ K and V per token instead of the causal forward over the whole prefix.
 
     python examples/generate.py [new_tokens]      # needs an MI355X; prints the prompt and the generated ids
     python examples/generate.py [new_tokens] --rope   # rotary positions: no position table, one shared RotaryEmbedding on every block
+    python examples/generate.py [new_tokens] --rmsnorm    # the three LayerNorms become nn.RMSNorm (no centring, no bias: LLaMA's block)
     python examples/generate.py [new_tokens] --device-sample [--temperature 0.8] [--top-k 8] [--top-p 0.95] [--seed 1]
                                                       # the loop stays on the device: `nn.Sampler` draws the next ids from the logits
                                                       # where the head left them, the ids Var feeds `Embedding.forward`, and the host
@@ -27,8 +28,9 @@ VOCAB, D_MODEL, HEADS, LAYERS, CONTEXT = 64, 64, 2, 2, 64
 
 
 class Block:
-    def __init__(self, nk, dev, seed, rope=None):
-        self.ln1, self.ln2 = nk.nn.LayerNorm(dev, [D_MODEL]), nk.nn.LayerNorm(dev, [D_MODEL])
+    def __init__(self, nk, dev, seed, rope=None, norm=None):
+        norm = norm or nk.nn.LayerNorm
+        self.ln1, self.ln2 = norm(dev, [D_MODEL]), norm(dev, [D_MODEL])
         self.mha = nk.nn.MultiheadAttention(dev, D_MODEL, HEADS, 0.0, seed)
         self.mha.causal = True
         self.mha.drop.eval()
@@ -49,14 +51,15 @@ class Block:
 
 
 class Decoder:
-    def __init__(self, nk, dev, rope=False):
+    def __init__(self, nk, dev, rope=False, rmsnorm=False):
         self.nk, self.dev = nk, dev
+        norm = nk.nn.RMSNorm if rmsnorm else nk.nn.LayerNorm
         self.tok, self.pos = nk.nn.Embedding(dev, VOCAB, D_MODEL, seed=1), nk.nn.Embedding(dev, CONTEXT, D_MODEL, seed=2)
         # rotary mode: the queries and keys of every layer are rotated by their position (at lens[b] + t in a step, so the caches
         # hold rotated keys) and nothing is added to the token embedding
         self.rope = nk.nn.RotaryEmbedding(dev, D_MODEL // HEADS, CONTEXT) if rope else None
-        self.blocks = [Block(nk, dev, 100 * (i + 1), self.rope) for i in range(LAYERS)]
-        self.ln, self.head = nk.nn.LayerNorm(dev, [D_MODEL]), nk.nn.Linear(dev, D_MODEL, VOCAB, 7)
+        self.blocks = [Block(nk, dev, 100 * (i + 1), self.rope, norm) for i in range(LAYERS)]
+        self.ln, self.head = norm(dev, [D_MODEL]), nk.nn.Linear(dev, D_MODEL, VOCAB, 7)
 
     def embed(self, ids, first, shape=None):
         """ids (batch, T) at positions first .. first + T - 1 -> (batch * T, d_model); a device Var of batch * T ids comes with its
@@ -110,11 +113,11 @@ def generate_on_device(nk, dev, model, prompt, new_tokens, caches, temperature, 
     return ids, worst
 
 
-def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=0, top_p=1.0, seed=0):
+def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=0, top_p=1.0, seed=0, rmsnorm=False):
     import neuronika_amd
     nk = neuronika_amd.tape
     dev = nk.Device(0)
-    model = Decoder(nk, dev, rope)
+    model = Decoder(nk, dev, rope, rmsnorm)
     prompt = np.array([[3, 14, 15, 9, 26, 5, 35, 8]])
     batch, n = prompt.shape
     assert n + new_tokens <= CONTEXT
@@ -140,10 +143,11 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("new_tokens", nargs="?", type=int, default=16)
     ap.add_argument("--rope", action="store_true", help="rotary positions instead of the learned position table")
+    ap.add_argument("--rmsnorm", action="store_true", help="nn.RMSNorm in place of the three nn.LayerNorm")
     ap.add_argument("--device-sample", action="store_true", help="draw the next ids on the device (nn.Sampler); the host reads them once")
     ap.add_argument("--temperature", type=float, default=0.0, help="with --device-sample: 0 = greedy")
     ap.add_argument("--top-k", type=int, default=0, help="with --device-sample: 0 = off")
     ap.add_argument("--top-p", type=float, default=1.0, help="with --device-sample: 1 = off")
     ap.add_argument("--seed", type=int, default=0, help="with --device-sample: the Philox key of the draws")
     a = ap.parse_args()
-    main(a.new_tokens, rope=a.rope, device_sample=a.device_sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed)
+    main(a.new_tokens, rope=a.rope, device_sample=a.device_sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, rmsnorm=a.rmsnorm)

@@ -1257,6 +1257,85 @@ VarDiff layer_norm_diff(const Var& x, const Shared<Gradient>& dx, const History<
     return VarDiff::node(std::move(var), grad, entry(bw, grad), std::move(h));
 }
 
+// RMS normalisation over the trailing dimensions (ours; the reference has no such node): x read as (rows, dim).  The forward node
+// owns `stats` = per-row rstd, which the backward node reads; the no-gradient form keeps none.
+struct RmsNormFwd : Forward {
+    Shared<HipArray> x, gamma, y, stats;  // gamma null: no weight; stats null: nothing kept for a backward pass
+    long long rows;
+    int dim;
+    double eps;
+    void forward() const override {
+        check(nk_rms_norm_fwd(D(x), x->ptr(), gamma ? gamma->ptr() : nullptr, y->ptr(), stats ? stats->ptr() : nullptr, rows, dim, eps));
+    }
+};
+// ONE backward entry for up to two gradients, each written only if that operand is differentiable, each through its own
+// first-writer-assigns state.
+struct RmsNormBwd : Backward {
+    Shared<Gradient> dx, dgamma, g;  // either target may be null
+    Shared<HipArray> x, gamma, stats;
+    long long rows;
+    int dim;
+    void backward() const override {
+        const HipArray& G = g->borrow();
+        nk_device* dev = D(x);
+        if (dgamma) {
+            bool assign = false;
+            HipArray& d = dgamma->borrow_first_write(assign);
+            check((assign ? nk_rms_norm_bwd_gamma_assign : nk_rms_norm_bwd_gamma)(dev, d.ptr(), G.ptr(), x->ptr(), stats->ptr(), rows, dim));
+        }
+        if (dx) {
+            bool assign = false;
+            HipArray& d = dx->borrow_first_write(assign);
+            check((assign ? nk_rms_norm_bwd_assign : nk_rms_norm_bwd)(dev, d.ptr(), G.ptr(), x->ptr(), gamma ? gamma->ptr() : nullptr,
+                                                                      stats->ptr(), rows, dim));
+        }
+    }
+    void targets(std::vector<const Gradient*>& out) const override {
+        if (dgamma) out.push_back(dgamma.get());
+        if (dx) out.push_back(dx.get());
+    }
+};
+
+Shared<RmsNormFwd> rms_norm_fwd_node(const Var& x, const Var* gamma, const Shape& ns, double eps, bool keep_stats) {
+    if (gamma && gamma->shape() != ns) panic("rms_norm: gamma must have the normalised shape");
+    if (!(eps >= 0.0) || !std::isfinite(eps)) panic("rms_norm: eps must be finite and not negative");
+    auto n = std::make_shared<RmsNormFwd>();
+    if (ns.empty() || ns.size() > x.shape().size() || !std::equal(ns.rbegin(), ns.rend(), x.shape().rbegin()))
+        panic("rms_norm: normalized_shape must equal the trailing dimensions of the input");
+    n->dim = layer_norm_dim(x.shape(), ns);
+    n->rows = (long long)(x.data->len() / (size_t)n->dim);
+    if (keep_stats && n->rows > (1ll << 30)) panic("rms_norm: too many rows");
+    n->x = x.data; n->gamma = gamma ? gamma->data : nullptr;
+    n->y = zeros_like(x.data, x.shape());
+    if (keep_stats) n->stats = zeros_like(x.data, Shape{(int)n->rows});
+    n->eps = eps;
+    return n;
+}
+Var rms_norm_var(const Var& x, const Var* gamma, const Shape& ns, double eps) {
+    History<ForwardEntry> h = x.history;
+    if (gamma) h.merge(gamma->history);
+    auto n = rms_norm_fwd_node(x, gamma, ns, eps, false);
+    auto y = n->y;
+    return Var::node(y, n, std::move(h));
+}
+// x and gamma with their gradients and tapes where differentiable (null otherwise); at least one gradient is not null
+VarDiff rms_norm_diff(const Var& x, const Shared<Gradient>& dx, const History<BackwardEntry>* hx, const Var* gamma,
+                      const Shared<Gradient>& dgamma, const History<BackwardEntry>* hg, const Shape& ns, double eps) {
+    History<ForwardEntry> fh = x.history;
+    if (gamma) fh.merge(gamma->history);
+    auto n = rms_norm_fwd_node(x, gamma, ns, eps, true);
+    auto y = n->y;
+    Var var = Var::node(y, n, std::move(fh));
+    History<BackwardEntry> h;
+    if (hx) h = *hx;
+    if (hg) h.merge(*hg);
+    auto grad = std::make_shared<Gradient>(var.device(), var.shape());
+    auto bw = std::make_shared<RmsNormBwd>();
+    bw->dx = dx; bw->dgamma = dgamma; bw->g = grad;
+    bw->x = x.data; bw->gamma = n->gamma; bw->stats = n->stats; bw->rows = n->rows; bw->dim = n->dim;
+    return VarDiff::node(std::move(var), grad, entry(bw, grad), std::move(h));
+}
+
 // Batch normalisation (ours; the reference has no such node): x read as (N, C, L), L the product of the extents behind the channel
 // axis.  The forward node reads `status` each time it runs on the host (as Dropout's does): training normalises with the batch
 // statistics and updates the running ones in place, inference normalises with the running ones.  Without running statistics the
@@ -1764,6 +1843,11 @@ Var Var::layer_norm(const Shape& normalized_shape, double eps) const { return la
 VarDiff Var::layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps) const {
     return layer_norm_diff(*this, nullptr, nullptr, &gamma.var, gamma.grad, &gamma.history, &beta.var, beta.grad, &beta.history, gamma.shape(), eps);
 }
+Var Var::rms_norm(const Var& gamma, double eps) const { return rms_norm_var(*this, &gamma, gamma.shape(), eps); }
+Var Var::rms_norm(const Shape& normalized_shape, double eps) const { return rms_norm_var(*this, nullptr, normalized_shape, eps); }
+VarDiff Var::rms_norm(const VarDiff& gamma, double eps) const {
+    return rms_norm_diff(*this, nullptr, nullptr, &gamma.var, gamma.grad, &gamma.history, gamma.shape(), eps);
+}
 Var Var::batch_norm(const Var* gamma, const Var* beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
                     Shared<bool> status) const {
     return batch_norm_var(*this, gamma, beta, running_mean, running_var, momentum, eps, std::move(status));
@@ -2248,6 +2332,15 @@ VarDiff VarDiff::layer_norm(const Var& gamma, const Var& beta, double eps) const
 VarDiff VarDiff::layer_norm(const Shape& normalized_shape, double eps) const {
     return layer_norm_diff(var, grad, &history, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, normalized_shape, eps);
 }
+VarDiff VarDiff::rms_norm(const VarDiff& gamma, double eps) const {
+    return rms_norm_diff(var, grad, &history, &gamma.var, gamma.grad, &gamma.history, gamma.shape(), eps);
+}
+VarDiff VarDiff::rms_norm(const Var& gamma, double eps) const {
+    return rms_norm_diff(var, grad, &history, &gamma, nullptr, nullptr, gamma.shape(), eps);
+}
+VarDiff VarDiff::rms_norm(const Shape& normalized_shape, double eps) const {
+    return rms_norm_diff(var, grad, &history, nullptr, nullptr, nullptr, normalized_shape, eps);
+}
 VarDiff VarDiff::embedding(const Var& indices, long padding_idx) const {
     auto n = embedding_fwd_node(var, indices, padding_idx);
     auto y = n->y;
@@ -2607,6 +2700,19 @@ VarDiff LayerNorm::forward(const Var& input) const {
 }
 VarDiff LayerNorm::forward(const VarDiff& input) const {
     return elementwise_affine ? input.layer_norm(weight, bias, eps) : input.layer_norm(normalized_shape, eps);
+}
+RMSNorm::RMSNorm(DevicePtr dev, Shape normalized_shape, double eps, bool elementwise_affine)
+    : normalized_shape(std::move(normalized_shape)), eps(eps), elementwise_affine(elementwise_affine) {
+    if (this->normalized_shape.empty() || numel(this->normalized_shape) == 0) panic("RMSNorm: normalized_shape must not be empty");
+    if (elementwise_affine) weight = ones(dev, this->normalized_shape).requires_grad();
+}
+RMSNorm::RMSNorm(VarDiff w, double eps) : weight(std::move(w)), normalized_shape(weight.shape()), eps(eps) {}
+VarDiff RMSNorm::forward(const Var& input) const {
+    if (!elementwise_affine) panic("RMSNorm without a weight on a Var input has nothing to differentiate: use Var::rms_norm(normalized_shape, eps)");
+    return input.rms_norm(weight, eps);
+}
+VarDiff RMSNorm::forward(const VarDiff& input) const {
+    return elementwise_affine ? input.rms_norm(weight, eps) : input.rms_norm(normalized_shape, eps);
 }
 Var GELU::forward(const Var& input) const { return input.gelu(approximate_tanh); }
 VarDiff GELU::forward(const VarDiff& input) const { return input.gelu(approximate_tanh); }
@@ -3257,6 +3363,12 @@ nn::LayerNorm layer_norm_from_json(DevicePtr dev, const Json& j, double eps) {
     return nn::LayerNorm(vardiff_from_json(dev, j.at("weight")), vardiff_from_json(dev, j.at("bias")), eps);
 }
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const std::string& text, double eps) { return layer_norm_from_json(std::move(dev), parse(text), eps); }
+std::string to_json(const nn::RMSNorm& l) {
+    if (!l.elementwise_affine) panic("serde: an RMSNorm without a weight has nothing to serialise");
+    return "{\"weight\":" + to_json(l.weight) + "}";
+}
+nn::RMSNorm rms_norm_from_json(DevicePtr dev, const Json& j, double eps) { return nn::RMSNorm(vardiff_from_json(dev, j.at("weight")), eps); }
+nn::RMSNorm rms_norm_from_json(DevicePtr dev, const std::string& text, double eps) { return rms_norm_from_json(std::move(dev), parse(text), eps); }
 
 std::string to_json(const nn::Embedding& e) { return "{\"weight\":" + to_json(e.weight) + "}"; }
 nn::Embedding embedding_from_json(DevicePtr dev, const Json& j, long padding_idx) {

@@ -335,6 +335,11 @@ class Var {
     Var layer_norm(const Var& gamma, const Var& beta, double eps = 1e-5) const;
     Var layer_norm(const Shape& normalized_shape, double eps = 1e-5) const;
     VarDiff layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps = 1e-5) const;
+    // RMS normalisation over the trailing dimensions (ours: the reference has none; semantics in neuronika_hip.h): no centring,
+    // no beta.  The normalised shape is gamma's, or `normalized_shape` without a weight.  The Var forms keep no statistics.
+    Var rms_norm(const Var& gamma, double eps = 1e-6) const;
+    Var rms_norm(const Shape& normalized_shape, double eps = 1e-6) const;
+    VarDiff rms_norm(const VarDiff& gamma, double eps = 1e-6) const;
     // Batch normalisation over (N, spatial...) for each channel of an (N, C, spatial...) input (ours: the reference has none;
     // semantics in neuronika_hip.h).  gamma / beta of shape (C), both or neither (null: no affine part); running_mean /
     // running_var of shape (C), both or neither, updated IN PLACE by a training forward.  `status` is read each time the forward
@@ -472,6 +477,10 @@ class VarDiff {
     VarDiff layer_norm(const VarDiff& gamma, const VarDiff& beta, double eps = 1e-5) const;
     VarDiff layer_norm(const Var& gamma, const Var& beta, double eps = 1e-5) const;
     VarDiff layer_norm(const Shape& normalized_shape, double eps = 1e-5) const;
+    // one forward and ONE backward entry; gradients flow to self and, independently, to gamma where differentiable
+    VarDiff rms_norm(const VarDiff& gamma, double eps = 1e-6) const;
+    VarDiff rms_norm(const Var& gamma, double eps = 1e-6) const;
+    VarDiff rms_norm(const Shape& normalized_shape, double eps = 1e-6) const;
     // Embedding (ours: the reference has none; semantics in neuronika_hip.h): self is the (V, D) table, `indices` holds ids as f32
     // (read as the NLL targets are) in any shape; the result has shape indices.shape + (D,).  Differentiable in the table only:
     // its gradient is the ordered sum per row, no atomics; rows selected through `padding_idx` (< 0: none) receive no gradient.
@@ -617,6 +626,21 @@ struct LayerNorm {
     LayerNorm(DevicePtr dev, Shape normalized_shape, double eps = 1e-5, bool elementwise_affine = true);
     LayerNorm(VarDiff weight, VarDiff bias, double eps = 1e-5);  // parameters built elsewhere (e.g. deserialised)
     VarDiff forward(const Var& input) const;  // differentiable in the parameters: needs elementwise_affine
+    VarDiff forward(const VarDiff& input) const;
+};
+
+// RMS normalisation over the trailing `normalized_shape` of the input (ours: the reference has no normalisation layer), the
+// normalisation of LLaMA-style decoders: y = x / sqrt(mean(x^2) + eps) * weight per row, no centring and no bias.  weight = ones
+// of `normalized_shape`, an ordinary leaf for the optimizers; without `elementwise_affine` there is no parameter (weight stays
+// empty) and y = xhat.  The default eps is LLaMA's.
+struct RMSNorm {
+    VarDiff weight;
+    Shape normalized_shape;
+    double eps = 1e-6;
+    bool elementwise_affine = true;
+    RMSNorm(DevicePtr dev, Shape normalized_shape, double eps = 1e-6, bool elementwise_affine = true);
+    RMSNorm(VarDiff weight, double eps = 1e-6);  // a parameter built elsewhere (e.g. deserialised)
+    VarDiff forward(const Var& input) const;  // differentiable in the weight: needs elementwise_affine
     VarDiff forward(const VarDiff& input) const;
 };
 
@@ -965,6 +989,9 @@ nn::Linear linear_from_json(DevicePtr dev, const std::string& text);
 std::string to_json(const nn::LayerNorm& l);  // {"weight":..., "bias":...}; eps is not part of the wire format
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const Json& j, double eps = 1e-5);
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const std::string& text, double eps = 1e-5);
+std::string to_json(const nn::RMSNorm& l);  // {"weight":...}; eps is not part of the wire format
+nn::RMSNorm rms_norm_from_json(DevicePtr dev, const Json& j, double eps = 1e-6);
+nn::RMSNorm rms_norm_from_json(DevicePtr dev, const std::string& text, double eps = 1e-6);
 std::string to_json(const nn::Embedding& e);  // {"weight":...}; padding_idx is not part of the wire format
 nn::Embedding embedding_from_json(DevicePtr dev, const Json& j, long padding_idx = -1);
 nn::Embedding embedding_from_json(DevicePtr dev, const std::string& text, long padding_idx = -1);

@@ -75,6 +75,9 @@ PYBIND11_MODULE(_tape, m) {
         .def("layer_norm", py::overload_cast<const Var&, const Var&, double>(&Var::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const VarDiff&, const VarDiff&, double>(&Var::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const Shape&, double>(&Var::layer_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-5)
+        .def("rms_norm", py::overload_cast<const Var&, double>(&Var::rms_norm, py::const_), py::arg("gamma"), py::arg("eps") = 1e-6)
+        .def("rms_norm", py::overload_cast<const VarDiff&, double>(&Var::rms_norm, py::const_), py::arg("gamma"), py::arg("eps") = 1e-6)
+        .def("rms_norm", py::overload_cast<const Shape&, double>(&Var::rms_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-6)
         // gamma / beta: VarDiff (differentiable result), Var, or None; running_mean / running_var: Var or None
         .def("batch_norm", [](const Var& x, const VarDiff& gamma, const VarDiff& beta, const Var* rm, const Var* rv, double momentum, double eps,
                               const Status& s) { return x.batch_norm(gamma, beta, rm, rv, momentum, eps, s.flag); },
@@ -155,6 +158,9 @@ PYBIND11_MODULE(_tape, m) {
         .def("layer_norm", py::overload_cast<const VarDiff&, const VarDiff&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const Var&, const Var&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
         .def("layer_norm", py::overload_cast<const Shape&, double>(&VarDiff::layer_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-5)
+        .def("rms_norm", py::overload_cast<const VarDiff&, double>(&VarDiff::rms_norm, py::const_), py::arg("gamma"), py::arg("eps") = 1e-6)
+        .def("rms_norm", py::overload_cast<const Var&, double>(&VarDiff::rms_norm, py::const_), py::arg("gamma"), py::arg("eps") = 1e-6)
+        .def("rms_norm", py::overload_cast<const Shape&, double>(&VarDiff::rms_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-6)
         .def("embedding", &VarDiff::embedding, py::arg("indices"), py::arg("padding_idx") = -1)
         .def("batch_norm", [](const VarDiff& x, const VarDiff& gamma, const VarDiff& beta, const Var* rm, const Var* rv, double momentum, double eps,
                               const Status& s) { return x.batch_norm(gamma, beta, rm, rv, momentum, eps, s.flag); },
@@ -287,6 +293,9 @@ PYBIND11_MODULE(_tape, m) {
     sd.def("to_json", py::overload_cast<const nn::LayerNorm&>(&serde::to_json));
     sd.def("layer_norm_from_json", py::overload_cast<DevicePtr, const std::string&, double>(&serde::layer_norm_from_json), py::arg("dev"), py::arg("text"),
            py::arg("eps") = 1e-5);
+    sd.def("to_json", py::overload_cast<const nn::RMSNorm&>(&serde::to_json));
+    sd.def("rms_norm_from_json", py::overload_cast<DevicePtr, const std::string&, double>(&serde::rms_norm_from_json), py::arg("dev"), py::arg("text"),
+           py::arg("eps") = 1e-6);
     sd.def("to_json", py::overload_cast<const nn::Embedding&>(&serde::to_json));
     sd.def("embedding_from_json", py::overload_cast<DevicePtr, const std::string&, long>(&serde::embedding_from_json), py::arg("dev"), py::arg("text"),
            py::arg("padding_idx") = -1);
@@ -318,6 +327,17 @@ PYBIND11_MODULE(_tape, m) {
         .def_readonly("elementwise_affine", &nn::LayerNorm::elementwise_affine)
         .def("forward", py::overload_cast<const Var&>(&nn::LayerNorm::forward, py::const_))
         .def("forward", py::overload_cast<const VarDiff&>(&nn::LayerNorm::forward, py::const_));
+    py::class_<nn::RMSNorm>(nn, "RMSNorm")
+        .def(py::init<DevicePtr, Shape, double, bool>(), py::arg("dev"), py::arg("normalized_shape"), py::arg("eps") = 1e-6,
+             py::arg("elementwise_affine") = true)
+        .def(py::init<VarDiff, double>(), py::arg("weight"), py::arg("eps") = 1e-6)
+        // without affine parameters there is no weight: None
+        .def_property_readonly("weight", [](const nn::RMSNorm& l) { return l.elementwise_affine ? py::cast(l.weight) : py::object(py::none()); })
+        .def_readonly("normalized_shape", &nn::RMSNorm::normalized_shape)
+        .def_readwrite("eps", &nn::RMSNorm::eps)
+        .def_readonly("elementwise_affine", &nn::RMSNorm::elementwise_affine)
+        .def("forward", py::overload_cast<const Var&>(&nn::RMSNorm::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::RMSNorm::forward, py::const_));
     py::class_<nn::GELU>(nn, "GELU")
         .def(py::init<bool>(), py::arg("approximate_tanh") = false)
         .def_readonly("approximate_tanh", &nn::GELU::approximate_tanh)

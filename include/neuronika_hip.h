@@ -629,6 +629,39 @@ int nk_layer_norm_bwd_params(nk_device* dev, float* dgamma, float* dbeta, const 
 int nk_layer_norm_bwd_params_assign(nk_device* dev, float* dgamma, float* dbeta, const float* g, const float* x,
                                     const float* stats, long long rows, int D);
 
+/* ------------------------------------------------------------------ RMS normalisation */
+/* Root-mean-square normalisation over the trailing extent (LLaMA / Mistral / Qwen style).  The reference has no such layer; the
+ * semantics are fixed here.  The input is a contiguous row-major tensor read as (rows, D), D the product of the normalised
+ * trailing dimensions.  All arithmetic in f32:
+ *   ms   = sum(x * x) / D                      (no centring, no mean)
+ *   rstd = 1 / sqrt(ms + eps)
+ *   xhat = x * rstd ;  y = xhat * gamma        (gamma of D elements, or NULL: y = xhat; there is no beta)
+ * fwd overwrites y and, when `stats` is not NULL, writes stats[rows] = rstd (rstd ALONE: half of nk_layer_norm_fwd's record).
+ * `gamma` and `stats` may each be NULL (NULL stats: inference, nothing kept).  eps must be finite and >= 0.  Every D in
+ * 1 .. 2^30 and every rows >= 0 is accepted; rows == 0 returns NK_OK and writes nothing (in every entry point below, the _assign
+ * twins included).  D % 4 == 0 with 16-byte aligned pointers and D <= 16384 takes the kernels that keep the row in registers.
+ * bwd, with gh = g * gamma (or g when gamma is NULL), xhat recomputed from x and stats, c = sum(gh * xhat) / D:
+ *   dx     += rstd * (gh - xhat * c)
+ *   dgamma += sum over rows of g * xhat
+ * Nothing is guarded at the edges: an all-zero row gives y = 0 and rstd = 1 / sqrt(eps) (its dx is rstd * gh); at eps = 0 that
+ * row is NaN, and only that row; a row whose sum of squares overflows f32 gives rstd = 0 (y = 0 where x is finite); other
+ * non-finite inputs propagate as the arithmetic produces them, inside their own row only.  Gemma's (1 + gamma) weight and a
+ * bias are not part of it.
+ * dgamma is summed without atomics (per-row-block partial sums in the device workspace, then a fixed-order final sum whose
+ * order depends on (rows, D) alone): every result repeats bit for bit.  Nothing here synchronises or allocates beyond the
+ * workspace, so the calls can be captured into a graph.  The `_assign` twins write what their `+=` twin would leave in an
+ * all-zero destination, without reading it (see "first-write variants"). */
+int nk_rms_norm_fwd(nk_device* dev, const float* x, const float* gamma, float* y, float* stats, long long rows, int D,
+                    double eps);
+int nk_rms_norm_bwd(nk_device* dev, float* dx, const float* g, const float* x, const float* gamma, const float* stats,
+                    long long rows, int D);
+int nk_rms_norm_bwd_assign(nk_device* dev, float* dx, const float* g, const float* x, const float* gamma,
+                           const float* stats, long long rows, int D);
+int nk_rms_norm_bwd_gamma(nk_device* dev, float* dgamma, const float* g, const float* x, const float* stats,
+                          long long rows, int D);
+int nk_rms_norm_bwd_gamma_assign(nk_device* dev, float* dgamma, const float* g, const float* x, const float* stats,
+                                 long long rows, int D);
+
 /* ------------------------------------------------------------------ embedding table */
 /* Rows of a (V, D) f32 table selected by id.  The reference has no such layer; the semantics are fixed here.
  *   weight: (V, D) row-major.  idx: n ids STORED AS f32 and read exactly as nk_nll_* reads its targets (Rust's saturating

@@ -201,6 +201,25 @@ impl<E: Dimension + 'static> LayerNorm<E> {
     }
 }
 
+/// RMS normalisation over the trailing dimensions `normalized_shape` of the input (the reference has no normalisation layer;
+/// semantics in `include/neuronika_hip.h`): `y = x / sqrt(mean(x^2) + eps) * weight` per row, no centring and no bias, the
+/// normalisation of LLaMA-style decoders (`eps` = 1e-6 there).  `weight` starts as ones of `normalized_shape` (dimension `E`).
+pub struct RMSNorm<E: Dimension> {
+    pub weight: HipVarDiff<E>,
+    pub eps: f64,
+}
+
+impl<E: Dimension + 'static> RMSNorm<E> {
+    pub fn new(normalized_shape: E, eps: f64, device: &Device) -> Self {
+        Self { weight: HipVarDiff::parameter(&Array::ones(normalized_shape), device.clone()), eps }
+    }
+
+    /// ONE forward node (`nk_rms_norm_fwd`) and ONE backward entry (`nk_rms_norm_bwd`, `nk_rms_norm_bwd_gamma`).
+    pub fn forward<D: Dimension + 'static>(&self, input: HipVarDiff<D>) -> HipVarDiff<D> {
+        input.rms_norm(self.weight.clone(), self.eps)
+    }
+}
+
 /// Embedding table (the reference has no such layer; semantics in `include/neuronika_hip.h`): `forward(indices)` = the rows of
 /// `weight` `(num_embeddings, embedding_dim)` selected by the ids of `indices` (f32, any dimension), with one more axis of extent
 /// `embedding_dim`.  `weight` ~ N(0, 1) (`init::normal`, `neuronika-nn/src/init.rs:195-201`), the row `padding_idx` zeroed; that row

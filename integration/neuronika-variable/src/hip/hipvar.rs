@@ -21,7 +21,7 @@ use super::{
         Convolution, ConvolutionBackwardInput, ConvolutionBackwardKernel, ConvolutionBackwardKernelBias, ConvolutionBackwardPadded, ConvolutionBias,
         ConvolutionBiasPadded, CrossEntropy, CrossEntropyBackward, Dropout, Embedding, EmbeddingBackward,
         AvgPool, AvgPoolBackward, MaxPool, MaxPoolBackward,
-        DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
+        DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, RmsNorm, RmsNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
         decode_chunk, decode_workspace, PackedDecodeAttention,
         rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
@@ -275,6 +275,22 @@ where
 
     pub fn layer_norm<E: 'static + Dimension>(self, gamma: HipVar<E>, beta: HipVar<E>, eps: f64) -> HipVar<D> {
         self.layer_norm_with_stats(gamma, beta, eps, None)
+    }
+
+    /// RMS normalisation over the trailing dimensions, which must equal `gamma`'s shape: ours, the reference has no normalisation
+    /// node.  `stats` = the per-row `rstd` buffer a backward node will read, `None` for the no-gradient form (`rms_norm`).
+    pub(crate) fn rms_norm_with_stats<E: 'static + Dimension>(mut self, gamma: HipVar<E>, eps: f64, stats: Option<Shared<HipArray<Ix1>>>) -> HipVar<D> {
+        let (xs, ns) = (self.data.borrow().shape_c(), gamma.data.borrow().shape_c());
+        assert!(!ns.is_empty() && ns.len() <= xs.len() && xs[xs.len() - ns.len()..] == ns[..], "rms_norm: gamma must have the shape of the input's trailing dimensions");
+        assert!(eps >= 0.0 && eps.is_finite(), "rms_norm: eps must be finite and not negative");
+        self.history.merge(gamma.history);
+        let data = shared(self.data.borrow().dimension(), &self.device());
+        let op = RmsNorm::new(self.data, gamma.data, data.clone(), stats, eps);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    pub fn rms_norm<E: 'static + Dimension>(self, gamma: HipVar<E>, eps: f64) -> HipVar<D> {
+        self.rms_norm_with_stats(gamma, eps, None)
     }
 
     /// Batch normalisation over `(N, spatial...)` for each channel of an `(N, C, spatial...)` input: ours, the reference has no
@@ -994,6 +1010,19 @@ where
         let var = self.var.layer_norm_with_stats(gamma.var, beta.var, eps, Some(stats.clone()));
         let op: Rc<dyn Backward> = Rc::new(LayerNormBackward::new(input_data, gamma_data, stats, Some(self.grad.clone()), gamma.grad.clone(),
                                                                    beta.grad.clone(), grad.clone()));
+        HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
+    }
+
+    /// RMS normalisation with a differentiable weight: ONE forward node and ONE backward entry writing the gradients of `self`
+    /// and `gamma` (`RmsNormBackward`).
+    pub fn rms_norm<E: 'static + Dimension>(mut self, gamma: HipVarDiff<E>, eps: f64) -> HipVarDiff<D> {
+        self.history.merge(gamma.history);
+        let (input_data, gamma_data) = (self.var.data.clone(), gamma.var.data.clone());
+        let rows = input_data.borrow().len() / gamma_data.borrow().len().max(1);
+        let stats = shared(Ix1(rows), &self.var.device());
+        let grad = self.new_grad(self.grad.shape());
+        let var = self.var.rms_norm_with_stats(gamma.var, eps, Some(stats.clone()));
+        let op: Rc<dyn Backward> = Rc::new(RmsNormBackward::new(input_data, gamma_data, stats, Some(self.grad.clone()), gamma.grad.clone(), grad.clone()));
         HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
     }
 

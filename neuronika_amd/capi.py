@@ -175,6 +175,11 @@ _SIGS = {
     "nk_layer_norm_bwd_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
     "nk_layer_norm_bwd_params": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
     "nk_layer_norm_bwd_params_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
+    "nk_rms_norm_fwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_double],
+    "nk_rms_norm_bwd": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
+    "nk_rms_norm_bwd_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
+    "nk_rms_norm_bwd_gamma": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
+    "nk_rms_norm_bwd_gamma_assign": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int],
     "nk_embedding_fwd": [VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_int],
     "nk_embedding_bwd": [VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_int, C.c_longlong],
     "nk_embedding_bwd_assign": [VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_int, C.c_longlong],
@@ -867,6 +872,19 @@ def layer_norm_bwd_params(dev, dgamma, dbeta, g, x, stats, rows, D, assign=False
     """either of `dgamma`, `dbeta` may be None"""
     check((lib.nk_layer_norm_bwd_params_assign if assign else lib.nk_layer_norm_bwd_params)(dev.h, _p(dgamma), _p(dbeta), _p(g), _p(x), _p(stats),
                                                                                               int(rows), int(D)))
+
+
+def rms_norm_fwd(dev, x, gamma, y, stats, rows, D, eps=1e-6):
+    """x read as (rows, D); `gamma` and `stats` (rows,) may be None"""
+    check(lib.nk_rms_norm_fwd(dev.h, _p(x), _p(gamma), _p(y), _p(stats), int(rows), int(D), float(eps)))
+
+
+def rms_norm_bwd(dev, dx, g, x, gamma, stats, rows, D, assign=False):
+    check((lib.nk_rms_norm_bwd_assign if assign else lib.nk_rms_norm_bwd)(dev.h, _p(dx), _p(g), _p(x), _p(gamma), _p(stats), int(rows), int(D)))
+
+
+def rms_norm_bwd_gamma(dev, dgamma, g, x, stats, rows, D, assign=False):
+    check((lib.nk_rms_norm_bwd_gamma_assign if assign else lib.nk_rms_norm_bwd_gamma)(dev.h, _p(dgamma), _p(g), _p(x), _p(stats), int(rows), int(D)))
 
 
 def batch_norm_fwd(dev, x, gamma, beta, y, stats, running_mean, running_var, N, C, L, eps=1e-5, momentum=0.1):
