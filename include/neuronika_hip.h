@@ -101,14 +101,16 @@ const char* nk_version(void);
  *                          tiles through buffer descriptors - 32-bit byte offsets from the block's tile origin - only while the window
  *                          a tile spans in EACH operand is at most W bytes: (127 ld + K) * 4 for an operand whose k runs along its
  *                          rows, (K ld + 128) * 4 for one whose k runs down its columns.  Rule: W = 2^31 - 1.  A launch above the limit
- *                          takes the kernels' 64-bit pointer path; both give the same bits.  A small W lets a test reach that fallback
- *                          with small matrices.
+ *                          takes the guarded instantiations of the same layout, tile and epilogue (64-bit base per k-tile, 32-bit
+ *                          element offsets inside it, one k-tile of look-ahead); both give the same bits.  k-pair blocks are decided
+ *                          first and are not affected.  A small W lets a test reach that route with small matrices.
  * For schedule sweeps (benchmarks/ab_*.py) and the tests that pit one schedule against another bit for bit; results never
  * depend on them beyond summation order (split-K, chain length, algorithm). */
 enum { NK_TUNE_GEMM_FORCE = 0, NK_TUNE_GEMM_KPAIR = 1, NK_TUNE_ATTENTION_OCC = 2, NK_TUNE_GEMM_PAIR = 3, NK_TUNE_CONV_NARROW = 4,
        NK_TUNE_CONV_WINOGRAD = 5, NK_TUNE_GEMM_CHAIN = 6, NK_TUNE_CONV_S2DX = 7, NK_TUNE_GEMM_WINDOW = 8 };
 int nk_dev_tune(nk_device* dev, int knob, const int* values, int n);
-/* How many GEMM launches on this handle took the buffer-addressed path of their kernel so far (NK_TUNE_GEMM_WINDOW decides per launch). */
+/* How many GEMM launches on this handle took the buffer-addressed kernels so far (NK_TUNE_GEMM_WINDOW decides per launch; a launch
+ * sent to the guarded instantiations instead does not count). */
 int nk_gemm_buffer_launches(nk_device* dev, uint64_t* count);
 /* The num_records (bytes) of the buffer descriptor a block on that path builds for one operand: the window of its R-row tile
  * at (row0, k0) up to k = kend, clipped to the operand's extent (`rows` rows or columns, leading dimension ld, floats).

@@ -375,11 +375,12 @@ class Device:
 
     def gemm_window(self, nbytes=None):
         """NK_TUNE_GEMM_WINDOW: None / 0 the rule (2^31 - 1), W > 0: aligned 128 x 128 GEMM launches take the buffer-addressed
-        kernels only while a tile's window in each operand is at most W bytes (above it: the 64-bit pointer path, same bits)"""
+        kernels only while a tile's window in each operand is at most W bytes (above it: the guarded instantiations, same bits)"""
         self.tune(TUNE_GEMM_WINDOW, nbytes)
 
     def gemm_buffer_launches(self) -> int:
-        """nk_gemm_buffer_launches: GEMM launches on this handle that took the buffer-addressed path so far."""
+        """nk_gemm_buffer_launches: GEMM launches on this handle that took the buffer-addressed kernels so far (not those sent to the
+        guarded instantiations above the window limit)."""
         n = C.c_uint64(0)
         check(lib.nk_gemm_buffer_launches(self.h, C.byref(n)))
         return int(n.value)

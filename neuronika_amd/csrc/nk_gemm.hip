@@ -30,8 +30,7 @@ struct GemmArgs {
     const float* A;
     const float* B;
     float* C;
-    int M, N, K;
-    int buf;          // sgemm_kernel, aligned 128 x 128, 256 threads, not TT: buffer-addressed tile loads (gemm_plan; sits in the padding in front of lda)
+    int M, N, K;      // (four bytes of padding follow; the per-launch loader flag that sat there is gone, every offset is what it was)
     long long lda, ldb, ldc;
     float alpha, beta;
     const float* bias;  // optional column bias (length N) added in the epilogue: C = alpha*A.B + bias + beta*C
@@ -150,7 +149,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[T
 // then MFMAs -> barrier, instead of MFMAs -> wait for this trip's own loads -> 8 LDS writes -> barrier.  Unrolled by
 // two so that P / Q and the LDS buffers are static (even tiles in buf0, odd tiles in buf1).
 // `skew` (k-pair blocks, group 1): the first half of a k-tile's MFMAs is issued BEFORE the trip's staging stores.
-// (LA / LB: TileLoader or, on sgemm_kernel's buffer-addressed path, BufTileLoader - deduced)
+// (LA / LB: TileLoader or, in sgemm_kernel's buffer-only instantiations, BufTileLoader - deduced)
 template <bool AKC, bool BKC, bool ALIGNED, int TI, int TJ, int KG, class LA, class LB>
 __device__ __forceinline__ void gemm_loop_lookahead2(LA& la, LB& lb, f32x16 (&acc)[TI][TJ],
                                                      float* smem, int nt, bool skew, int t, int wr, int wc, int lane) {
@@ -231,6 +230,9 @@ __device__ __forceinline__ void gemm_loop_lookahead2(LA& la, LB& lb, f32x16 (&ac
 // floats of LDS one block of a given instantiation needs (both stages of every wave group)
 template <bool TA, bool TB, int TI, int TJ, int KG>
 constexpr int gemm_smem_floats() { return KG * 2 * (tile_floats<!TA, 64 * TI>() + tile_floats<TB, 64 * TJ>()); }
+// the sgemm_kernel instantiations whose block program loads its tiles through buffer descriptors, and only so
+template <bool TA, bool TB, bool ALIGNED, int TI, int TJ, int KG>
+constexpr bool gemm_buffer_only() { return ALIGNED && TI == 2 && TJ == 2 && KG == 1 && !(TA && TB); }
 
 template <bool TA, bool TB, bool ALIGNED, int TI, int TJ, int KG = 1, bool EPX = false>
 __global__ __launch_bounds__(NT * KG, (min_waves<TI, TJ, !TA && TB>())) void sgemm_kernel(GemmArgs p) {
@@ -238,20 +240,12 @@ __global__ __launch_bounds__(NT * KG, (min_waves<TI, TJ, !TA && TB>())) void sge
 #define NK_GEMM_BX blockIdx.x
 #define NK_GEMM_NBX gridDim.x
 #define NK_GEMM_SPLIT blockIdx.y
-    // The aligned 128 x 128 kernels of 256-thread blocks (NN, NT, TN) hold the block program twice: with buffer-addressed tile
-    // loads (BufTileLoader, nk_mma.h) for launches whose operand windows fit 32-bit byte offsets (gemm_plan sets `p.buf`, block-
-    // uniform), and with the 64-bit pointer loader for the rest.  The same MFMA feeding order and chains: bit-identical.  The
-    // buffer form frees the per-lane pointers of the k-loop.  Every other instantiation keeps the code it had.
-    if constexpr (ALIGNED && TI == 2 && TJ == 2 && KG == 1 && !(TA && TB)) {
-        if (p.buf) {
-            {
-                constexpr bool BUF = true;
-#include "nk_gemm_body.h"
-            }
-            return;
-        }
-    }
-    constexpr bool BUF = false;
+    // The aligned 128 x 128 kernels of 256-thread blocks (NN, NT, TN) hold the block program with buffer-addressed tile loads
+    // (BufTileLoader, nk_mma.h) and nothing else: the k-loops own the kernel's register budget (230 - 234 VGPRs, no scratch).
+    // gemm_impl launches them only when the operand windows fit 32-bit byte offsets (GemmPlan::buf) and sends a launch above
+    // the window limit to the guarded instantiation of the same layout, tile and epilogue.  Every other instantiation keeps
+    // the 64-bit pointer loader and the code it had.
+    constexpr bool BUF = gemm_buffer_only<TA, TB, ALIGNED, TI, TJ, KG>();
 #include "nk_gemm_body.h"
 #undef NK_GEMM_BX
 #undef NK_GEMM_NBX
@@ -433,7 +427,8 @@ struct GemmPlan {
     GemmArgs p;
     int ti, tj, kg, nbatch;
     bool aligned, empty;
-    bool buf;  // a launch of its own takes sgemm_kernel's buffer-addressed path (p.buf is set from it at the launch)
+    bool buf;   // a launch of its own goes to a buffer-only kernel (aligned 128 x 128, 256 threads, not TT, windows inside the limit)
+    bool over;  // ... would, but an operand window passes the limit: it goes to the guarded instantiation instead
 };
 
 static int gemm_plan(nk_device* dev, int transA, int transB, int M, int N, int K, float alpha,
@@ -593,15 +588,22 @@ static int gemm_plan(nk_device* dev, int transA, int transB, int M, int N, int K
         if (can && want) kg = 2;
         if (kpair_tune == 1) p.kskew = 0;
     }
-    // Buffer-addressed tile loads (sgemm_kernel's `p.buf` path): the aligned 128 x 128 launch of 256-thread blocks, NN / NT / TN, when the
-    // window a tile spans in EACH operand - from the shape alone, the whole K - fits the limit (2^31 - 1 bytes by rule: the
-    // loads' 32-bit voffset + soffset never wraps and num_records is a positive int; NK_TUNE_GEMM_WINDOW lowers it so that a
-    // test reaches the pointer kernels with small matrices).  Same bits either way.
+    // Buffer-addressed tile loads (the buffer-only kernels, gemm_buffer_only): the aligned 128 x 128 launch of 256-thread blocks,
+    // NN / NT / TN, when the window a tile spans in EACH operand - from the shape alone, the whole K - fits the limit (2^31 - 1
+    // bytes by rule: the loads' 32-bit voffset + soffset never wraps and num_records is a positive int; NK_TUNE_GEMM_WINDOW
+    // lowers it so that a test reaches the over-window route with small matrices).
+    // Above the limit (`over`; decided AFTER k-pair, whose blocks keep their aligned pointer kernel) gemm_impl launches the
+    // GUARDED instantiation of the same layout, tile and epilogue.  On an aligned problem its loader takes the 16-byte
+    // `interior` path of every tile and k-tile, its one-k-tile look-ahead loop feeds the MFMAs in the same order, and the
+    // split-K, chunk, batch and epilogue code is the same: the same bits.  Its reach is the pointer program's: 32-bit ELEMENT
+    // offsets inside one k-tile (127 ld + 32, or 31 ld + 128, below 2^32) from a 64-bit base advanced per k-tile.
     {
         const long long limit = dev->tune_gemm_window > 0 ? dev->tune_gemm_window : 0x7fffffffLL;
         const long long wa = !transA ? (127 * (long long)lda + K) * 4 : ((long long)K * lda + 128) * 4;
         const long long wb = transB ? (127 * (long long)ldb + K) * 4 : ((long long)K * ldb + 128) * 4;
-        plan->buf = aligned && ti == 2 && tj == 2 && kg == 1 && !(transA && transB) && wa <= limit && wb <= limit;
+        const bool buffer_only = aligned && ti == 2 && tj == 2 && kg == 1 && !(transA && transB);
+        plan->buf = buffer_only && wa <= limit && wb <= limit;
+        plan->over = buffer_only && !plan->buf;
     }
     plan->p = p; plan->ti = ti; plan->tj = tj; plan->kg = kg; plan->aligned = aligned;
     return NK_OK;
@@ -710,7 +712,7 @@ static int gemm_impl(nk_device* dev, int transA, int transB, int M, int N, int K
     }
     GemmArgs& p = plan.p;
     const int nbatch = plan.nbatch, ti = plan.ti, tj = plan.tj, kg = plan.kg;
-    const bool aligned = plan.aligned;
+    bool aligned = plan.aligned;
     if (dev->busy_slots > 0 && ti == 2 && tj == 2 && kg == 1 && aligned && p.splits == 1 && p.chunk == 1 && nbatch == 1 &&
         !(transA && transB) && dev->tune_gemm_n < 3) {
         bool taken = false;
@@ -725,8 +727,8 @@ static int gemm_impl(nk_device* dev, int transA, int transB, int M, int N, int K
     }
     rc = nk_prof_start(dev, NK_KERNEL_SGEMM, 2.0 * M * N * (double)K * nbatch);
     if (rc) return rc;
-    p.buf = plan.buf ? 1 : 0;  // (the pair and tail kernels launch a plan's arguments with buf = 0: they hold the pointer loader only)
     if (plan.buf) ++dev->gemm_buf_launches;
+    if (plan.over) aligned = false;  // the guarded instantiation (gemm_plan); the pair and tail kernels hold the pointer loader and take any window
     if (!transA && !transB) rc = launch<false, false>(dev, p, nbatch, aligned, ti, tj, kg);
     else if (!transA && transB) rc = launch<false, true>(dev, p, nbatch, aligned, ti, tj, kg);
     else if (transA && !transB) rc = launch<true, false>(dev, p, nbatch, aligned, ti, tj, kg);

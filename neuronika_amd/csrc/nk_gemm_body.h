@@ -5,7 +5,7 @@
 // that differs between the two uses is where a block's position in the tile sequence comes from:
 //   NK_GEMM_BX / NK_GEMM_NBX   this block's index among the blocks of ITS problem / their number
 //   NK_GEMM_SPLIT              which range of the reduction it takes (blockIdx.y, except in sgemm_tail_kernel's second problem)
-// In scope: template parameters (or constants) TA, TB, ALIGNED, TI, TJ, KG, EPX, BUF (buffer-addressed loader); `const GemmArgs& p`; `float* smem_all` (the block's LDS).
+// In scope: template parameters (or constants) TA, TB, ALIGNED, TI, TJ, KG, EPX, BUF (buffer-addressed loader: a constant of the template arguments, true in sgemm_kernel's buffer-only instantiations alone); `const GemmArgs& p`; `float* smem_all` (the block's LDS).
 // grid.z = batch in every use.  Not a stand-alone header.
     constexpr int BM = 64 * TI, BN = 64 * TJ;
     constexpr bool AKC = !TA;  // A (M x K): k-contiguous unless stored transposed

@@ -87,7 +87,8 @@ __device__ __forceinline__ void stage_store(float* Xs, const Stage<R / 32>& r, i
 // emits in the GEMM k-loops is a per-lane 64-bit pointer per load (`v_lshl_add_u64 v[a:a+1], v[o:o+1], 0, s[base]`, then
 // `global_load_dwordx4 v, v[a:a+1], off`): two VGPRs of widened offset and two of current pointer per load, live across the
 // whole loop.  The convolution kernels and the unaligned / 64-wide GEMMs keep this loader; the aligned 128 x 128 GEMM takes
-// BufTileLoader below (a second copy of its block program, chosen per launch) where the host finds that the tile's window fits 32-bit offsets.
+// BufTileLoader below - its kernels hold no other loader; the host launches them only where the tile's window fits 32-bit byte
+// offsets and sends the rest to the guarded instantiation, which reads whole tiles through this loader's `interior` path.
 template <bool KC, int R>
 struct TileLoader {
     const float* base;  // &X[tile origin] for the current k-tile (wave-uniform)
