@@ -12,6 +12,9 @@ K and V per token instead of the causal forward over the whole prefix.
                                                       # where the head left them, the ids Var feeds `Embedding.forward`, and the host
                                                       # reads the ids once, after the last step.  Temperature 0 (the default) is greedy
                                                       # and generates the ids of the host path token for token
+    python examples/generate.py [new_tokens] --kv-heads 2    # grouped-query attention: 4 query heads share 2 (or 1: multi-query) key /
+                                                      # value heads; the caches are built with that many heads and hold 1/2 (1/4) of
+                                                      # the bytes; with --rope --rmsnorm this is the attention block of LLaMA-2-70B / 3
 
 The weights are random (fixed seeds): the text means nothing, the mechanics are the point.  The last lines compare every step's
 logits with those of the full causal forward over the same prefix."""
@@ -24,14 +27,14 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-VOCAB, D_MODEL, HEADS, LAYERS, CONTEXT = 64, 64, 2, 2, 64
+VOCAB, D_MODEL, HEADS, LAYERS, CONTEXT = 64, 128, 4, 2, 64
 
 
 class Block:
-    def __init__(self, nk, dev, seed, rope=None, norm=None):
+    def __init__(self, nk, dev, seed, rope=None, norm=None, kv_heads=HEADS):
         norm = norm or nk.nn.LayerNorm
         self.ln1, self.ln2 = norm(dev, [D_MODEL]), norm(dev, [D_MODEL])
-        self.mha = nk.nn.MultiheadAttention(dev, D_MODEL, HEADS, 0.0, seed)
+        self.mha = nk.nn.MultiheadAttention(dev, D_MODEL, HEADS, 0.0, seed, kv_heads=kv_heads)
         self.mha.causal = True
         self.mha.drop.eval()
         self.mha.rope = rope                                             # None: the learned position table below carries the positions
@@ -51,14 +54,14 @@ class Block:
 
 
 class Decoder:
-    def __init__(self, nk, dev, rope=False, rmsnorm=False):
+    def __init__(self, nk, dev, rope=False, rmsnorm=False, kv_heads=HEADS):
         self.nk, self.dev = nk, dev
         norm = nk.nn.RMSNorm if rmsnorm else nk.nn.LayerNorm
         self.tok, self.pos = nk.nn.Embedding(dev, VOCAB, D_MODEL, seed=1), nk.nn.Embedding(dev, CONTEXT, D_MODEL, seed=2)
         # rotary mode: the queries and keys of every layer are rotated by their position (at lens[b] + t in a step, so the caches
         # hold rotated keys) and nothing is added to the token embedding
         self.rope = nk.nn.RotaryEmbedding(dev, D_MODEL // HEADS, CONTEXT) if rope else None
-        self.blocks = [Block(nk, dev, 100 * (i + 1), self.rope, norm) for i in range(LAYERS)]
+        self.blocks = [Block(nk, dev, 100 * (i + 1), self.rope, norm, kv_heads) for i in range(LAYERS)]
         self.ln, self.head = norm(dev, [D_MODEL]), nk.nn.Linear(dev, D_MODEL, VOCAB, 7)
 
     def embed(self, ids, first, shape=None):
@@ -113,15 +116,15 @@ def generate_on_device(nk, dev, model, prompt, new_tokens, caches, temperature, 
     return ids, worst
 
 
-def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=0, top_p=1.0, seed=0, rmsnorm=False):
+def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=0, top_p=1.0, seed=0, rmsnorm=False, kv_heads=HEADS):
     import neuronika_amd
     nk = neuronika_amd.tape
     dev = nk.Device(0)
-    model = Decoder(nk, dev, rope, rmsnorm)
+    model = Decoder(nk, dev, rope, rmsnorm, kv_heads)
     prompt = np.array([[3, 14, 15, 9, 26, 5, 35, 8]])
     batch, n = prompt.shape
     assert n + new_tokens <= CONTEXT
-    caches = [nk.nn.KvCache(dev, batch, HEADS, D_MODEL // HEADS, CONTEXT) for _ in range(LAYERS)]
+    caches = [nk.nn.KvCache(dev, batch, kv_heads, D_MODEL // HEADS, CONTEXT) for _ in range(LAYERS)]   # kv_heads heads per layer
     if device_sample:
         ids, worst = generate_on_device(nk, dev, model, prompt, new_tokens, caches, temperature, top_k, top_p, seed)
     else:
@@ -144,10 +147,12 @@ if __name__ == "__main__":
     ap.add_argument("new_tokens", nargs="?", type=int, default=16)
     ap.add_argument("--rope", action="store_true", help="rotary positions instead of the learned position table")
     ap.add_argument("--rmsnorm", action="store_true", help="nn.RMSNorm in place of the three nn.LayerNorm")
+    ap.add_argument("--kv-heads", type=int, default=HEADS, choices=[1, 2, 4], help="key / value heads shared by the %d query heads (grouped-query attention)" % HEADS)
     ap.add_argument("--device-sample", action="store_true", help="draw the next ids on the device (nn.Sampler); the host reads them once")
     ap.add_argument("--temperature", type=float, default=0.0, help="with --device-sample: 0 = greedy")
     ap.add_argument("--top-k", type=int, default=0, help="with --device-sample: 0 = off")
     ap.add_argument("--top-p", type=float, default=1.0, help="with --device-sample: 1 = off")
     ap.add_argument("--seed", type=int, default=0, help="with --device-sample: the Philox key of the draws")
     a = ap.parse_args()
-    main(a.new_tokens, rope=a.rope, device_sample=a.device_sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, rmsnorm=a.rmsnorm)
+    main(a.new_tokens, rope=a.rope, device_sample=a.device_sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, rmsnorm=a.rmsnorm,
+         kv_heads=a.kv_heads)

@@ -906,41 +906,53 @@ struct QkvAttentionBwd : Backward {
 };
 
 // nn::MultiheadAttention::forward_step: one slice of T new positions per sample against the layer's key / value cache, in
-// inference.  Projections (one GEMM into qkv (n, 3d) when packed, three into q / k / v (n, d) otherwise), append, attention,
-// output projection.  `start` is the int32 image of the lengths the cache had when the node was built: a second forward() writes
+// inference.  Projections (one GEMM into qkv (n, d + 2 dkv) when packed - (n, 3d) without kv_heads -, three into q (n, d) and
+// k / v (n, dkv) otherwise), rope, append of Hkv heads, attention, output projection.  `start` is the int32 image of the lengths the cache had when the node was built: a second forward() writes
 // the same rows again.
 struct DecodeStepFwd : Forward {
-    int B, T, H, dh, cap;
-    Shared<HipArray> x, w[3], b[3], wo, bo;  // packed: w[0] / b[0] are the (3d, d) / (3d) storage, the others null
+    int B, T, H, Hkv, dh, cap;  // Hkv == H: plain multi-head attention, the launches of the module without kv_heads
+    Shared<HipArray> x, w[3], b[3], wo, bo;  // packed: w[0] / b[0] are the (d + 2 dkv, d) / (d + 2 dkv) storage, the others null
     Shared<HipArray> qkv, q, k, v, ctx, out;
     Shared<HipArray> kc, vc, ws, start;
+    Shared<HipArray> qf, kf, vf;  // grouped prefill on the core: K and V repeated to (n, d); qf: Q out of the packed buffer, contiguous
     float scale;
     bool core = false;  // every start 0, T >= 2, head size of the fused core
     Shared<HipArray> rope;  // the rotary table or null: the new Q and K rows are rotated at start[b] + t before the append
-    RopeGeom rg;            // NH = 2 H when packed (Q|K in one launch), H otherwise (two launches)
+    RopeGeom rg, rgk;       // rg: NH = H + Hkv when packed (Q|K in one launch), H otherwise; rgk: the K launch of the unpacked form, NH = Hkv
     void forward() const override {
         nk_device* dev = D(x);
-        const int n = B * T, d = H * dh;
+        const int n = B * T, d = H * dh, dkv = Hkv * dh;
         const float *Q, *K, *V;
-        int ld;
+        int ld, ldkv;
         if (qkv) {
-            check(nk_linear_fwd(dev, x->ptr(), w[0]->ptr(), b[0]->ptr(), qkv->ptr(), n, d, 3 * d));
-            Q = qkv->ptr(); K = Q + d; V = Q + 2 * d; ld = 3 * d;
+            check(nk_linear_fwd(dev, x->ptr(), w[0]->ptr(), b[0]->ptr(), qkv->ptr(), n, d, d + 2 * dkv));
+            Q = qkv->ptr(); K = Q + d; V = Q + d + dkv; ld = ldkv = d + 2 * dkv;
         } else {
             Shared<HipArray> y[3] = {q, k, v};
-            for (int i = 0; i < 3; ++i) check(nk_linear_fwd(dev, x->ptr(), w[i]->ptr(), b[i]->ptr(), y[i]->ptr(), n, d, d));
-            Q = q->ptr(); K = k->ptr(); V = v->ptr(); ld = d;
+            for (int i = 0; i < 3; ++i) check(nk_linear_fwd(dev, x->ptr(), w[i]->ptr(), b[i]->ptr(), y[i]->ptr(), n, d, i == 0 ? d : dkv));
+            Q = q->ptr(); K = k->ptr(); V = v->ptr(); ld = d; ldkv = dkv;
         }
         const int* st = reinterpret_cast<const int*>(start->ptr());
         if (rope) {
             rope_inplace(dev, const_cast<float*>(Q), ld, rope, st, rg, false);
-            if (!qkv) rope_inplace(dev, const_cast<float*>(K), ld, rope, st, rg, false);
+            if (!qkv) rope_inplace(dev, const_cast<float*>(K), ldkv, rope, st, rgk, false);
         }
-        check(nk_kv_cache_append(dev, kc->ptr(), vc->ptr(), K, V, ld, st, B, T, H, dh, cap));
-        if (core && qkv)
+        check(nk_kv_cache_append(dev, kc->ptr(), vc->ptr(), K, V, ldkv, st, B, T, Hkv, dh, cap));
+        if (core && Hkv != H) {  // the core runs on H heads of K and V: the step's rows repeated into the node's temporaries
+            const int G = H / Hkv;
+            check(nk_repeat_kv_fwd(dev, K, ldkv, kf->ptr(), d, n, Hkv, G, dh));
+            check(nk_repeat_kv_fwd(dev, V, ldkv, vf->ptr(), d, n, Hkv, G, dh));
+            if (qf) {  // the core takes contiguous rows: the Q block of the packed buffer copied out (G = 1)
+                check(nk_repeat_kv_fwd(dev, Q, ld, qf->ptr(), d, n, H, 1, dh));
+                Q = qf->ptr();
+            }
+            check(nk_attention_causal_fwd(dev, Q, kf->ptr(), vf->ptr(), nullptr, nullptr, nullptr, ctx->ptr(), B, T, H, dh, scale, 0.0, 0, 0, 0));
+        } else if (core && qkv)
             check(nk_attention_qkv_causal_fwd(dev, qkv->ptr(), nullptr, nullptr, nullptr, ctx->ptr(), B, T, H, dh, scale, 0.0, 0, 0, 0));
         else if (core)
             check(nk_attention_causal_fwd(dev, Q, K, V, nullptr, nullptr, nullptr, ctx->ptr(), B, T, H, dh, scale, 0.0, 0, 0, 0));
+        else if (Hkv != H)
+            check(nk_attention_decode_gqa_fwd(dev, Q, ld, kc->ptr(), vc->ptr(), st, ctx->ptr(), ws->ptr(), B, T, H, Hkv, dh, cap, scale));
         else
             check(nk_attention_decode_fwd(dev, Q, ld, kc->ptr(), vc->ptr(), st, ctx->ptr(), ws->ptr(), B, T, H, dh, cap, scale));
         check(nk_linear_fwd(dev, ctx->ptr(), wo->ptr(), bo->ptr(), out->ptr(), n, d, d));
@@ -1019,6 +1031,26 @@ struct RopeBwd : Backward {
         const int ld = rg.NH * rg.dh;
         check((assign ? nk_rope_bwd_assign : nk_rope_bwd)(D(table), d.ptr(), ld, G.ptr(), ld, table->ptr(), nullptr, rg.B, rg.T, rg.NH, rg.dh, rg.rot,
                                                           rg.max_pos, rg.interleaved));
+    }
+    void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
+};
+
+// repeat_kv (ours; the reference has no such node; semantics at nk_repeat_kv_fwd in neuronika_hip.h): a (rows, Hkv*dh) value with every
+// head written G times in front of the attention core of a grouped-query layer.  The backward sums the gradients of the copies in
+// ascending copy order and keeps nothing of the input.  The first writer of the input's gradient takes the assign form.
+struct RepeatKvFwd : Forward {
+    int rows = 0, Hkv = 0, G = 0, dh = 0;
+    Shared<HipArray> x, y;
+    void forward() const override { check(nk_repeat_kv_fwd(D(x), x->ptr(), Hkv * dh, y->ptr(), Hkv * G * dh, rows, Hkv, G, dh)); }
+};
+struct RepeatKvBwd : Backward {
+    int rows = 0, Hkv = 0, G = 0, dh = 0;
+    Shared<Gradient> dx, g;
+    void backward() const override {
+        const HipArray& Gr = g->borrow();
+        bool assign = false;
+        HipArray& d = dx->borrow_first_write(assign);
+        check((assign ? nk_repeat_kv_bwd_assign : nk_repeat_kv_bwd)(Gr.device()->raw(), d.ptr(), Hkv * dh, Gr.ptr(), Hkv * G * dh, rows, Hkv, G, dh));
     }
     void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
 };
@@ -1786,6 +1818,23 @@ Var Var::rope(const nn::RotaryEmbedding& rotary, int batch, int heads) const {
     auto y = n->y;
     return Var::node(y, n, history);
 }
+static Shared<RepeatKvFwd> repeat_kv_fwd_node(const Var& x, int groups, int head_dim) {
+    const Shape& s = x.shape();
+    if (groups <= 0 || head_dim <= 0) panic("repeat_kv: groups and head_dim must be positive");
+    if (s.size() != 2 || s[0] <= 0 || s[1] <= 0 || s[1] % head_dim != 0)
+        panic("repeat_kv: the input must be (rows, kv_heads*head_dim) with head_dim = " + std::to_string(head_dim));
+    if ((long long)s[1] * groups > (long long)INT_MAX || (unsigned long long)s[0] * s[1] * groups > (unsigned long long)INT_MAX)
+        panic("repeat_kv: the output must fit 31 bits");
+    auto n = std::make_shared<RepeatKvFwd>();
+    n->rows = s[0]; n->Hkv = s[1] / head_dim; n->G = groups; n->dh = head_dim;
+    n->x = x.data; n->y = zeros_like(x.data, Shape{s[0], s[1] * groups});
+    return n;
+}
+Var Var::repeat_kv(int groups, int head_dim) const {
+    auto n = repeat_kv_fwd_node(*this, groups, head_dim);
+    auto y = n->y;
+    return Var::node(y, n, history);
+}
 Var Var::sample(const nn::Sampler& sp, int batch) const {
     const Shape& s = shape();
     if (s.size() != 2 || batch <= 0 || s[0] == 0 || s[0] % batch != 0 || s[1] <= 0)
@@ -2291,6 +2340,15 @@ VarDiff VarDiff::rope(const nn::RotaryEmbedding& rotary, int batch, int heads) c
     auto g = std::make_shared<Gradient>(v.device(), v.shape());
     auto bw = std::make_shared<RopeBwd>();
     bw->rg = n->rg; bw->table = n->table; bw->dx = grad; bw->g = g;
+    return VarDiff::node(std::move(v), g, entry(bw, g), history);
+}
+VarDiff VarDiff::repeat_kv(int groups, int head_dim) const {
+    auto n = repeat_kv_fwd_node(var, groups, head_dim);
+    auto y = n->y;
+    Var v = Var::node(y, n, var.history);
+    auto g = std::make_shared<Gradient>(v.device(), v.shape());
+    auto bw = std::make_shared<RepeatKvBwd>();
+    bw->rows = n->rows; bw->Hkv = n->Hkv; bw->G = n->G; bw->dh = n->dh; bw->dx = grad; bw->g = g;
     return VarDiff::node(std::move(v), g, entry(bw, g), history);
 }
 VarDiff VarDiff::tanh() const { return pointwise_diff(NK_TANH, 0, *this); }
@@ -2955,41 +3013,57 @@ VarDiff ConvNd::forward(const VarDiff& input) const {
     return conv_diff(weight, padded.var, padded.grad, &padded.history, stride, dilation, groups, &bias);
 }
 
-// a Linear whose weight / bias (and their gradients) are rows [row0, row0 + d) of the packed storage, initialised as
-// `Linear(dev, d, d, seed)` would be
+// a Linear whose weight / bias (and their gradients) are rows [row0, row0 + out) of the packed storage, initialised as
+// `Linear(dev, d, out, seed)` would be
 static Linear packed_linear(const Shared<HipArray>& w_all, const Shared<HipArray>& b_all, const Shared<HipArray>& gw_all,
-                            const Shared<HipArray>& gb_all, int row0, int d, uint64_t seed) {
+                            const Shared<HipArray>& gb_all, int row0, int out, int d, uint64_t seed) {
     const float k = 1.f / std::sqrt((float)d);
-    auto w = std::make_shared<HipArray>(w_all, (size_t)row0 * d, Shape{d, d});
-    auto b = std::make_shared<HipArray>(b_all, (size_t)row0, Shape{d});
-    w->upload(uniform((size_t)d * d, -k, k, seed).data());
-    b->upload(uniform((size_t)d, -k, k, seed + 1).data());
-    return Linear(VarDiff::leaf(Var::leaf(w), std::make_shared<Gradient>(gw_all, (size_t)row0 * d, Shape{d, d})),
-                  VarDiff::leaf(Var::leaf(b), std::make_shared<Gradient>(gb_all, (size_t)row0, Shape{d})));
+    auto w = std::make_shared<HipArray>(w_all, (size_t)row0 * d, Shape{out, d});
+    auto b = std::make_shared<HipArray>(b_all, (size_t)row0, Shape{out});
+    w->upload(uniform((size_t)out * d, -k, k, seed).data());
+    b->upload(uniform((size_t)out, -k, k, seed + 1).data());
+    return Linear(VarDiff::leaf(Var::leaf(w), std::make_shared<Gradient>(gw_all, (size_t)row0 * d, Shape{out, d})),
+                  VarDiff::leaf(Var::leaf(b), std::make_shared<Gradient>(gb_all, (size_t)row0, Shape{out})));
 }
 static Linear placeholder_linear(const DevicePtr& dev) { return Linear(zeros(dev, {1, 1}).requires_grad(), zeros(dev, {1}).requires_grad()); }
+static void check_kv_heads(int d_model, int heads, int kv_heads) {
+    if (heads <= 0 || d_model % heads != 0) panic("d_model must be divisible by heads");
+    if (kv_heads <= 0 || kv_heads > heads || heads % kv_heads != 0)
+        panic("MultiheadAttention: kv_heads must be positive and divide heads, got heads = " + std::to_string(heads) + ", kv_heads = " +
+              std::to_string(kv_heads));
+}
 MultiheadAttention::MultiheadAttention(DevicePtr dev, int d_model_, int heads_, double p, uint64_t seed)
+    : MultiheadAttention(std::move(dev), d_model_, heads_, heads_, p, seed) {}
+MultiheadAttention::MultiheadAttention(DevicePtr dev, int d_model_, int heads_, int kv_heads_, double p, uint64_t seed)
     : q(placeholder_linear(dev)), k(placeholder_linear(dev)), v(placeholder_linear(dev)), o(dev, d_model_, d_model_, seed + 6),
-      d_model(d_model_), heads(heads_), drop(p) {
-    if (d_model % heads != 0) panic("d_model must be divisible by heads");
-    if (d_model % 4 != 0) {
-        // the bias views of a packed allocation start d and 2d floats in: not 16-byte aligned unless d % 4 == 0, and kernels
-        // that take whole float4s (nk_fill with a value, the pointwise kernels) refuse such a buffer.  Three ordinary layers.
-        q = Linear(dev, d_model, d_model, seed); k = Linear(dev, d_model, d_model, seed + 2); v = Linear(dev, d_model, d_model, seed + 4);
+      d_model(d_model_), heads(heads_), kv_heads(kv_heads_), drop(p) {
+    check_kv_heads(d_model, heads, kv_heads);
+    const int dkv = d_model / heads * kv_heads, rows = d_model + 2 * dkv;
+    if (d_model % 4 != 0 || dkv % 4 != 0) {
+        // the bias views of a packed allocation start d and d + dkv floats in: not 16-byte aligned unless both are multiples of 4,
+        // and kernels that take whole float4s (nk_fill with a value, the pointwise kernels) refuse such a buffer.  Three ordinary layers.
+        q = Linear(dev, d_model, d_model, seed); k = Linear(dev, d_model, dkv, seed + 2); v = Linear(dev, d_model, dkv, seed + 4);
         packed_qkv = false;
         return;
     }
-    wqkv_ = std::make_shared<HipArray>(dev, Shape{3 * d_model, d_model});
-    bqkv_ = std::make_shared<HipArray>(dev, Shape{3 * d_model});
-    gwqkv_ = std::make_shared<HipArray>(dev, Shape{3 * d_model, d_model}, HipArray::Uninit{});
-    gbqkv_ = std::make_shared<HipArray>(dev, Shape{3 * d_model}, HipArray::Uninit{});
-    q = packed_linear(wqkv_, bqkv_, gwqkv_, gbqkv_, 0, d_model, seed);
-    k = packed_linear(wqkv_, bqkv_, gwqkv_, gbqkv_, d_model, d_model, seed + 2);
-    v = packed_linear(wqkv_, bqkv_, gwqkv_, gbqkv_, 2 * d_model, d_model, seed + 4);
+    wqkv_ = std::make_shared<HipArray>(dev, Shape{rows, d_model});
+    bqkv_ = std::make_shared<HipArray>(dev, Shape{rows});
+    gwqkv_ = std::make_shared<HipArray>(dev, Shape{rows, d_model}, HipArray::Uninit{});
+    gbqkv_ = std::make_shared<HipArray>(dev, Shape{rows}, HipArray::Uninit{});
+    q = packed_linear(wqkv_, bqkv_, gwqkv_, gbqkv_, 0, d_model, d_model, seed);
+    k = packed_linear(wqkv_, bqkv_, gwqkv_, gbqkv_, d_model, dkv, d_model, seed + 2);
+    v = packed_linear(wqkv_, bqkv_, gwqkv_, gbqkv_, d_model + dkv, dkv, d_model, seed + 4);
 }
-MultiheadAttention::MultiheadAttention(Linear q_, Linear k_, Linear v_, Linear o_, int heads_, double p)
-    : q(std::move(q_)), k(std::move(k_)), v(std::move(v_)), o(std::move(o_)), d_model(q.weight.shape()[1]), heads(heads_), drop(p) {
-    if (d_model % heads != 0) panic("d_model must be divisible by heads");
+MultiheadAttention::MultiheadAttention(Linear q_, Linear k_, Linear v_, Linear o_, int heads_, double p, int kv_heads_)
+    : q(std::move(q_)), k(std::move(k_)), v(std::move(v_)), o(std::move(o_)), d_model(q.weight.shape()[1]), heads(heads_),
+      kv_heads(kv_heads_ == 0 ? heads_ : kv_heads_), drop(p) {
+    check_kv_heads(d_model, heads, kv_heads);
+    if (kv_heads != heads) {
+        const Shape want{d_model / heads * kv_heads, d_model};
+        if (k.weight.shape() != want || v.weight.shape() != want)
+            panic("MultiheadAttention: with " + std::to_string(kv_heads) + " kv heads of " + std::to_string(d_model / heads) +
+                  " the k and v projections must be (" + std::to_string(want[0]) + ", " + std::to_string(d_model) + ")");
+    }
     packed_qkv = false;
 }
 static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipArray>& w, const Shared<HipArray>& b, const Shared<HipArray>& gw,
@@ -3031,11 +3105,13 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
 bool MultiheadAttention::still_packed() const {
     if (!wqkv_) return false;
     const Linear* ls[3] = {&q, &k, &v};
-    const size_t dd = (size_t)d_model * d_model;
+    const int dkv = d_model / heads * kv_heads;
+    const int row0[3] = {0, d_model, d_model + dkv}, out[3] = {d_model, dkv, dkv};
     for (int i = 0; i < 3; ++i) {
-        if (ls[i]->weight.var.data->ptr() != wqkv_->ptr() + i * dd || ls[i]->bias.var.data->ptr() != bqkv_->ptr() + (size_t)i * d_model) return false;
-        if (ls[i]->weight.shape() != Shape{d_model, d_model} || ls[i]->bias.shape() != Shape{d_model}) return false;
-        if (!ls[i]->weight.grad->is_view_of(gwqkv_, i * dd) || !ls[i]->bias.grad->is_view_of(gbqkv_, (size_t)i * d_model)) return false;
+        const size_t wo = (size_t)row0[i] * d_model;
+        if (ls[i]->weight.var.data->ptr() != wqkv_->ptr() + wo || ls[i]->bias.var.data->ptr() != bqkv_->ptr() + (size_t)row0[i]) return false;
+        if (ls[i]->weight.shape() != Shape{out[i], d_model} || ls[i]->bias.shape() != Shape{out[i]}) return false;
+        if (!ls[i]->weight.grad->is_view_of(gwqkv_, wo) || !ls[i]->bias.grad->is_view_of(gbqkv_, (size_t)row0[i])) return false;
     }
     return true;
 }
@@ -3049,7 +3125,12 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
         if (S > rope->max_pos) panic("MultiheadAttention: " + std::to_string(S) + " positions exceed rope's table of " + std::to_string(rope->max_pos));
     }
     // the projections of the unpacked paths: queries and keys rotated when `rope` is set
-    auto rotated = [&](const Linear& l) { return rope ? l.forward(x).rope(*rope, batch, heads) : l.forward(x); };
+    auto rotated = [&](const Linear& l, int nh) { return rope ? l.forward(x).rope(*rope, batch, nh) : l.forward(x); };
+    // Grouped-query attention: kv head k written G times in front of the branches below, which then run on `heads` heads as they
+    // are (kv_heads == heads: no node is added)
+    const int G = heads / kv_heads;
+    auto keys = [&]() { return G == 1 ? rotated(k, heads) : rotated(k, kv_heads).repeat_kv(G, dh); };
+    auto values = [&]() { return G == 1 ? v.forward(x) : v.forward(x).repeat_kv(G, dh); };
     // Causal, where the fused core does not apply: the composition spelled out - one Addition node (broadcast over B*H) of a
     // constant (S, S) leaf, 0 on and below the diagonal and -inf above, in front of the Softmax, whose -inf lanes come out exactly 0.
     // Uploaded once per graph build; the fused `attention_probs` node has no mask operand and is not used.
@@ -3059,11 +3140,11 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
             for (int c = r + 1; c < n; ++c) m[(size_t)r * n + c] = -INFINITY;
         return from_host(x.var.device(), Shape{n, n}, m.data());
     };
-    if (packed_qkv && wqkv_ && strided_heads && fused && fused_core && q.fused && k.fused && v.fused && Var::attention_core_supported(S, dh, drop.p) &&
+    if (G == 1 && packed_qkv && wqkv_ && strided_heads && fused && fused_core && q.fused && k.fused && v.fused && Var::attention_core_supported(S, dh, drop.p) &&
         still_packed())
         return o.forward(qkv_attention_node(*this, wqkv_, bqkv_, gwqkv_, gbqkv_, x, batch, S, heads, dh, scale));
     if (strided_heads && dh % 4 == 0) {  // attention GEMMs address the heads inside the projection layout: no copies
-        const VarDiff Qf = rotated(q), Kf = rotated(k), Vf = v.forward(x);
+        const VarDiff Qf = rotated(q, heads), Kf = keys(), Vf = values();
         if (fused && fused_core && Var::attention_core_supported(S, dh, drop.p))
             return o.forward(Qf.heads_attention(Kf, Vf, batch, S, heads, dh, scale, drop.p, drop.status, causal));
         const VarDiff scores = Qf.heads_scores(Kf, batch, S, heads, dh);
@@ -3072,9 +3153,9 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
                                                                : drop.forward((scores * scale).softmax(2));
         return o.forward(P.heads_context(Vf, batch, S, heads, dh));
     }
-    const VarDiff Q = rotated(q).split_heads(batch, S, heads, dh);
-    const VarDiff K = rotated(k).split_heads(batch, S, heads, dh);
-    const VarDiff V = v.forward(x).split_heads(batch, S, heads, dh);
+    const VarDiff Q = rotated(q, heads).split_heads(batch, S, heads, dh);
+    const VarDiff K = keys().split_heads(batch, S, heads, dh);
+    const VarDiff V = values().split_heads(batch, S, heads, dh);
     const VarDiff P = causal ? drop.forward((Q.bmm_t(K) * scale + causal_mask(S)).softmax(2))
                       : (fused && S % 4 == 0 && S <= 2048) ? Q.bmm_t(K).attention_probs(scale, drop.p, drop.status)
                                                            : drop.forward((Q.bmm_t(K) * scale).softmax(2));
@@ -3111,14 +3192,16 @@ KvCache::KvCache(DevicePtr dev, int batch_, int heads_, int head_dim_, int capac
     k = std::make_shared<HipArray>(dev, s, HipArray::Uninit{});
     v = std::make_shared<HipArray>(dev, s, HipArray::Uninit{});
     lens_.assign((size_t)batch, 0);
-    (void)workspace(1);
+    (void)workspace(1, heads);
 }
-Shared<HipArray> KvCache::workspace(int T) {
-    if (T > ws_T_) {
-        const size_t n = nk_attention_decode_workspace(batch, T, heads, head_dim, capacity);
+Shared<HipArray> KvCache::workspace(int T, int query_heads) {
+    if (T > ws_T_ || query_heads > ws_H_) {
+        T = std::max(T, ws_T_);
+        query_heads = std::max(query_heads, ws_H_);
+        const size_t n = nk_attention_decode_workspace(batch, T, query_heads, head_dim, capacity);
         if (n == 0 || n > (size_t)INT_MAX) panic("KvCache: the decode workspace for " + std::to_string(T) + " rows per sample does not fit 31 bits");
         ws_ = std::make_shared<HipArray>(k->device(), Shape{(int)n}, HipArray::Uninit{});
-        ws_T_ = T;
+        ws_T_ = T; ws_H_ = query_heads;
     }
     return ws_;
 }
@@ -3141,10 +3224,10 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
     if (x.shape().size() != 2 || batch <= 0 || x.shape()[0] % batch != 0 || x.shape()[0] == 0 || x.shape()[1] != d_model)
         panic("MultiheadAttention::forward_step: bad input shape");
     const int T = x.shape()[0] / batch, dh = d_model / heads;
-    if (cache.batch != batch || cache.heads != heads || cache.head_dim != dh)
+    if (cache.batch != batch || cache.heads != kv_heads || cache.head_dim != dh)
         panic("MultiheadAttention::forward_step: the cache was built for batch " + std::to_string(cache.batch) + ", " + std::to_string(cache.heads) +
-              " heads of " + std::to_string(cache.head_dim) + ", the step has batch " + std::to_string(batch) + ", " + std::to_string(heads) +
-              " heads of " + std::to_string(dh));
+              " heads of " + std::to_string(cache.head_dim) + ", the step has batch " + std::to_string(batch) + ", " + std::to_string(kv_heads) +
+              " kv heads (of " + std::to_string(heads) + " query heads) of " + std::to_string(dh));
     if (cache.k->device().get() != x.device().get()) panic("MultiheadAttention::forward_step: the cache lives on another device");
     if (rope) {
         if (rope->head_dim != dh)
@@ -3162,22 +3245,23 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
         fresh = fresh && cache.lens()[b] == 0;
     }
     auto fw = std::make_shared<DecodeStepFwd>();
-    fw->B = batch; fw->T = T; fw->H = heads; fw->dh = dh; fw->cap = cache.capacity;
+    fw->B = batch; fw->T = T; fw->H = heads; fw->Hkv = kv_heads; fw->dh = dh; fw->cap = cache.capacity;
     fw->x = x.data;
     History<ForwardEntry> hf = x.history;
     for (const Linear* l : {&q, &k, &v, &o}) { hf.merge(l->weight.var.history); hf.merge(l->bias.var.history); }
-    const int n = batch * T;
+    const int n = batch * T, dkv = kv_heads * dh;
     if (packed_qkv && still_packed()) {
         fw->w[0] = wqkv_; fw->b[0] = bqkv_;
-        fw->qkv = zeros_like(x.data, Shape{n, 3 * d_model});
+        fw->qkv = zeros_like(x.data, Shape{n, d_model + 2 * dkv});
     } else {
         const Linear* ls[3] = {&q, &k, &v};
         for (int i = 0; i < 3; ++i) {
-            if (ls[i]->weight.shape() != Shape{d_model, d_model} || ls[i]->bias.shape() != Shape{d_model})
-                panic("MultiheadAttention::forward_step: the projections must be (d_model, d_model) with a (d_model) bias");
+            const int out = i == 0 ? d_model : dkv;
+            if (ls[i]->weight.shape() != Shape{out, d_model} || ls[i]->bias.shape() != Shape{out})
+                panic("MultiheadAttention::forward_step: the projections must be (d_model, d_model) - k and v (kv_heads*head_dim, d_model) - with a bias of their rows");
             fw->w[i] = ls[i]->weight.var.data; fw->b[i] = ls[i]->bias.var.data;
         }
-        fw->q = zeros_like(x.data, Shape{n, d_model}); fw->k = zeros_like(x.data, Shape{n, d_model}); fw->v = zeros_like(x.data, Shape{n, d_model});
+        fw->q = zeros_like(x.data, Shape{n, d_model}); fw->k = zeros_like(x.data, Shape{n, dkv}); fw->v = zeros_like(x.data, Shape{n, dkv});
     }
     if (o.weight.shape() != Shape{d_model, d_model} || o.bias.shape() != Shape{d_model})
         panic("MultiheadAttention::forward_step: the output projection must be (d_model, d_model) with a (d_model) bias");
@@ -3185,14 +3269,22 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
     fw->ctx = zeros_like(x.data, Shape{n, d_model});
     fw->out = zeros_like(x.data, Shape{n, d_model});
     fw->kc = cache.k; fw->vc = cache.v;
-    if (rope) { fw->rope = rope->table; fw->rg = rope_geom(*rope, batch, T, fw->qkv ? 2 * heads : heads); }
+    if (rope) {
+        fw->rope = rope->table;
+        fw->rg = rope_geom(*rope, batch, T, fw->qkv ? heads + kv_heads : heads);  // packed: the Q and K heads are contiguous columns
+        fw->rgk = rope_geom(*rope, batch, T, kv_heads);
+    }
     fw->scale = 1.f / std::sqrt((float)dh);
     // the core's own size guards (nk_attention.hip: mask words and projection elements below 2^31): past them the decode kernels
     // take the prefill instead of a refused call
     const long long tiles = (T + 31) / 32;
     const bool core_fits = (long long)batch * heads * tiles * tiles < (1ll << 31) / 32 && (long long)n * 3 * d_model < (1ll << 31);
     fw->core = fresh && T >= 2 && core_fits && nk_attention_supported(T, dh, 0.0, 0) != 0;
-    if (!fw->core) fw->ws = cache.workspace(T);
+    if (!fw->core) fw->ws = cache.workspace(T, heads);  // one partial per QUERY head
+    else if (kv_heads != heads) {  // nothing is allocated inside forward()
+        fw->kf = zeros_like(x.data, Shape{n, d_model}); fw->vf = zeros_like(x.data, Shape{n, d_model});
+        if (fw->qkv) fw->qf = zeros_like(x.data, Shape{n, d_model});
+    }
     static_assert(sizeof(int) == sizeof(float), "the start positions travel in an f32 array");
     fw->start = std::make_shared<HipArray>(x.device(), Shape{batch}, HipArray::Uninit{});
     fw->start->upload(reinterpret_cast<const float*>(cache.lens().data()));

@@ -314,6 +314,10 @@ class Var {
     // first `rot` columns of every head rotated by the angles of the row's position, ONE node.  Panics on a shape mismatch or
     // T > max_pos.
     Var rope(const nn::RotaryEmbedding& rotary, int batch, int heads) const;
+    // Grouped-query attention (ours; semantics at nk_repeat_kv_fwd in neuronika_hip.h): a (rows, kv_heads*head_dim) value with every
+    // head written `groups` times, (rows, kv_heads*groups*head_dim) - what the attention core reads as the keys / values of
+    // `kv_heads*groups` query heads.  One forward node, a bit-exact copy.
+    Var repeat_kv(int groups, int head_dim) const;
     // The next token of every sample of (batch*T, V) logits (ours; semantics at nk_sample_fwd in neuronika_hip.h): a (batch,) value of
     // ids in f32, drawn from the LAST row of each sample, ONE node, no gradient.  Panics when batch does not divide the rows.
     Var sample(const nn::Sampler& sampler, int batch) const;
@@ -463,6 +467,9 @@ class VarDiff {
     // one forward and one backward node; the rotation is orthogonal, so the backward (the same kernel with the sign of the sine
     // flipped) holds the table and the geometry only
     VarDiff rope(const nn::RotaryEmbedding& rotary, int batch, int heads) const;
+    // `Var::repeat_kv` with one backward entry: the gradients of the copies summed in ascending copy order (nk_repeat_kv_bwd); the
+    // first writer of the input's gradient takes the assign form.
+    VarDiff repeat_kv(int groups, int head_dim) const;
     VarDiff unsqueeze(int axis) const;
     // the differentiable max-pool node owns the int32 offsets of the selected elements (4 bytes per output)
     VarDiff max_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding) const;
@@ -882,7 +889,7 @@ struct RotaryEmbedding {
 
 // The keys and values of one causal attention layer, kept on the device between the steps of incremental decoding (ours: the
 // reference has no such thing; semantics at nk_kv_cache_append / nk_attention_decode_fwd in neuronika_hip.h).  Kc, Vc are
-// (batch, heads, capacity, head_dim), head-major, allocated once and never initialised: nothing past a sample's length is read
+// (batch, heads, capacity, head_dim) - `heads` is the layer's kv_heads - head-major, allocated once and never initialised: nothing past a sample's length is read
 // into a result.  The lengths live on the host; `MultiheadAttention::forward_step` advances them when it BUILDS its node.
 //   reset()      every length back to 0 (the buffers are kept)
 //   truncate(l)  every sample to a length no longer than its current one.  This is what makes ragged prompts work - prefill a
@@ -894,16 +901,16 @@ struct KvCache {
     const std::vector<int>& lens() const { return lens_; }
     void reset();
     void truncate(const std::vector<int>& lens);
-    // used by forward_step: the buffers, the scratch of nk_attention_decode_fwd (sized for T = 1 at construction, regrown when a
-    // larger T first arrives; a node keeps the one it was built with alive), and the lengths after a step of T rows
+    // used by forward_step: the buffers, the scratch of nk_attention_decode_fwd (sized for T = 1 and `heads` query heads at
+    // construction, regrown when a larger T or a grouped layer's larger query head count first arrives; a node keeps the one it was built with alive), and the lengths after a step of T rows
     Shared<HipArray> k, v;
-    Shared<HipArray> workspace(int T);
+    Shared<HipArray> workspace(int T, int query_heads);
     void advance(int T);
 
    private:
     std::vector<int> lens_;
     Shared<HipArray> ws_;
-    int ws_T_ = 0;
+    int ws_T_ = 0, ws_H_ = 0;
 };
 
 // Multi-head attention composed from reference ops (the module does not exist in the reference;
@@ -912,12 +919,18 @@ struct KvCache {
 struct MultiheadAttention {
     Linear q, k, v, o;
     int d_model, heads;
+    // Grouped-query attention: `kv_heads` key / value heads (a divisor of `heads`; == heads: the module and the graphs of plain
+    // multi-head attention, bit for bit), each shared by heads / kv_heads query heads.  k and v are (kv_heads*dh, d_model).  With
+    // kv_heads < heads, forward() takes the unpacked branches below with K and V repeated in front of them (`VarDiff::repeat_kv`;
+    // rope rotates kv_heads heads of K), forward_step() appends kv_heads heads to a cache built with kv_heads and attends through
+    // nk_attention_decode_gqa_fwd, where the query heads of a group share one read of their keys and values.
+    int kv_heads;
     Dropout drop;
     bool fused = true;  // scale + softmax + dropout as one node (false: three reference nodes)
     bool strided_heads = true;  // attention GEMMs read Q/K/V and write O in the projection layout (false: split/merge copies)
     bool fused_core = true;     // scores -> probabilities -> context as one node on the fused attention kernels (dh in {32, 64, 128}, any S)
-    // The three projection weights (and biases, and their gradients) are views of ONE (3*d_model, d_model) allocation, rows
-    // [Wq; Wk; Wv]: with `packed_qkv` the projections run as one GEMM with N = 3*d_model, their input gradient as one GEMM
+    // The three projection weights (and biases, and their gradients) are views of ONE (3*d_model, d_model) allocation -
+    // (d_model + 2*kv_heads*dh, d_model) with kv_heads < heads - rows [Wq; Wk; Wv]: with `packed_qkv` the projections run as one GEMM with N = 3*d_model, their input gradient as one GEMM
     // with K = 3*d_model, the weight gradients as one GEMM with M = 3*d_model, and the fused attention kernels read Q, K, V
     // as column blocks of the packed output (`nk_attention_qkv_*`).  q / k / v stay ordinary `Linear`s over those views
     // (optimizers, serde and the data-parallel exchange see three parameters as before).  false: three Linear nodes.
@@ -935,8 +948,10 @@ struct MultiheadAttention {
     // keys.  Panics: rope->head_dim != d_model / heads, S > max_pos (forward), cache.capacity > max_pos (forward_step).
     Shared<RotaryEmbedding> rope;
     MultiheadAttention(DevicePtr dev, int d_model, int heads, double p, uint64_t seed);
-    // four Linear layers built elsewhere (e.g. deserialised): their weights are NOT packed, `packed_qkv` is off
-    MultiheadAttention(Linear q, Linear k, Linear v, Linear o, int heads, double p);
+    MultiheadAttention(DevicePtr dev, int d_model, int heads, int kv_heads, double p, uint64_t seed);
+    // four Linear layers built elsewhere (e.g. deserialised): their weights are NOT packed, `packed_qkv` is off.  kv_heads 0 = heads;
+    // k and v must be (kv_heads * d_model / heads, d_model)
+    MultiheadAttention(Linear q, Linear k, Linear v, Linear o, int heads, double p, int kv_heads = 0);
     VarDiff forward(const VarDiff& x, int batch) const;  // x: (batch*seq, d_model)
     // Incremental decoding: the causal forward, one slice of T = rows / batch positions at a time, in inference.  x holds the NEW
     // positions only, (batch*T, d_model); the result, (batch*T, d_model) without a gradient, equals rows lens[b] .. lens[b] + T - 1
@@ -946,8 +961,10 @@ struct MultiheadAttention {
     // forward() again writes the same rows to the same places.  Attention part: every start 0, T >= 2 and a head size the fused
     // core takes -> the causal core in its inference form (no (T, T) tensor); otherwise the split-KV decode kernels over
     // (b, h, t), which also covers chunked prefill (T > 1 at start > 0).
+    // With kv_heads < heads the cache is built with kv_heads as its head count; a fresh prefill repeats the step's K and V rows
+    // into temporaries of the node for the causal core, every other step runs nk_attention_decode_gqa_fwd.
     // Panics: causal == false; dropout active (train mode and p > 0: call drop.eval() first); any lens[b] + T > capacity; a
-    // batch / heads / head size that differs from the cache's.
+    // batch / head size that differs from the cache's; cache.heads != kv_heads.
     Var forward_step(const Var& x, int batch, KvCache& cache) const;
 
    private:

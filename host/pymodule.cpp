@@ -512,6 +512,11 @@ PYBIND11_MODULE(_tape, m) {
              "Rotate the first `rot` columns of every head of a (batch*T, heads*head_dim) value by the angles of positions 0 .. T-1.");
     py::reinterpret_borrow<py::class_<VarDiff>>(m.attr("VarDiff"))
         .def("rope", &VarDiff::rope, py::arg("rotary"), py::arg("batch"), py::arg("heads"));
+    py::reinterpret_borrow<py::class_<Var>>(m.attr("Var"))
+        .def("repeat_kv", &Var::repeat_kv, py::arg("groups"), py::arg("head_dim"),
+             "Every head of a (rows, kv_heads*head_dim) value written `groups` times: (rows, kv_heads*groups*head_dim), a bit-exact copy.");
+    py::reinterpret_borrow<py::class_<VarDiff>>(m.attr("VarDiff"))
+        .def("repeat_kv", &VarDiff::repeat_kv, py::arg("groups"), py::arg("head_dim"));
     py::class_<nn::Sampler>(nn, "Sampler")
         .def(py::init<DevicePtr, float, int, float, uint64_t>(), py::arg("dev"), py::arg("temperature") = 1.0f, py::arg("top_k") = 0,
              py::arg("top_p") = 1.0f, py::arg("seed") = 0,
@@ -531,10 +536,12 @@ PYBIND11_MODULE(_tape, m) {
         .def("sample", &Var::sample, py::arg("sampler"), py::arg("batch"),
              "The ids of the last position of every sample of (batch*T, V) logits, drawn by `sampler` on the device.");
     py::class_<nn::MultiheadAttention>(nn, "MultiheadAttention")
-        .def(py::init<DevicePtr, int, int, double, uint64_t>(), py::arg("dev"), py::arg("d_model"), py::arg("heads"),
-             py::arg("p") = 0.0, py::arg("seed") = 0)
-        .def(py::init<nn::Linear, nn::Linear, nn::Linear, nn::Linear, int, double>(), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
-             py::arg("heads"), py::arg("p") = 0.0)  // four layers built elsewhere: not packed
+        // kv_heads = 0: heads (plain multi-head attention); a divisor of heads: grouped-query attention, k and v (kv_heads*dh, d_model)
+        .def(py::init([](DevicePtr dev, int d_model, int heads, double p, uint64_t seed, int kv_heads) {
+                 return nn::MultiheadAttention(std::move(dev), d_model, heads, kv_heads == 0 ? heads : kv_heads, p, seed); }),
+             py::arg("dev"), py::arg("d_model"), py::arg("heads"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("kv_heads") = 0)
+        .def(py::init<nn::Linear, nn::Linear, nn::Linear, nn::Linear, int, double, int>(), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+             py::arg("heads"), py::arg("p") = 0.0, py::arg("kv_heads") = 0)  // four layers built elsewhere: not packed
         .def_readwrite("q", &nn::MultiheadAttention::q)   // public, assignable members in the C++ mirror as well
         .def_readwrite("k", &nn::MultiheadAttention::k)
         .def_readwrite("v", &nn::MultiheadAttention::v)
@@ -548,6 +555,7 @@ PYBIND11_MODULE(_tape, m) {
         .def_readwrite("rope", &nn::MultiheadAttention::rope)  // a shared RotaryEmbedding; None clears it
         .def_readonly("d_model", &nn::MultiheadAttention::d_model)
         .def_readonly("heads", &nn::MultiheadAttention::heads)
+        .def_readonly("kv_heads", &nn::MultiheadAttention::kv_heads)
         .def("forward", &nn::MultiheadAttention::forward)
         .def("forward_step", &nn::MultiheadAttention::forward_step, py::arg("x"), py::arg("batch"), py::arg("cache"),
              "Incremental decoding: x holds the new positions only, (batch*T, d_model); returns (batch*T, d_model) without a gradient. "

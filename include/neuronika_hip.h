@@ -865,7 +865,8 @@ int nk_attention_qkv_causal_bwd(nk_device* dev, float* dQKV, float* dS, float* d
  * positions.  `start`: a DEVICE array of B int32, each sample's length before this step (per sample: ragged batches).
  * nk_kv_cache_append: row b*T + t of K / V (row stride ld floats) goes to position start[b] + t of every head of sample b, head h
  *   taking columns h*dh .. h*dh + dh - 1 of the row.  K = QKV + d, V = QKV + 2d, ld = 3d addresses a packed projection output
- *   (d = H*dh); ld = d separate projections.  A bit-exact copy.  A row whose position would be >= cap (or < 0) is NOT written -
+ *   (d = H*dh); ld = d separate projections.  A grouped-query layer's (B, Hkv, cap, dh) caches take the same call with H = Hkv,
+ *   K = QKV + d, V = QKV + d + dkv, ld = d + 2*dkv (d = heads*dh, dkv = Hkv*dh; see grouped-query attention below).  A bit-exact copy.  A row whose position would be >= cap (or < 0) is NOT written -
  *   never out of bounds; nothing else of the cache is touched.
  * nk_attention_decode_fwd: Q row b*T + t has stride ldq; O is (B*T, H*dh).  Query (b, t) reads keys < min(start[b] + t + 1, cap)
  *   (none, for a negative start: the output row is 0).  Split-KV: a problem (b, h, t) is cut into chunks of
@@ -885,6 +886,39 @@ int nk_attention_decode_fwd(nk_device* dev, const float* Q, int ldq, const float
                             float* workspace, int B, int T, int H, int dh, int cap, float scale);
 size_t nk_attention_decode_workspace(int B, int T, int H, int dh, int cap);
 int nk_attention_decode_chunk(int dh);
+/* ------------------------------------------------------------------ grouped-query attention --
+ * Ours (the reference has one head count): GQA, Ainslie et al. 2023, as LLaMA-2-70B / 3, Mistral and Qwen use it; multi-query
+ * (Shazeer 2019) is Hkv = 1.  H query heads, Hkv key / value heads, H % Hkv == 0, G = H / Hkv: query head h attends to kv head
+ * h / G.  d = H*dh, dkv = Hkv*dh; a packed projection output is (rows, d + 2*dkv) = [Q | K | V].
+ * The cache of a grouped layer is (B, Hkv, cap, dh) - G times less memory and decode traffic.  nk_kv_cache_append serves it as it
+ * is: call it with H = Hkv, K = QKV + d, V = QKV + d + dkv, ld = d + 2*dkv.
+ * nk_attention_decode_gqa_fwd: Kc, Vc are (B, Hkv, cap, dh); Q (row stride ldq, head h at columns h*dh ..), O (B*T, H*dh), start,
+ *   scale and `workspace` (nk_attention_decode_workspace(B, T, H, dh, cap) floats, the per-(b, t, h) layout) are those of
+ *   nk_attention_decode_fwd.  Query head h of row b*T + t reads the n = min(start[b] + t + 1, cap) first keys of kv head h / G.
+ *   dh in {32, 64, 128}: one block per ((b, t, kv head), batch of at most 8 query heads of the group, chunk of
+ *   nk_attention_decode_chunk(dh) keys) loads its chunk of K and V ONCE into registers and runs nk_attention_decode_fwd's per-head
+ *   arithmetic for each of its heads; a group of more than 8 heads takes ceil(G / 8) blocks.  Any other dh: a scalar kernel without
+ *   sharing.  The merge of the partials is nk_attention_decode_fwd's.  No atomics.
+ *   Bit contract: the bits of o for (b, h, t) are those nk_attention_decode_fwd gives for the same query on a cache whose head h
+ *   holds kv head h / G's rows - same chunking, same order - so they depend on that problem's q, its n keys / values and scale
+ *   ONLY: not on G, on the heads that share the block, on B, T, cap or the cache's tail.  Hkv == H forwards to
+ *   nk_attention_decode_fwd: the same launches.
+ *   NK_ERR_INVALID, nothing written: Hkv <= 0, Hkv > H, H % Hkv != 0, and everything nk_attention_decode_fwd refuses.
+ * nk_repeat_kv_*: the training / prefill side.  The fused core keeps running on H heads: kv head k is written G times in front of
+ *   it and the gradients of the copies are summed behind it.  x / dx are `rows` rows of Hkv*dh floats (row stride ldx / lddx),
+ *   y / g `rows` rows of Hkv*G*dh floats (row stride ldy / ldg).
+ *   fwd:        y[r, (k*G + j)*dh + e] = x[r, k*dh + e], 0 <= j < G: a bit-exact copy.
+ *   bwd:        dx[r, k*dh + e] += s, s = ((g_0 + g_1) + g_2) + ... with g_j = g[r, (k*G + j)*dh + e], j ascending, in f32;
+ *   bwd_assign: dx[r, k*dh + e] = s.  The bits are fixed by that order (G = 1: an add / a copy).
+ *   16-byte accesses when dh % 4 == 0 and both strides and pointers allow it, scalar otherwise; row offsets are 64-bit.  Columns
+ *   outside [0, Hkv*dh) of x / dx and [0, Hkv*G*dh) of y / g are never touched: the operands may be column blocks of packed
+ *   buffers.  The operands must not overlap.  No atomics, no LDS.
+ *   NK_ERR_INVALID: non-positive rows / Hkv / G / dh, a null pointer, a row stride below the operand's width, Hkv*G*dh >= 2^31. */
+int nk_attention_decode_gqa_fwd(nk_device* dev, const float* Q, int ldq, const float* Kc, const float* Vc, const int* start, float* O,
+                                float* workspace, int B, int T, int H, int Hkv, int dh, int cap, float scale);
+int nk_repeat_kv_fwd(nk_device* dev, const float* x, int ldx, float* y, int ldy, int rows, int Hkv, int G, int dh);
+int nk_repeat_kv_bwd(nk_device* dev, float* dx, int lddx, const float* g, int ldg, int rows, int Hkv, int G, int dh);
+int nk_repeat_kv_bwd_assign(nk_device* dev, float* dx, int lddx, const float* g, int ldg, int rows, int Hkv, int G, int dh);
 /* ------------------------------------------------------------------ rotary position embedding --
  * Ours (the reference has no position encoding of any kind): RoPE, Su et al. 2021 (RoFormer), as LLaMA / Mistral / Qwen / GPT-NeoX /
  * Phi apply it to the query and key rows in front of the attention scores.

@@ -529,6 +529,12 @@ pub struct MultiheadAttention {
     pub o: Linear,
     pub d_model: usize,
     pub heads: usize,
+    /// Grouped-query attention (the tested mirror is `nn::MultiheadAttention::kv_heads` in `host/neuronika.hpp`): key / value heads, a
+    /// divisor of `heads`; `heads` after `new`.  With fewer, `qkv` is `Linear(d_model, d_model + 2 * kv_heads * dh)`, rows
+    /// `[Wq; Wk; Wv]`, `forward_step` appends `kv_heads` heads to a `KvCache` built with `kv_heads` and attends through
+    /// `nk_attention_decode_gqa_fwd`.  The TRAINING forward of a grouped layer is not mirrored here: it is composed from separate
+    /// projections, `HipVarDiff::repeat_kv` on K and V and `heads_attention`, as `host/neuronika.cpp` composes it.
+    pub kv_heads: usize,
     pub dropout: Dropout,
     /// Causal self-attention: query `r` of a sample attends to the keys `<= r` of that sample (`P = dropout(softmax(scores * scale +
     /// M))`, `M` = 0 on and below the diagonal, -inf above).  Read by `forward` when it builds the graph; `false` after `new`.
@@ -547,7 +553,20 @@ impl MultiheadAttention {
         // each of the three row blocks is initialised as its own Linear(d_model, d_model): U(-k, k), k = 1 / sqrt(d_model) -
         // the fan-in of the packed layer is d_model too, so one draw over (3 d, d) follows the same law
         Self { qkv: Linear::new(d_model, 3 * d_model, device), o: Linear::new(d_model, d_model, device), d_model, heads, dropout: Dropout::new(p),
-               causal: false, rope: None }
+               kv_heads: heads, causal: false, rope: None }
+    }
+
+    /// `new` with `kv_heads < heads` key / value heads shared by `heads / kv_heads` query heads each.
+    pub fn new_grouped(d_model: usize, heads: usize, kv_heads: usize, p: f64, device: &Device) -> Self {
+        assert!(kv_heads > 0 && kv_heads <= heads && heads % kv_heads == 0, "MultiheadAttention: kv_heads must be positive and divide heads");
+        let mut layer = Self::new(d_model, heads, p, device);
+        layer.qkv = Linear::new(d_model, d_model + 2 * (d_model / heads) * kv_heads, device);
+        layer.kv_heads = kv_heads;
+        layer
+    }
+
+    fn dkv(&self) -> usize {
+        self.d_model / self.heads * self.kv_heads
     }
 
     /// Row range of the packed weight (and element range of the packed bias) holding the query / key / value projection.
@@ -556,17 +575,18 @@ impl MultiheadAttention {
     }
 
     pub fn k_rows(&self) -> std::ops::Range<usize> {
-        self.d_model..2 * self.d_model
+        self.d_model..self.d_model + self.dkv()
     }
 
     pub fn v_rows(&self) -> std::ops::Range<usize> {
-        2 * self.d_model..3 * self.d_model
+        self.d_model + self.dkv()..self.d_model + 2 * self.dkv()
     }
 
     /// `input`: `(batch * seq, d_model)`, rows of a sample contiguous.
     pub fn forward(&self, input: HipVarDiff<Ix2>, batch: usize) -> HipVarDiff<Ix2> {
         let rows = input.shape()[0];
         assert!(batch > 0 && rows % batch == 0, "MultiheadAttention: rows must be a multiple of batch");
+        assert!(self.kv_heads == self.heads, "MultiheadAttention::forward: the packed node takes kv_heads == heads (see `kv_heads`)");
         let (seq, dh) = (rows / batch, self.d_model / self.heads);
         let scale = 1. / (dh as f32).sqrt();
         let packed = self.qkv.forward(input);
@@ -599,7 +619,8 @@ impl MultiheadAttention {
         assert!(batch > 0 && rows > 0 && rows % batch == 0, "MultiheadAttention: rows must be a multiple of batch");
         let dh = self.d_model / self.heads;
         let (cb, ch, capacity, cd) = cache.buffers.geometry();
-        assert!((cb, ch, cd) == (batch, self.heads, dh), "MultiheadAttention::forward_step: the cache was built for another geometry");
+        assert!((cb, ch, cd) == (batch, self.kv_heads, dh),
+                "MultiheadAttention::forward_step: the cache holds {} heads, the layer has {} kv heads (of {} query heads)", ch, self.kv_heads, self.heads);
         let start = cache.lens();
         assert!(start.iter().all(|&l| l + rows / batch <= capacity), "MultiheadAttention::forward_step: the step exceeds the capacity");
         let scale = 1. / (dh as f32).sqrt();
@@ -607,11 +628,11 @@ impl MultiheadAttention {
         let packed = match &self.rope {
             Some(r) => {
                 assert!(r.table.head_dim() == dh && capacity <= r.table.max_pos(), "MultiheadAttention::forward_step: rope does not fit the head size or the capacity");
-                packed.rope_in_place(&r.table, batch, 2 * self.heads, Some(&start))
+                packed.rope_in_place(&r.table, batch, self.heads + self.kv_heads, Some(&start))
             }
             None => packed,
         };
-        let context = packed.packed_decode_attention(&cache.buffers, &start, scale);
+        let context = packed.packed_decode_attention(&cache.buffers, self.heads, &start, scale);
         cache.advance(rows / batch);
         context.linear(self.o.weight.detached(), self.o.bias.detached(), false)
     }

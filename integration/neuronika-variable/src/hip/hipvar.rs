@@ -24,7 +24,7 @@ use super::{
         DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, RmsNorm, RmsNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
         decode_chunk, decode_workspace, PackedDecodeAttention,
-        rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
+        RepeatKv, RepeatKvBackward, RepeatKvGeometry, rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
         sample_stage_limit, Sample, SampleParams,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
         ReLUBackward, ReluMask, Softmax, SoftmaxBackward,
@@ -555,7 +555,8 @@ pub struct KvBuffers {
     pub(crate) values: Shared<HipArray<Ix4>>,
     workspace: RefCell<Shared<HipArray<Ix1>>>,
     workspace_rows: Cell<usize>,
-    geometry: (usize, usize, usize, usize), // batch, heads, capacity, dh
+    workspace_heads: Cell<usize>, // query heads the scratch is sized for: more than `heads` once a grouped-query layer has used it
+    geometry: (usize, usize, usize, usize), // batch, heads (kv heads of a grouped-query layer), capacity, dh
 }
 
 impl KvBuffers {
@@ -564,7 +565,7 @@ impl KvBuffers {
         let dim = ndarray::Dim([batch, heads, capacity, dh]);
         Self { keys: shared(dim, device), values: shared(dim, device),
                workspace: RefCell::new(shared(ndarray::Dim([decode_workspace(batch, 1, heads, dh, capacity)]), device)),
-               workspace_rows: Cell::new(1), geometry: (batch, heads, capacity, dh) }
+               workspace_rows: Cell::new(1), workspace_heads: Cell::new(heads), geometry: (batch, heads, capacity, dh) }
     }
 
     /// `(batch, heads, capacity, dh)`
@@ -577,11 +578,13 @@ impl KvBuffers {
         decode_chunk(self.geometry.3)
     }
 
-    fn workspace_for(&self, rows: usize, device: &Device) -> Shared<HipArray<Ix1>> {
-        if rows > self.workspace_rows.get() {
-            let (batch, heads, capacity, dh) = self.geometry;
+    fn workspace_for(&self, rows: usize, query_heads: usize, device: &Device) -> Shared<HipArray<Ix1>> {
+        if rows > self.workspace_rows.get() || query_heads > self.workspace_heads.get() {
+            let (batch, _, capacity, dh) = self.geometry;
+            let (rows, heads) = (rows.max(self.workspace_rows.get()), query_heads.max(self.workspace_heads.get()));
             *self.workspace.borrow_mut() = shared(ndarray::Dim([decode_workspace(batch, rows, heads, dh, capacity)]), device);
             self.workspace_rows.set(rows);
+            self.workspace_heads.set(heads);
         }
         self.workspace.borrow().clone()
     }
@@ -591,21 +594,25 @@ impl HipVar<Ix2> {
     /// One step of incremental decoding: `self` is the `(batch*rows, 3*heads*dh)` packed projection of the NEW positions; its key
     /// and value blocks are appended to `buffers` at `start[b] + t` and every new row attends to the keys `< start[b] + t + 1` of
     /// its sample (`nk_kv_cache_append`, `nk_attention_decode_fwd`).  `start`: each sample's length before the step, captured
-    /// here.  Output `(batch*rows, heads*dh)`, no gradient.
-    pub fn packed_decode_attention(self, buffers: &KvBuffers, start: &[usize], scale: f32) -> HipVar<Ix2> {
+    /// here.  Output `(batch*rows, query_heads*dh)`, no gradient.  `query_heads`: the heads of Q - the buffers' head count for plain
+    /// multi-head attention, a multiple of it for a grouped-query layer, whose packed projection is `(rows, (query_heads +
+    /// 2*heads)*dh)` and whose step runs `nk_attention_decode_gqa_fwd`.
+    pub fn packed_decode_attention(self, buffers: &KvBuffers, query_heads: usize, start: &[usize], scale: f32) -> HipVar<Ix2> {
         let device = self.device();
         let (batch, heads, capacity, dh) = buffers.geometry();
         let total = self.data.borrow().dimension()[0];
         assert!(start.len() == batch && total % batch == 0 && total > 0, "packed_decode_attention: rows must be a positive multiple of the batch");
-        assert!(self.data.borrow().dimension()[1] == 3 * heads * dh, "packed_decode_attention: the input must be (rows, 3 * heads * dh)");
+        assert!(query_heads >= heads && query_heads % heads == 0, "packed_decode_attention: query_heads must be a multiple of the cache's heads");
+        assert!(self.data.borrow().dimension()[1] == (query_heads + 2 * heads) * dh,
+                "packed_decode_attention: the input must be (rows, (query_heads + 2 * heads) * dh)");
         let rows = total / batch;
         assert!(start.iter().all(|&s| s + rows <= capacity), "packed_decode_attention: the step exceeds the capacity of the cache");
         let cells: Vec<f32> = start.iter().map(|&s| f32::from_bits(s as u32)).collect();
         let start = HipArray::from_slice(&cells, ndarray::Dim([batch]), device.clone());
         let geometry = Heads { batch: batch as i32, seq: rows as i32, heads: heads as i32, dh: dh as i32 };
-        let data = shared(ndarray::Dim([total, heads * dh]), &device);
-        let op = PackedDecodeAttention::new(geometry, capacity as i32, self.data, buffers.keys.clone(), buffers.values.clone(), start,
-                                            buffers.workspace_for(rows, &device), data.clone(), scale);
+        let data = shared(ndarray::Dim([total, query_heads * dh]), &device);
+        let op = PackedDecodeAttention::new(geometry, query_heads as i32, capacity as i32, self.data, buffers.keys.clone(), buffers.values.clone(), start,
+                                            buffers.workspace_for(rows, query_heads, &device), data.clone(), scale);
         HipVar::node(data, Rc::new(op), self.history)
     }
 }
@@ -746,6 +753,38 @@ impl HipVarDiff<Ix2> {
         let var = self.var.rope_in_place(rotary, batch, heads, None);
         let grad = self.grad;
         let op: Rc<dyn Backward> = Rc::new(RopeInPlaceBackward::new(geometry, rotary.table.clone(), grad.clone()));
+        HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
+    }
+}
+
+fn repeat_kv_geometry(dim: ndarray::Ix2, groups: usize, head_dim: usize) -> RepeatKvGeometry {
+    assert!(groups > 0 && head_dim > 0 && dim[0] > 0 && dim[1] > 0 && dim[1] % head_dim == 0,
+            "repeat_kv: the input must be (rows, kv_heads*head_dim)");
+    assert!(dim[0] * dim[1] * groups <= i32::MAX as usize, "repeat_kv: the output must fit 31 bits");
+    RepeatKvGeometry { rows: dim[0] as i32, kv_heads: (dim[1] / head_dim) as i32, groups: groups as i32, dh: head_dim as i32 }
+}
+
+impl HipVar<Ix2> {
+    /// Grouped-query attention: every head of a `(rows, kv_heads*head_dim)` value written `groups` times, `(rows,
+    /// kv_heads*groups*head_dim)` - what the attention core reads as the keys / values of its query heads.  ONE node
+    /// (`nk_repeat_kv_fwd`), a bit-exact copy.
+    pub fn repeat_kv(self, groups: usize, head_dim: usize) -> HipVar<Ix2> {
+        let dim = self.data.borrow().dimension();
+        let geometry = repeat_kv_geometry(dim, groups, head_dim);
+        let data = shared(ndarray::Dim([dim[0], dim[1] * groups]), &self.device());
+        let op = RepeatKv::new(geometry, self.data, data.clone());
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+}
+
+impl HipVarDiff<Ix2> {
+    /// `HipVar::repeat_kv` with its backward entry (`RepeatKvBackward`: the gradients of the copies summed in ascending order).
+    pub fn repeat_kv(self, groups: usize, head_dim: usize) -> HipVarDiff<Ix2> {
+        let dim = self.var.data.borrow().dimension();
+        let geometry = repeat_kv_geometry(dim, groups, head_dim);
+        let var = self.var.repeat_kv(groups, head_dim);
+        let grad = Rc::new(Gradient::hip_zeros(ndarray::Dim([dim[0], dim[1] * groups]), var.device()));
+        let op: Rc<dyn Backward> = Rc::new(RepeatKvBackward::new(geometry, self.grad, grad.clone()));
         HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
     }
 }

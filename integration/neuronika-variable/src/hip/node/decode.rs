@@ -20,12 +20,15 @@ pub(crate) fn decode_workspace(batch: usize, rows: usize, heads: usize, dh: usiz
 
 /// One step of incremental decoding over PACKED projections (ours: the reference has no such node; semantics in
 /// `include/neuronika_hip.h`): `packed` is the `(batch*rows, 3*heads*dh)` output of one `Linear` over `[Wq; Wk; Wv]` for the NEW
-/// positions only.  The forward appends its key and value blocks to the `(batch, heads, capacity, dh)` caches at
+/// positions only - `(batch*rows, (query_heads + 2*heads)*dh)` for a grouped-query layer, where `geometry.heads` counts the kv heads
+/// the caches hold and `query_heads` (a multiple of it) the heads of Q and of the output.  The forward appends its key and value blocks to the `(batch, heads, capacity, dh)` caches at
 /// `start[b] + t` (`nk_kv_cache_append`) and lets every new row attend to the keys `< start[b] + t + 1` of its sample
-/// (`nk_attention_decode_fwd`: split-KV partials merged in chunk order, no atomics).  `start` is fixed when the node is built,
+/// (`nk_attention_decode_fwd`: split-KV partials merged in chunk order, no atomics; `nk_attention_decode_gqa_fwd` when
+/// `query_heads > heads`: the query heads of a group share one read of their keys and values).  `start` is fixed when the node is built,
 /// so a second `forward()` writes the same rows to the same places.  Inference only: there is no backward node.
 pub(crate) struct PackedDecodeAttention {
-    geometry: Heads, // `seq` = new rows per sample
+    geometry: Heads, // `seq` = new rows per sample, `heads` = kv heads
+    query_heads: i32,
     capacity: i32,
     packed: Shared<HipArray<Ix2>>,
     keys: Shared<HipArray<Ix4>>,
@@ -38,9 +41,9 @@ pub(crate) struct PackedDecodeAttention {
 
 impl PackedDecodeAttention {
     #[allow(clippy::too_many_arguments)]
-    pub(crate) fn new(geometry: Heads, capacity: i32, packed: Shared<HipArray<Ix2>>, keys: Shared<HipArray<Ix4>>, values: Shared<HipArray<Ix4>>,
+    pub(crate) fn new(geometry: Heads, query_heads: i32, capacity: i32, packed: Shared<HipArray<Ix2>>, keys: Shared<HipArray<Ix4>>, values: Shared<HipArray<Ix4>>,
                       start: HipArray<Ix1>, workspace: Shared<HipArray<Ix1>>, data: Shared<HipArray<Ix2>>, scale: f32) -> Self {
-        Self { geometry, capacity, packed, keys, values, start, workspace, data, scale }
+        Self { geometry, query_heads, capacity, packed, keys, values, start, workspace, data, scale }
     }
 }
 
@@ -51,16 +54,24 @@ impl Forward for PackedDecodeAttention {
         let mut ws = self.workspace.borrow_mut();
         let mut out = self.data.borrow_mut();
         let h = self.geometry;
-        let d = (h.heads * h.dh) as usize;
+        let (d, dkv) = ((self.query_heads * h.dh) as usize, (h.heads * h.dh) as usize);
+        let ld = (d + 2 * dkv) as i32;
         let start = self.start.as_ptr() as *const i32;
         let dev = qkv.device().as_raw();
         ffi::check(unsafe {
-            ffi::nk_kv_cache_append(dev, kc.as_mut_ptr(), vc.as_mut_ptr(), qkv.as_ptr().add(d), qkv.as_ptr().add(2 * d), 3 * d as i32, start,
+            ffi::nk_kv_cache_append(dev, kc.as_mut_ptr(), vc.as_mut_ptr(), qkv.as_ptr().add(d), qkv.as_ptr().add(d + dkv), ld, start,
                                     h.batch, h.seq, h.heads, h.dh, self.capacity)
         });
-        ffi::check(unsafe {
-            ffi::nk_attention_decode_fwd(dev, qkv.as_ptr(), 3 * d as i32, kc.as_ptr(), vc.as_ptr(), start, out.as_mut_ptr(), ws.as_mut_ptr(),
-                                         h.batch, h.seq, h.heads, h.dh, self.capacity, self.scale)
-        });
+        if self.query_heads == h.heads {
+            ffi::check(unsafe {
+                ffi::nk_attention_decode_fwd(dev, qkv.as_ptr(), ld, kc.as_ptr(), vc.as_ptr(), start, out.as_mut_ptr(), ws.as_mut_ptr(),
+                                             h.batch, h.seq, h.heads, h.dh, self.capacity, self.scale)
+            });
+        } else {
+            ffi::check(unsafe {
+                ffi::nk_attention_decode_gqa_fwd(dev, qkv.as_ptr(), ld, kc.as_ptr(), vc.as_ptr(), start, out.as_mut_ptr(), ws.as_mut_ptr(),
+                                                 h.batch, h.seq, self.query_heads, h.heads, h.dh, self.capacity, self.scale)
+            });
+        }
     }
 }

@@ -20,6 +20,7 @@ mod optim;
 mod pointwise;
 mod pooling;
 mod reduction;
+mod repeat_kv;
 mod rms_norm;
 mod rope;
 mod sample;
@@ -40,6 +41,7 @@ pub(crate) use optim::*;
 pub(crate) use pointwise::*;
 pub(crate) use pooling::*;
 pub(crate) use reduction::*;
+pub(crate) use repeat_kv::*;
 pub(crate) use rms_norm::*;
 pub(crate) use rope::*;
 pub(crate) use sample::*;

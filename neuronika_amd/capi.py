@@ -212,6 +212,10 @@ _SIGS = {
     "nk_attention_decode_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float],
     "nk_attention_decode_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_attention_decode_chunk": [C.c_int],
+    "nk_attention_decode_gqa_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float],
+    "nk_repeat_kv_fwd": [VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_repeat_kv_bwd": [VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_repeat_kv_bwd_assign": [VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_rope_table": [VP, VP, C.c_int, C.c_int, C.c_double],
     "nk_rope_fwd": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_rope_bwd": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
@@ -1019,6 +1023,23 @@ def attention_decode_fwd(dev, Q, ldq, Kc, Vc, start, out, workspace, B, T, H, dh
     """Single-query attention over the caches: query (b, t) reads keys < min(start[b] + t + 1, cap); out is (B*T, H*dh);
     workspace: `attention_decode_workspace(B, T, H, dh, cap)` floats."""
     check(lib.nk_attention_decode_fwd(dev.h, _p(Q), ldq, _p(Kc), _p(Vc), _p(start), _p(out), _p(workspace), B, T, H, dh, cap, scale))
+
+
+def attention_decode_gqa_fwd(dev, Q, ldq, Kc, Vc, start, out, workspace, B, T, H, Hkv, dh, cap, scale):
+    """Grouped-query decode: the caches are (B, Hkv, cap, dh), query head h reads kv head h // (H // Hkv); everything else is
+    `attention_decode_fwd`'s, its workspace included.  The heads of a group share one read of their K / V chunk."""
+    check(lib.nk_attention_decode_gqa_fwd(dev.h, _p(Q), ldq, _p(Kc), _p(Vc), _p(start), _p(out), _p(workspace), B, T, H, Hkv, dh, cap, scale))
+
+
+def repeat_kv_fwd(dev, x, ldx, y, ldy, rows, Hkv, G, dh):
+    """y[r, (k*G + j)*dh + e] = x[r, k*dh + e]: kv head k written G times; `view_offset` addresses column blocks of packed buffers."""
+    check(lib.nk_repeat_kv_fwd(dev.h, _p(x), int(ldx), _p(y), int(ldy), int(rows), int(Hkv), int(G), int(dh)))
+
+
+def repeat_kv_bwd(dev, dx, lddx, g, ldg, rows, Hkv, G, dh, assign=False):
+    """dx (+)= the f32 sum of the G copies' gradients in ascending copy order."""
+    fn = lib.nk_repeat_kv_bwd_assign if assign else lib.nk_repeat_kv_bwd
+    check(fn(dev.h, _p(dx), int(lddx), _p(g), int(ldg), int(rows), int(Hkv), int(G), int(dh)))
 
 
 def rope_table(dev, table, max_pos, rot, base=10000.0):
