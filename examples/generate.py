@@ -15,6 +15,11 @@ K and V per token instead of the causal forward over the whole prefix.
     python examples/generate.py [new_tokens] --kv-heads 2    # grouped-query attention: 4 query heads share 2 (or 1: multi-query) key /
                                                       # value heads; the caches are built with that many heads and hold 1/2 (1/4) of
                                                       # the bytes; with --rope --rmsnorm this is the attention block of LLaMA-2-70B / 3
+    python examples/generate.py 240 --window 64 --rolling    # sliding-window attention (Mistral): every position attends to the last
+                                                      # 64 only; --rolling keeps them in a ring of window + prompt - 1 slots per layer
+                                                      # however long the generation runs (here past three times the ring); without
+                                                      # --rolling the caches are linear, long enough for the whole run, and the ids
+                                                      # are the same
 
 The weights are random (fixed seeds): the text means nothing, the mechanics are the point.  The last lines compare every step's
 logits with those of the full causal forward over the same prefix."""
@@ -31,13 +36,14 @@ VOCAB, D_MODEL, HEADS, LAYERS, CONTEXT = 64, 128, 4, 2, 64
 
 
 class Block:
-    def __init__(self, nk, dev, seed, rope=None, norm=None, kv_heads=HEADS):
+    def __init__(self, nk, dev, seed, rope=None, norm=None, kv_heads=HEADS, window=0):
         norm = norm or nk.nn.LayerNorm
         self.ln1, self.ln2 = norm(dev, [D_MODEL]), norm(dev, [D_MODEL])
         self.mha = nk.nn.MultiheadAttention(dev, D_MODEL, HEADS, 0.0, seed, kv_heads=kv_heads)
         self.mha.causal = True
         self.mha.drop.eval()
         self.mha.rope = rope                                             # None: the learned position table below carries the positions
+        self.mha.window = window                                         # 0: every position attends to its whole prefix
         self.up, self.down = nk.nn.Linear(dev, D_MODEL, 4 * D_MODEL, seed + 20), nk.nn.Linear(dev, 4 * D_MODEL, D_MODEL, seed + 22)
         self.act = nk.nn.GELU()
 
@@ -54,14 +60,14 @@ class Block:
 
 
 class Decoder:
-    def __init__(self, nk, dev, rope=False, rmsnorm=False, kv_heads=HEADS):
+    def __init__(self, nk, dev, rope=False, rmsnorm=False, kv_heads=HEADS, window=0, context=CONTEXT):
         self.nk, self.dev = nk, dev
         norm = nk.nn.RMSNorm if rmsnorm else nk.nn.LayerNorm
-        self.tok, self.pos = nk.nn.Embedding(dev, VOCAB, D_MODEL, seed=1), nk.nn.Embedding(dev, CONTEXT, D_MODEL, seed=2)
+        self.tok, self.pos = nk.nn.Embedding(dev, VOCAB, D_MODEL, seed=1), nk.nn.Embedding(dev, context, D_MODEL, seed=2)
         # rotary mode: the queries and keys of every layer are rotated by their position (at lens[b] + t in a step, so the caches
         # hold rotated keys) and nothing is added to the token embedding
-        self.rope = nk.nn.RotaryEmbedding(dev, D_MODEL // HEADS, CONTEXT) if rope else None
-        self.blocks = [Block(nk, dev, 100 * (i + 1), self.rope, norm, kv_heads) for i in range(LAYERS)]
+        self.rope = nk.nn.RotaryEmbedding(dev, D_MODEL // HEADS, context) if rope else None
+        self.blocks = [Block(nk, dev, 100 * (i + 1), self.rope, norm, kv_heads, window) for i in range(LAYERS)]
         self.ln, self.head = norm(dev, [D_MODEL]), nk.nn.Linear(dev, D_MODEL, VOCAB, 7)
 
     def embed(self, ids, first, shape=None):
@@ -116,15 +122,20 @@ def generate_on_device(nk, dev, model, prompt, new_tokens, caches, temperature, 
     return ids, worst
 
 
-def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=0, top_p=1.0, seed=0, rmsnorm=False, kv_heads=HEADS):
+def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=0, top_p=1.0, seed=0, rmsnorm=False, kv_heads=HEADS, window=0,
+         rolling=False):
     import neuronika_amd
     nk = neuronika_amd.tape
     dev = nk.Device(0)
-    model = Decoder(nk, dev, rope, rmsnorm, kv_heads)
     prompt = np.array([[3, 14, 15, 9, 26, 5, 35, 8]])
     batch, n = prompt.shape
-    assert n + new_tokens <= CONTEXT
-    caches = [nk.nn.KvCache(dev, batch, kv_heads, D_MODEL // HEADS, CONTEXT) for _ in range(LAYERS)]   # kv_heads heads per layer
+    context = max(CONTEXT, n + new_tokens)                               # positions the run reaches: the position table / rope table
+    assert window > 0 or not rolling, "--rolling keeps the last positions only: it needs --window"
+    assert window > 0 or context == CONTEXT, "more than %d positions need --window" % CONTEXT
+    model = Decoder(nk, dev, rope, rmsnorm, kv_heads, window, context)
+    # a linear cache holds every position of the run; a rolling one the window and the prompt's rows, whatever the length
+    slots, ring = (window + n - 1, dict(rolling=True)) if rolling else (context, dict())
+    caches = [nk.nn.KvCache(dev, batch, kv_heads, D_MODEL // HEADS, slots, **ring) for _ in range(LAYERS)]   # kv_heads heads per layer
     if device_sample:
         ids, worst = generate_on_device(nk, dev, model, prompt, new_tokens, caches, temperature, top_k, top_p, seed)
     else:
@@ -136,6 +147,8 @@ def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=
             logits = model.logits_step(nxt, ids.shape[1] - 1, caches)    # one token through the layers, K and V from the caches
             worst = max(worst, float(np.abs(logits[:, -1] - model.logits_full(ids)[:, -1]).max()))
     assert caches[0].lens() == [n + new_tokens] * batch
+    if rolling:
+        print("rolling caches of %d slots held the last %d of %d positions" % (slots, window, n + new_tokens))
     print("prompt   ", prompt[0].tolist())
     print("generated", ids[0, n:].tolist())
     print("largest difference between a step's logits and the full causal forward's: %.3g" % worst)
@@ -148,6 +161,8 @@ if __name__ == "__main__":
     ap.add_argument("--rope", action="store_true", help="rotary positions instead of the learned position table")
     ap.add_argument("--rmsnorm", action="store_true", help="nn.RMSNorm in place of the three nn.LayerNorm")
     ap.add_argument("--kv-heads", type=int, default=HEADS, choices=[1, 2, 4], help="key / value heads shared by the %d query heads (grouped-query attention)" % HEADS)
+    ap.add_argument("--window", type=int, default=0, help="sliding-window attention: every position attends to the last WINDOW positions (0 = off)")
+    ap.add_argument("--rolling", action="store_true", help="with --window: rolling caches of window + prompt - 1 slots instead of linear ones")
     ap.add_argument("--device-sample", action="store_true", help="draw the next ids on the device (nn.Sampler); the host reads them once")
     ap.add_argument("--temperature", type=float, default=0.0, help="with --device-sample: 0 = greedy")
     ap.add_argument("--top-k", type=int, default=0, help="with --device-sample: 0 = off")
@@ -155,4 +170,4 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0, help="with --device-sample: the Philox key of the draws")
     a = ap.parse_args()
     main(a.new_tokens, rope=a.rope, device_sample=a.device_sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, rmsnorm=a.rmsnorm,
-         kv_heads=a.kv_heads)
+         kv_heads=a.kv_heads, window=a.window, rolling=a.rolling)

@@ -911,6 +911,8 @@ struct QkvAttentionBwd : Backward {
 // the same rows again.
 struct DecodeStepFwd : Forward {
     int B, T, H, Hkv, dh, cap;  // Hkv == H: plain multi-head attention, the launches of the module without kv_heads
+    int window = 0;             // > 0: every step the core does not take runs nk_attention_decode_window_fwd
+    bool ring = false;          // a rolling cache: position p at slot p % cap
     Shared<HipArray> x, w[3], b[3], wo, bo;  // packed: w[0] / b[0] are the (d + 2 dkv, d) / (d + 2 dkv) storage, the others null
     Shared<HipArray> qkv, q, k, v, ctx, out;
     Shared<HipArray> kc, vc, ws, start;
@@ -937,7 +939,8 @@ struct DecodeStepFwd : Forward {
             rope_inplace(dev, const_cast<float*>(Q), ld, rope, st, rg, false);
             if (!qkv) rope_inplace(dev, const_cast<float*>(K), ldkv, rope, st, rgk, false);
         }
-        check(nk_kv_cache_append(dev, kc->ptr(), vc->ptr(), K, V, ldkv, st, B, T, Hkv, dh, cap));
+        if (ring) check(nk_kv_cache_append_ring(dev, kc->ptr(), vc->ptr(), K, V, ldkv, st, B, T, Hkv, dh, cap));
+        else check(nk_kv_cache_append(dev, kc->ptr(), vc->ptr(), K, V, ldkv, st, B, T, Hkv, dh, cap));
         if (core && Hkv != H) {  // the core runs on H heads of K and V: the step's rows repeated into the node's temporaries
             const int G = H / Hkv;
             check(nk_repeat_kv_fwd(dev, K, ldkv, kf->ptr(), d, n, Hkv, G, dh));
@@ -951,6 +954,9 @@ struct DecodeStepFwd : Forward {
             check(nk_attention_qkv_causal_fwd(dev, qkv->ptr(), nullptr, nullptr, nullptr, ctx->ptr(), B, T, H, dh, scale, 0.0, 0, 0, 0));
         else if (core)
             check(nk_attention_causal_fwd(dev, Q, K, V, nullptr, nullptr, nullptr, ctx->ptr(), B, T, H, dh, scale, 0.0, 0, 0, 0));
+        else if (window > 0)
+            check(nk_attention_decode_window_fwd(dev, Q, ld, kc->ptr(), vc->ptr(), st, ctx->ptr(), ws->ptr(), B, T, H, Hkv, dh, cap, window, ring ? 1 : 0,
+                                                 scale));
         else if (Hkv != H)
             check(nk_attention_decode_gqa_fwd(dev, Q, ld, kc->ptr(), vc->ptr(), st, ctx->ptr(), ws->ptr(), B, T, H, Hkv, dh, cap, scale));
         else
@@ -3119,6 +3125,9 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
     const int rows = x.shape()[0], S = rows / batch, dh = d_model / heads;
     if (rows % batch != 0 || x.shape()[1] != d_model) panic("MultiheadAttention: bad input shape");
     const float scale = 1.f / std::sqrt((float)dh);
+    if (window < 0) panic("MultiheadAttention: window must not be negative, got " + std::to_string(window));
+    if (window > 0 && !causal) panic("MultiheadAttention: a sliding window is a band of the CAUSAL triangle: set causal = true");
+    const bool banded = window > 0 && S > window;  // S <= window: the band is the whole triangle, every path as without a window
     if (rope) {
         if (rope->head_dim != dh)
             panic("MultiheadAttention: rope was built for heads of " + std::to_string(rope->head_dim) + ", the module has heads of " + std::to_string(dh));
@@ -3134,18 +3143,23 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
     // Causal, where the fused core does not apply: the composition spelled out - one Addition node (broadcast over B*H) of a
     // constant (S, S) leaf, 0 on and below the diagonal and -inf above, in front of the Softmax, whose -inf lanes come out exactly 0.
     // Uploaded once per graph build; the fused `attention_probs` node has no mask operand and is not used.
+    // With a window shorter than S the constant is banded - also -inf at k <= r - window - and the fused core, which has no window,
+    // is not taken; every row keeps its diagonal.
     auto causal_mask = [&](int n) {
         std::vector<float> m((size_t)n * n, 0.f);
-        for (int r = 0; r < n; ++r)
+        for (int r = 0; r < n; ++r) {
             for (int c = r + 1; c < n; ++c) m[(size_t)r * n + c] = -INFINITY;
+            if (banded)
+                for (int c = 0; c <= r - window; ++c) m[(size_t)r * n + c] = -INFINITY;
+        }
         return from_host(x.var.device(), Shape{n, n}, m.data());
     };
-    if (G == 1 && packed_qkv && wqkv_ && strided_heads && fused && fused_core && q.fused && k.fused && v.fused && Var::attention_core_supported(S, dh, drop.p) &&
+    if (!banded && G == 1 && packed_qkv && wqkv_ && strided_heads && fused && fused_core && q.fused && k.fused && v.fused && Var::attention_core_supported(S, dh, drop.p) &&
         still_packed())
         return o.forward(qkv_attention_node(*this, wqkv_, bqkv_, gwqkv_, gbqkv_, x, batch, S, heads, dh, scale));
     if (strided_heads && dh % 4 == 0) {  // attention GEMMs address the heads inside the projection layout: no copies
         const VarDiff Qf = rotated(q, heads), Kf = keys(), Vf = values();
-        if (fused && fused_core && Var::attention_core_supported(S, dh, drop.p))
+        if (!banded && fused && fused_core && Var::attention_core_supported(S, dh, drop.p))
             return o.forward(Qf.heads_attention(Kf, Vf, batch, S, heads, dh, scale, drop.p, drop.status, causal));
         const VarDiff scores = Qf.heads_scores(Kf, batch, S, heads, dh);
         const VarDiff P = causal ? drop.forward((scores * scale + causal_mask(S)).softmax(2))
@@ -3183,8 +3197,9 @@ RotaryEmbedding::RotaryEmbedding(DevicePtr dev, int head_dim_, int max_pos_, dou
     check(nk_rope_table(dev->raw(), table->ptr(), max_pos, rot, base));
 }
 
-KvCache::KvCache(DevicePtr dev, int batch_, int heads_, int head_dim_, int capacity_)
-    : batch(batch_), heads(heads_), head_dim(head_dim_), capacity(capacity_) {
+KvCache::KvCache(DevicePtr dev, int batch_, int heads_, int head_dim_, int capacity_) : KvCache(std::move(dev), batch_, heads_, head_dim_, capacity_, false) {}
+KvCache::KvCache(DevicePtr dev, int batch_, int heads_, int head_dim_, int capacity_, bool rolling_)
+    : batch(batch_), heads(heads_), head_dim(head_dim_), capacity(capacity_), rolling(rolling_) {
     if (batch <= 0 || heads <= 0 || head_dim <= 0 || capacity <= 0) panic("KvCache: batch, heads, head_dim and capacity must be positive");
     if ((unsigned long long)batch * heads * capacity * head_dim > (unsigned long long)INT_MAX)
         panic("KvCache: batch * heads * capacity * head_dim must fit 31 bits");
@@ -3192,29 +3207,48 @@ KvCache::KvCache(DevicePtr dev, int batch_, int heads_, int head_dim_, int capac
     k = std::make_shared<HipArray>(dev, s, HipArray::Uninit{});
     v = std::make_shared<HipArray>(dev, s, HipArray::Uninit{});
     lens_.assign((size_t)batch, 0);
+    high_.assign((size_t)batch, 0);
     (void)workspace(1, heads);
 }
-Shared<HipArray> KvCache::workspace(int T, int query_heads) {
-    if (T > ws_T_ || query_heads > ws_H_) {
+void KvCache::remember_window(int window) { window_ = window; }
+Shared<HipArray> KvCache::workspace(int T, int query_heads, int window) {
+    window = std::min(window, capacity);  // the kernel's own clamp on a linear cache; a ring has window <= capacity
+    if (T > ws_T_ || query_heads > ws_H_ || window > ws_W_) {
         T = std::max(T, ws_T_);
         query_heads = std::max(query_heads, ws_H_);
-        const size_t n = nk_attention_decode_workspace(batch, T, query_heads, head_dim, capacity);
+        window = std::max(window, ws_W_);
+        size_t n = nk_attention_decode_workspace(batch, T, query_heads, head_dim, capacity);
+        if (window > 0) n = std::max(n, nk_attention_decode_window_workspace(batch, T, query_heads, head_dim, window));
         if (n == 0 || n > (size_t)INT_MAX) panic("KvCache: the decode workspace for " + std::to_string(T) + " rows per sample does not fit 31 bits");
         ws_ = std::make_shared<HipArray>(k->device(), Shape{(int)n}, HipArray::Uninit{});
-        ws_T_ = T; ws_H_ = query_heads;
+        ws_T_ = T; ws_H_ = query_heads; ws_W_ = window;
     }
     return ws_;
 }
 void KvCache::advance(int T) {
-    for (int& l : lens_) l += T;
+    for (size_t b = 0; b < lens_.size(); ++b) {
+        lens_[b] += T;
+        high_[b] = std::max(high_[b], lens_[b]);
+    }
 }
-void KvCache::reset() { lens_.assign((size_t)batch, 0); }
+void KvCache::reset() {
+    lens_.assign((size_t)batch, 0);
+    high_.assign((size_t)batch, 0);
+}
 void KvCache::truncate(const std::vector<int>& lens) {
     if ((int)lens.size() != batch) panic("KvCache::truncate: " + std::to_string(lens.size()) + " lengths for a batch of " + std::to_string(batch));
     for (int b = 0; b < batch; ++b)
         if (lens[b] < 0 || lens[b] > lens_[b])
             panic("KvCache::truncate: sample " + std::to_string(b) + " holds " + std::to_string(lens_[b]) + " positions, asked for " +
                   std::to_string(lens[b]));
+    if (rolling) {  // the slots hold positions [high - capacity, high): the next query's window must start inside them
+        const int W = window_ > 0 ? window_ : capacity;
+        for (int b = 0; b < batch; ++b)
+            if (std::max(0, lens[b] - W) < high_[b] - capacity)
+                panic("KvCache::truncate: sample " + std::to_string(b) + " of a rolling cache of " + std::to_string(capacity) + " slots reached " +
+                      std::to_string(high_[b]) + " positions; a window of " + std::to_string(W) + " at length " + std::to_string(lens[b]) +
+                      " would read positions that were overwritten");
+    }
     lens_ = lens;
 }
 
@@ -3233,19 +3267,32 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
         if (rope->head_dim != dh)
             panic("MultiheadAttention::forward_step: rope was built for heads of " + std::to_string(rope->head_dim) + ", the module has heads of " +
                   std::to_string(dh));
-        if (cache.capacity > rope->max_pos)
+        if (!cache.rolling && cache.capacity > rope->max_pos)
             panic("MultiheadAttention::forward_step: the cache's capacity of " + std::to_string(cache.capacity) + " exceeds rope's table of " +
                   std::to_string(rope->max_pos));
     }
+    if (window < 0) panic("MultiheadAttention::forward_step: window must not be negative, got " + std::to_string(window));
+    if (cache.rolling && window == 0)
+        panic("MultiheadAttention::forward_step: a rolling cache keeps the last positions only: it needs a layer with window > 0");
+    if (cache.rolling && T > cache.capacity)
+        panic("MultiheadAttention::forward_step: " + std::to_string(T) + " rows per sample exceed the rolling cache's " +
+              std::to_string(cache.capacity) + " slots: chunk the prompt");
     bool fresh = true;
     for (int b = 0; b < batch; ++b) {
-        if (cache.lens()[b] + T > cache.capacity)
+        if (cache.rolling) {  // the positions keep growing: they must stay inside rope's table (and 31 bits)
+            if (rope && (long long)cache.lens()[b] + T > rope->max_pos)
+                panic("MultiheadAttention::forward_step: sample " + std::to_string(b) + " holds " + std::to_string(cache.lens()[b]) + " positions, " +
+                      std::to_string(T) + " more exceed rope's table of " + std::to_string(rope->max_pos));
+            if ((long long)cache.lens()[b] + T > (long long)INT_MAX - 1024)
+                panic("MultiheadAttention::forward_step: sample " + std::to_string(b) + ": positions must stay below 2^31 - 1024");
+        } else if (cache.lens()[b] + T > cache.capacity)
             panic("MultiheadAttention::forward_step: sample " + std::to_string(b) + " holds " + std::to_string(cache.lens()[b]) + " positions, " +
                   std::to_string(T) + " more exceed the cache's capacity of " + std::to_string(cache.capacity));
         fresh = fresh && cache.lens()[b] == 0;
     }
     auto fw = std::make_shared<DecodeStepFwd>();
     fw->B = batch; fw->T = T; fw->H = heads; fw->Hkv = kv_heads; fw->dh = dh; fw->cap = cache.capacity;
+    fw->window = window; fw->ring = cache.rolling;
     fw->x = x.data;
     History<ForwardEntry> hf = x.history;
     for (const Linear* l : {&q, &k, &v, &o}) { hf.merge(l->weight.var.history); hf.merge(l->bias.var.history); }
@@ -3279,9 +3326,15 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
     // take the prefill instead of a refused call
     const long long tiles = (T + 31) / 32;
     const bool core_fits = (long long)batch * heads * tiles * tiles < (1ll << 31) / 32 && (long long)n * 3 * d_model < (1ll << 31);
-    fw->core = fresh && T >= 2 && core_fits && nk_attention_supported(T, dh, 0.0, 0) != 0;
-    if (!fw->core) fw->ws = cache.workspace(T, heads);  // one partial per QUERY head
-    else if (kv_heads != heads) {  // nothing is allocated inside forward()
+    // with a window the core, which has none, takes the prefill only while the band is the whole triangle
+    fw->core = fresh && T >= 2 && core_fits && nk_attention_supported(T, dh, 0.0, 0) != 0 && (window == 0 || T <= window);
+    if (!fw->core && cache.rolling && (long long)window + T - 1 > cache.capacity)
+        panic("MultiheadAttention::forward_step: a rolling cache of " + std::to_string(cache.capacity) + " slots cannot hold a window of " +
+              std::to_string(window) + " keys and " + std::to_string(T) + " new rows (window + T - 1 <= capacity): chunk the prompt into slices of at most " +
+              std::to_string(std::max(0, cache.capacity - window + 1)) + " rows");
+    if (!fw->core) fw->ws = cache.workspace(T, heads, window);  // one partial per QUERY head
+    if (window > 0) cache.remember_window(window);              // for truncate(): the core path asks for no scratch
+    if (fw->core && kv_heads != heads) {  // nothing is allocated inside forward()
         fw->kf = zeros_like(x.data, Shape{n, d_model}); fw->vf = zeros_like(x.data, Shape{n, d_model});
         if (fw->qkv) fw->qf = zeros_like(x.data, Shape{n, d_model});
     }

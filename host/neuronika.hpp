@@ -895,22 +895,39 @@ struct RotaryEmbedding {
 //   truncate(l)  every sample to a length no longer than its current one.  This is what makes ragged prompts work - prefill a
 //                right-padded batch, then truncate each sample to its true prompt length: under the causal rule the padding never
 //                influenced the real positions - and it gives roll-back.
+//   rolling      (the second constructor's argument; false, and the first constructor: the object above, field for field) a ring for a sliding-window layer
+//                (`MultiheadAttention::window`): position p lives at slot p % capacity, lens[b] grows past `capacity`, and
+//                `high_water()[b]` is the largest length sample b has reached since the last reset() - the slots hold the positions
+//                [high_water - capacity, high_water).  truncate(l) must leave the next window intact: it panics unless
+//                max(0, l[b] - W) >= high_water[b] - capacity, with W the window of the layer that last stepped the cache (the cache
+//                REMEMBERS it: forward_step records it (`remember_window`) when it builds its node; before any step W = capacity).  The ragged-prompt
+//                recipe works whenever the prefill's T <= capacity: high_water = T then, and the right side is <= 0.
 struct KvCache {
     KvCache(DevicePtr dev, int batch, int heads, int head_dim, int capacity);
+    KvCache(DevicePtr dev, int batch, int heads, int head_dim, int capacity, bool rolling);
     int batch, heads, head_dim, capacity;
+    bool rolling;
     const std::vector<int>& lens() const { return lens_; }
-    void reset();
+    const std::vector<int>& high_water() const { return high_; }
+    void reset();  // rolling: clears the high-water marks too
     void truncate(const std::vector<int>& lens);
     // used by forward_step: the buffers, the scratch of nk_attention_decode_fwd (sized for T = 1 and `heads` query heads at
     // construction, regrown when a larger T or a grouped layer's larger query head count first arrives; a node keeps the one it was built with alive), and the lengths after a step of T rows
     Shared<HipArray> k, v;
-    Shared<HipArray> workspace(int T, int query_heads);
+    // window > 0: also at least nk_attention_decode_window_workspace(batch, T, query_heads, head_dim, window) floats - a window
+    // that straddles one more chunk seam than the capacity has chunks needs a chunk more than the capacity-sized scratch.
+    // workspace_floats(): the size of the scratch held now (a prefill the causal core takes asks for none and must not grow it).
+    // remember_window(): forward_step records the layer's window with every step, for truncate()
+    Shared<HipArray> workspace(int T, int query_heads, int window = 0);
+    size_t workspace_floats() const { return ws_ ? ws_->len() : 0; }
+    void remember_window(int window);
     void advance(int T);
 
    private:
-    std::vector<int> lens_;
+    std::vector<int> lens_, high_;
     Shared<HipArray> ws_;
-    int ws_T_ = 0, ws_H_ = 0;
+    int ws_T_ = 0, ws_H_ = 0, ws_W_ = 0;
+    int window_ = 0;  // of the layer that last stepped the cache (0: none yet)
 };
 
 // Multi-head attention composed from reference ops (the module does not exist in the reference;
@@ -947,6 +964,22 @@ struct MultiheadAttention {
     // through `VarDiff::rope`.  forward_step rotates the new Q and K rows at lens[b] + t before the append: the cache holds ROTATED
     // keys.  Panics: rope->head_dim != d_model / heads, S > max_pos (forward), cache.capacity > max_pos (forward_step).
     Shared<RotaryEmbedding> rope;
+    // Sliding-window attention (semantics at nk_attention_decode_window_fwd in neuronika_hip.h): query position i attends to the keys
+    // max(0, i - window + 1) .. i.  0 (the default) = off: every path as without it, bit for bit, same launches.  Read when
+    // forward() / forward_step() build their nodes, like `causal`; window > 0 with causal == false panics.
+    //   forward()       S <= window: the band is the causal triangle - the paths above untouched, fused core included.  S > window:
+    //                   the node-by-node paths (`heads_scores` / `bmm_t`) with the banded constant M[r][k] = 0 for r - window < k <= r,
+    //                   -inf elsewhere, on the Addition node in place of the causal one: differentiable through the existing
+    //                   Addition / Softmax / Dropout nodes, not fast (the fused core takes no window).
+    //   forward_step()  a fresh prefill with 2 <= T <= window keeps the causal core; every other step runs
+    //                   nk_attention_decode_window_fwd over its T rows, on a linear cache or a rolling one (`KvCache::rolling`,
+    //                   appended through nk_kv_cache_append_ring).  A step reads at most `window` keys per kv head whatever the length.
+    //                   Panics: a rolling cache with window == 0; on a rolling cache T > capacity, or window + T - 1 > capacity for a
+    //                   step the window kernel takes (the step's rows are appended before they are attended to and must not land on
+    //                   a slot row 0 still reads: chunk the prompt into slices of at most capacity - window + 1 rows); a linear cache
+    //                   overflowing, as without a window.  With rope on a rolling cache the positions keep growing: the guard is
+    //                   lens[b] + T <= rope->max_pos instead of capacity <= max_pos.
+    int window = 0;
     MultiheadAttention(DevicePtr dev, int d_model, int heads, double p, uint64_t seed);
     MultiheadAttention(DevicePtr dev, int d_model, int heads, int kv_heads, double p, uint64_t seed);
     // four Linear layers built elsewhere (e.g. deserialised): their weights are NOT packed, `packed_qkv` is off.  kv_heads 0 = heads;

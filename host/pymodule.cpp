@@ -483,10 +483,13 @@ PYBIND11_MODULE(_tape, m) {
         .def("eval", &nn::Dropout::eval)
         .def("forward", &nn::Dropout::forward);
     py::class_<nn::KvCache>(nn, "KvCache")
-        .def(py::init<DevicePtr, int, int, int, int>(), py::arg("dev"), py::arg("batch"), py::arg("heads"), py::arg("head_dim"),
-             py::arg("capacity"),
+        .def(py::init<DevicePtr, int, int, int, int, bool>(), py::arg("dev"), py::arg("batch"), py::arg("heads"), py::arg("head_dim"),
+             py::arg("capacity"), py::arg("rolling") = false,
              "Keys and values of one causal attention layer on the device, (batch, heads, capacity, head_dim) each, for "
-             "MultiheadAttention.forward_step.")
+             "MultiheadAttention.forward_step. rolling: a ring for a sliding-window layer, position p at slot p % capacity.")
+        .def_readonly("rolling", &nn::KvCache::rolling)
+        .def("workspace_floats", &nn::KvCache::workspace_floats, "floats of decode scratch the cache holds now")
+        .def("high_water", [](const nn::KvCache& c) { return c.high_water(); }, "the largest length every sample reached since the last reset")
         .def_readonly("batch", &nn::KvCache::batch)
         .def_readonly("heads", &nn::KvCache::heads)
         .def_readonly("head_dim", &nn::KvCache::head_dim)
@@ -552,6 +555,7 @@ PYBIND11_MODULE(_tape, m) {
         .def_readwrite("fused_core", &nn::MultiheadAttention::fused_core)
         .def_readwrite("packed_qkv", &nn::MultiheadAttention::packed_qkv)
         .def_readwrite("causal", &nn::MultiheadAttention::causal)
+        .def_readwrite("window", &nn::MultiheadAttention::window)  // sliding window: 0 = off; needs causal
         .def_readwrite("rope", &nn::MultiheadAttention::rope)  // a shared RotaryEmbedding; None clears it
         .def_readonly("d_model", &nn::MultiheadAttention::d_model)
         .def_readonly("heads", &nn::MultiheadAttention::heads)

@@ -919,6 +919,49 @@ int nk_attention_decode_gqa_fwd(nk_device* dev, const float* Q, int ldq, const f
 int nk_repeat_kv_fwd(nk_device* dev, const float* x, int ldx, float* y, int ldy, int rows, int Hkv, int G, int dh);
 int nk_repeat_kv_bwd(nk_device* dev, float* dx, int lddx, const float* g, int ldg, int rows, int Hkv, int G, int dh);
 int nk_repeat_kv_bwd_assign(nk_device* dev, float* dx, int lddx, const float* g, int ldg, int rows, int Hkv, int G, int dh);
+/* ------------------------------------------------------------------ sliding-window decoding --
+ * Ours (the reference has no attention layer): the sliding window of Longformer (Beltagy et al. 2020) as Mistral 7B uses it.  Query
+ * position i attends to the keys max(0, i - W + 1) .. i, so a decoding step reads at most W keys per kv head whatever the length of
+ * the generation, and a cache of W + T - 1 slots serves any length.  For sample b, query head h and the t-th new row (0 <= t < T),
+ * with n = start[b] + t + 1 and lo = max(0, n - W):
+ *   o = softmax(q . K[lo:n]^T * scale) . V[lo:n]
+ * over the rows of kv head h / (H / Hkv).  As a composition this is row n - 1 of the causal chain documented at
+ * nk_attention_causal_fwd with the BANDED constant M[r][k] = 0 for r - W < k <= r and -inf elsewhere; every row keeps its diagonal,
+ * so no row is empty for any W >= 1.
+ * nk_attention_decode_window_fwd: Kc, Vc are (B, Hkv, cap, dh); Hkv == H is the ungrouped layer, otherwise query head h reads kv
+ *   head h / (H / Hkv) exactly as nk_attention_decode_gqa_fwd does.  Q, ldq, O, start and scale are nk_attention_decode_fwd's.
+ *   ring == 0: a linear cache, position p at slot p, n clipped to cap as in nk_attention_decode_fwd.
+ *   ring != 0: a rolling cache, position p at slot p % cap, n NOT clipped; requires window + T - 1 <= cap.  Why: the T rows of a
+ *   step are appended before they are attended to, so positions start .. start + T - 1 are written while row 0 (n = start + 1)
+ *   still reads position start + 1 - W.  The write of position start + T - 1 lands on that slot iff
+ *   (start + T - 1) - (start + 1 - W) = W + T - 2 is a multiple of cap; all T writes and the W - 1 older keys row 0 reads are
+ *   W + T - 1 consecutive positions, distinct slots iff W + T - 1 <= cap.  Positions must stay below 2^31 - 1024.
+ *   A negative start[b] gives a zero output row.
+ *   Chunking: chunks stay aligned to ABSOLUTE positions - chunk c covers positions [cC, cC + C), C = nk_attention_decode_chunk(dh) -
+ *   and a problem visits chunks lo / C .. (n - 1) / C only: at most (W + C - 2) / C + 1 of them (integer division), which is the
+ *   grid's second extent and the workspace's per-problem stride, never a function of cap.  Positions of a visited chunk outside
+ *   [lo, n): the load is redirected to position n - 1 (always inside the window), the probability is SELECTED to 0, and the chunk's
+ *   shift is the exact maximum over its in-window keys; a slot outside the window is never read into a result.  Partials are merged
+ *   in ascending chunk order in nk_attention_decode_fwd's exp2 form; a window inside one chunk writes O directly.  No atomics.  The
+ *   slot of a position is the slot of lo (one remainder per block) plus an offset with one conditional subtract: no table and
+ *   no dependent load.  The per-head arithmetic is nk_attention_decode_fwd's; a grouped layer loads a chunk once for up to 8 query heads.
+ *   Bit contract:
+ *   (1) n <= window: the bits are those of nk_attention_decode_gqa_fwd on the same inputs (nk_attention_decode_fwd when Hkv == H).
+ *   (2) for the same positions' contents, the bits of a ring cache equal the bits of a linear cache.
+ *   (3) the bits of o for (b, h, t) depend on that problem's q, its keys / values at positions [lo, n), n, W and scale ONLY: not on
+ *       B, T, cap, ring, the group size, the other samples, or anything a slot outside the window holds (NaN or 1e30 is harmless).
+ *   (4) grouped bits equal ungrouped bits on the cache with every kv head repeated.
+ *   `workspace`: nk_attention_decode_window_workspace(B, T, H, dh, window) floats (needs no device; a function of the window,
+ *   never of cap; on a linear cache a window above cap acts as the window cap - the same keys - and uses less of it).
+ *   NK_ERR_INVALID, nothing written: window <= 0, ring with window + T - 1 > cap, and everything nk_attention_decode_gqa_fwd refuses.
+ * nk_kv_cache_append_ring: nk_kv_cache_append with row b*T + t going to slot (start[b] + t) % cap.  Every row with a non-negative
+ *   position is written; T > cap (two rows of a sample on one slot) is NK_ERR_INVALID.  A bit-exact copy; nothing else of the cache
+ *   is touched. */
+int nk_attention_decode_window_fwd(nk_device* dev, const float* Q, int ldq, const float* Kc, const float* Vc, const int* start, float* O,
+                                   float* workspace, int B, int T, int H, int Hkv, int dh, int cap, int window, int ring, float scale);
+size_t nk_attention_decode_window_workspace(int B, int T, int H, int dh, int window);
+int nk_kv_cache_append_ring(nk_device* dev, float* Kc, float* Vc, const float* K, const float* V, int ld, const int* start, int B, int T,
+                            int H, int dh, int cap);
 /* ------------------------------------------------------------------ rotary position embedding --
  * Ours (the reference has no position encoding of any kind): RoPE, Su et al. 2021 (RoFormer), as LLaMA / Mistral / Qwen / GPT-NeoX /
  * Phi apply it to the query and key rows in front of the attention scores.

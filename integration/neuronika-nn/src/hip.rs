@@ -437,14 +437,34 @@ conv_layer!(Conv3d, GroupedConv3d, Ix5, Ix4, (usize, usize, usize),
 /// The keys and values of one causal attention layer between the steps of incremental decoding (ours; the tested mirror is
 /// `nn::KvCache` in `host/neuronika.hpp`): device buffers `(batch, heads, capacity, head_dim)` and the per-sample lengths on the
 /// host.  `MultiheadAttention::forward_step` advances the lengths when it builds its node.
+/// `new_rolling`: a ring for a sliding-window layer (`MultiheadAttention::window`) - position `p` lives at slot `p % capacity`, the
+/// lengths grow past the capacity, and `high_water` keeps the largest length every sample has reached since the last `reset`: the
+/// slots hold the positions `[high_water - capacity, high_water)`.
 pub struct KvCache {
     pub buffers: KvBuffers,
     lens: RefCell<Vec<usize>>,
+    high: RefCell<Vec<usize>>,
+    window: Cell<usize>, // of the layer that last stepped the cache (0: none yet)
 }
 
 impl KvCache {
     pub fn new(batch: usize, heads: usize, head_dim: usize, capacity: usize, device: &Device) -> Self {
-        Self { buffers: KvBuffers::new(batch, heads, head_dim, capacity, device), lens: RefCell::new(vec![0; batch]) }
+        Self { buffers: KvBuffers::new(batch, heads, head_dim, capacity, device), lens: RefCell::new(vec![0; batch]),
+               high: RefCell::new(vec![0; batch]), window: Cell::new(0) }
+    }
+
+    pub fn new_rolling(batch: usize, heads: usize, head_dim: usize, capacity: usize, device: &Device) -> Self {
+        Self { buffers: KvBuffers::new_rolling(batch, heads, head_dim, capacity, device), lens: RefCell::new(vec![0; batch]),
+               high: RefCell::new(vec![0; batch]), window: Cell::new(0) }
+    }
+
+    pub fn rolling(&self) -> bool {
+        self.buffers.rolling()
+    }
+
+    /// The largest length every sample has reached since the last `reset`.
+    pub fn high_water(&self) -> Vec<usize> {
+        self.high.borrow().clone()
     }
 
     pub fn capacity(&self) -> usize {
@@ -459,19 +479,29 @@ impl KvCache {
     /// Every length back to 0; the buffers are kept.
     pub fn reset(&self) {
         self.lens.borrow_mut().iter_mut().for_each(|l| *l = 0);
+        self.high.borrow_mut().iter_mut().for_each(|l| *l = 0);
     }
 
     /// Every sample to a length no longer than its current one: ragged prompts after a right-padded prefill (under the causal
-    /// rule the padding never influenced the real positions), and roll-back.
+    /// rule the padding never influenced the real positions), and roll-back.  On a rolling cache the next query's window must
+    /// still lie in the ring: `max(0, l - W) >= high_water - capacity`, `W` the window of the layer that last stepped the cache
+    /// (remembered by `forward_step`; the capacity before any step).
     pub fn truncate(&self, lens: &[usize]) {
         let mut mine = self.lens.borrow_mut();
         assert!(lens.len() == mine.len(), "KvCache::truncate: one length per sample");
         assert!(lens.iter().zip(mine.iter()).all(|(new, old)| new <= old), "KvCache::truncate: a sample cannot grow");
+        if self.rolling() {
+            let capacity = self.capacity();
+            let w = if self.window.get() > 0 { self.window.get() } else { capacity };
+            assert!(lens.iter().zip(self.high.borrow().iter()).all(|(&l, &h)| l.saturating_sub(w) + capacity >= h),
+                    "KvCache::truncate: the window of the next query would read positions that were overwritten");
+        }
         mine.copy_from_slice(lens);
     }
 
     fn advance(&self, rows: usize) {
         self.lens.borrow_mut().iter_mut().for_each(|l| *l += rows);
+        self.high.borrow_mut().iter_mut().zip(self.lens.borrow().iter()).for_each(|(h, &l)| *h = (*h).max(l));
     }
 }
 
@@ -544,6 +574,12 @@ pub struct MultiheadAttention {
     /// right behind the projection (one launch, `2 * heads` heads, stride `3 * d_model`), at `lens[b] + t` in `forward_step`, so the
     /// cache holds rotated keys; the backward applies the inverse in place to `[dQ | dK]` in front of the projection's products.
     pub rope: Option<Rc<RotaryEmbedding>>,
+    /// Sliding-window attention (the tested mirror is `nn::MultiheadAttention::window` in `host/neuronika.hpp`): query position `i`
+    /// attends to the keys `max(0, i - window + 1) ..= i`.  `0` after `new`: off.  Read by `forward_step`, which then runs
+    /// `nk_attention_decode_window_fwd` over a linear `KvCache` or a rolling one (`KvCache::new_rolling`).  The TRAINING forward with
+    /// a window shorter than the sequence is not mirrored here (the packed node runs the fused core, which has no window): `forward`
+    /// panics for it.
+    pub window: usize,
 }
 
 impl MultiheadAttention {
@@ -553,7 +589,7 @@ impl MultiheadAttention {
         // each of the three row blocks is initialised as its own Linear(d_model, d_model): U(-k, k), k = 1 / sqrt(d_model) -
         // the fan-in of the packed layer is d_model too, so one draw over (3 d, d) follows the same law
         Self { qkv: Linear::new(d_model, 3 * d_model, device), o: Linear::new(d_model, d_model, device), d_model, heads, dropout: Dropout::new(p),
-               kv_heads: heads, causal: false, rope: None }
+               kv_heads: heads, causal: false, rope: None, window: 0 }
     }
 
     /// `new` with `kv_heads < heads` key / value heads shared by `heads / kv_heads` query heads each.
@@ -588,6 +624,8 @@ impl MultiheadAttention {
         assert!(batch > 0 && rows % batch == 0, "MultiheadAttention: rows must be a multiple of batch");
         assert!(self.kv_heads == self.heads, "MultiheadAttention::forward: the packed node takes kv_heads == heads (see `kv_heads`)");
         let (seq, dh) = (rows / batch, self.d_model / self.heads);
+        assert!(self.window == 0 || self.causal, "MultiheadAttention: a sliding window is a band of the causal triangle: set causal");
+        assert!(self.window == 0 || seq <= self.window, "MultiheadAttention::forward: the packed node has no window shorter than the sequence (see `window`)");
         let scale = 1. / (dh as f32).sqrt();
         let packed = self.qkv.forward(input);
         let packed = match &self.rope {
@@ -622,17 +660,28 @@ impl MultiheadAttention {
         assert!((cb, ch, cd) == (batch, self.kv_heads, dh),
                 "MultiheadAttention::forward_step: the cache holds {} heads, the layer has {} kv heads (of {} query heads)", ch, self.kv_heads, self.heads);
         let start = cache.lens();
-        assert!(start.iter().all(|&l| l + rows / batch <= capacity), "MultiheadAttention::forward_step: the step exceeds the capacity");
+        if cache.rolling() {
+            assert!(self.window > 0, "MultiheadAttention::forward_step: a rolling cache keeps the last positions only: it needs a layer with window > 0");
+            assert!(self.window + rows / batch - 1 <= capacity,
+                    "MultiheadAttention::forward_step: window + T - 1 <= capacity on a rolling cache: chunk the prompt");
+        } else {
+            assert!(start.iter().all(|&l| l + rows / batch <= capacity), "MultiheadAttention::forward_step: the step exceeds the capacity");
+        }
         let scale = 1. / (dh as f32).sqrt();
         let packed = input.linear(self.qkv.weight.detached(), self.qkv.bias.detached(), false);
         let packed = match &self.rope {
             Some(r) => {
-                assert!(r.table.head_dim() == dh && capacity <= r.table.max_pos(), "MultiheadAttention::forward_step: rope does not fit the head size or the capacity");
+                // a rolling cache's positions keep growing: they, not the capacity, must stay inside the table
+                let fits = if cache.rolling() { start.iter().all(|&l| l + rows / batch <= r.table.max_pos()) } else { capacity <= r.table.max_pos() };
+                assert!(r.table.head_dim() == dh && fits, "MultiheadAttention::forward_step: rope does not fit the head size or the capacity");
                 packed.rope_in_place(&r.table, batch, self.heads + self.kv_heads, Some(&start))
             }
             None => packed,
         };
-        let context = packed.packed_decode_attention(&cache.buffers, self.heads, &start, scale);
+        let context = packed.packed_decode_attention(&cache.buffers, self.heads, &start, scale, self.window);
+        if self.window > 0 {
+            cache.window.set(self.window);
+        }
         cache.advance(rows / batch);
         context.linear(self.o.weight.detached(), self.o.bias.detached(), false)
     }

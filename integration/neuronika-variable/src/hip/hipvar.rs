@@ -23,7 +23,7 @@ use super::{
         AvgPool, AvgPoolBackward, MaxPool, MaxPoolBackward,
         DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, RmsNorm, RmsNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
-        decode_chunk, decode_workspace, PackedDecodeAttention,
+        decode_chunk, decode_window_workspace, decode_workspace, PackedDecodeAttention,
         RepeatKv, RepeatKvBackward, RepeatKvGeometry, rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
         sample_stage_limit, Sample, SampleParams,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
@@ -549,23 +549,40 @@ impl HipVar<Ix2> {
 /// Device storage of one causal attention layer's keys and values for incremental decoding (ours; layout in
 /// `include/neuronika_hip.h`): `(batch, heads, capacity, dh)` each, head-major, plus the scratch of the split-KV kernels, sized
 /// for one new row per sample and regrown when a longer slice first arrives.  The lengths are the caller's
-/// (`neuronika_nn::hip::KvCache`).
+/// (`neuronika_nn::hip::KvCache`).  `rolling` (`new_rolling`): a ring for a sliding-window layer - position `p` lives at slot
+/// `p % capacity` and the lengths may pass the capacity.
 pub struct KvBuffers {
     pub(crate) keys: Shared<HipArray<Ix4>>,
     pub(crate) values: Shared<HipArray<Ix4>>,
     workspace: RefCell<Shared<HipArray<Ix1>>>,
     workspace_rows: Cell<usize>,
     workspace_heads: Cell<usize>, // query heads the scratch is sized for: more than `heads` once a grouped-query layer has used it
+    workspace_window: Cell<usize>, // the widest window the scratch is sized for (0: none yet)
     geometry: (usize, usize, usize, usize), // batch, heads (kv heads of a grouped-query layer), capacity, dh
+    rolling: bool,
 }
 
 impl KvBuffers {
     pub fn new(batch: usize, heads: usize, dh: usize, capacity: usize, device: &Device) -> Self {
+        Self::build(batch, heads, dh, capacity, false, device)
+    }
+
+    /// `new` as a ring: position `p` at slot `p % capacity`.
+    pub fn new_rolling(batch: usize, heads: usize, dh: usize, capacity: usize, device: &Device) -> Self {
+        Self::build(batch, heads, dh, capacity, true, device)
+    }
+
+    fn build(batch: usize, heads: usize, dh: usize, capacity: usize, rolling: bool, device: &Device) -> Self {
         assert!(batch > 0 && heads > 0 && dh > 0 && capacity > 0, "KvBuffers: batch, heads, dh and capacity must be positive");
         let dim = ndarray::Dim([batch, heads, capacity, dh]);
         Self { keys: shared(dim, device), values: shared(dim, device),
                workspace: RefCell::new(shared(ndarray::Dim([decode_workspace(batch, 1, heads, dh, capacity)]), device)),
-               workspace_rows: Cell::new(1), workspace_heads: Cell::new(heads), geometry: (batch, heads, capacity, dh) }
+               workspace_rows: Cell::new(1), workspace_heads: Cell::new(heads), workspace_window: Cell::new(0),
+               geometry: (batch, heads, capacity, dh), rolling }
+    }
+
+    pub fn rolling(&self) -> bool {
+        self.rolling
     }
 
     /// `(batch, heads, capacity, dh)`
@@ -578,13 +595,22 @@ impl KvBuffers {
         decode_chunk(self.geometry.3)
     }
 
-    fn workspace_for(&self, rows: usize, query_heads: usize, device: &Device) -> Shared<HipArray<Ix1>> {
-        if rows > self.workspace_rows.get() || query_heads > self.workspace_heads.get() {
+    /// `window > 0`: also at least `nk_attention_decode_window_workspace` floats - a window that straddles one more chunk seam
+    /// than the capacity has chunks needs a chunk more than the capacity-sized scratch.
+    fn workspace_for(&self, rows: usize, query_heads: usize, window: usize, device: &Device) -> Shared<HipArray<Ix1>> {
+        let window = window.min(self.geometry.2);
+        if rows > self.workspace_rows.get() || query_heads > self.workspace_heads.get() || window > self.workspace_window.get() {
             let (batch, _, capacity, dh) = self.geometry;
             let (rows, heads) = (rows.max(self.workspace_rows.get()), query_heads.max(self.workspace_heads.get()));
-            *self.workspace.borrow_mut() = shared(ndarray::Dim([decode_workspace(batch, rows, heads, dh, capacity)]), device);
+            let window = window.max(self.workspace_window.get());
+            let mut floats = decode_workspace(batch, rows, heads, dh, capacity);
+            if window > 0 {
+                floats = floats.max(decode_window_workspace(batch, rows, heads, dh, window));
+            }
+            *self.workspace.borrow_mut() = shared(ndarray::Dim([floats]), device);
             self.workspace_rows.set(rows);
             self.workspace_heads.set(heads);
+            self.workspace_window.set(window);
         }
         self.workspace.borrow().clone()
     }
@@ -596,8 +622,10 @@ impl HipVar<Ix2> {
     /// its sample (`nk_kv_cache_append`, `nk_attention_decode_fwd`).  `start`: each sample's length before the step, captured
     /// here.  Output `(batch*rows, query_heads*dh)`, no gradient.  `query_heads`: the heads of Q - the buffers' head count for plain
     /// multi-head attention, a multiple of it for a grouped-query layer, whose packed projection is `(rows, (query_heads +
-    /// 2*heads)*dh)` and whose step runs `nk_attention_decode_gqa_fwd`.
-    pub fn packed_decode_attention(self, buffers: &KvBuffers, query_heads: usize, start: &[usize], scale: f32) -> HipVar<Ix2> {
+    /// 2*heads)*dh)` and whose step runs `nk_attention_decode_gqa_fwd`.  `window`: 0 = every key below the row's position; `W > 0` =
+    /// the keys `max(0, n - W) .. n - 1` through `nk_attention_decode_window_fwd`, on linear buffers or rolling ones
+    /// (`KvBuffers::new_rolling`: `nk_kv_cache_append_ring`, `start` may pass the capacity, `W + rows - 1 <= capacity`).
+    pub fn packed_decode_attention(self, buffers: &KvBuffers, query_heads: usize, start: &[usize], scale: f32, window: usize) -> HipVar<Ix2> {
         let device = self.device();
         let (batch, heads, capacity, dh) = buffers.geometry();
         let total = self.data.borrow().dimension()[0];
@@ -606,13 +634,22 @@ impl HipVar<Ix2> {
         assert!(self.data.borrow().dimension()[1] == (query_heads + 2 * heads) * dh,
                 "packed_decode_attention: the input must be (rows, (query_heads + 2 * heads) * dh)");
         let rows = total / batch;
-        assert!(start.iter().all(|&s| s + rows <= capacity), "packed_decode_attention: the step exceeds the capacity of the cache");
+        if buffers.rolling() {
+            assert!(window > 0, "packed_decode_attention: rolling buffers keep the last positions only: they need a window");
+            assert!(window + rows - 1 <= capacity,
+                    "packed_decode_attention: rolling buffers of {} slots cannot hold a window of {} keys and {} new rows (window + rows - 1 <= capacity): chunk the prompt",
+                    capacity, window, rows);
+            assert!(start.iter().all(|&s| s + rows < (1usize << 31) - 1024), "packed_decode_attention: positions must stay below 2^31 - 1024");
+        } else {
+            assert!(start.iter().all(|&s| s + rows <= capacity), "packed_decode_attention: the step exceeds the capacity of the cache");
+        }
         let cells: Vec<f32> = start.iter().map(|&s| f32::from_bits(s as u32)).collect();
         let start = HipArray::from_slice(&cells, ndarray::Dim([batch]), device.clone());
         let geometry = Heads { batch: batch as i32, seq: rows as i32, heads: heads as i32, dh: dh as i32 };
         let data = shared(ndarray::Dim([total, query_heads * dh]), &device);
-        let op = PackedDecodeAttention::new(geometry, query_heads as i32, capacity as i32, self.data, buffers.keys.clone(), buffers.values.clone(), start,
-                                            buffers.workspace_for(rows, query_heads, &device), data.clone(), scale);
+        let op = PackedDecodeAttention::new(geometry, query_heads as i32, capacity as i32, window.min(i32::MAX as usize) as i32, buffers.rolling(), self.data,
+                                            buffers.keys.clone(), buffers.values.clone(), start,
+                                            buffers.workspace_for(rows, query_heads, window, &device), data.clone(), scale);
         HipVar::node(data, Rc::new(op), self.history)
     }
 }

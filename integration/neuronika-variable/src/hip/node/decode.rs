@@ -18,6 +18,12 @@ pub(crate) fn decode_workspace(batch: usize, rows: usize, heads: usize, dh: usiz
     unsafe { ffi::nk_attention_decode_workspace(batch as i32, rows as i32, heads as i32, dh as i32, capacity as i32) }
 }
 
+/// Floats of scratch `nk_attention_decode_window_fwd` needs (`nk_attention_decode_window_workspace`): a function of the window,
+/// never of the capacity.
+pub(crate) fn decode_window_workspace(batch: usize, rows: usize, heads: usize, dh: usize, window: usize) -> usize {
+    unsafe { ffi::nk_attention_decode_window_workspace(batch as i32, rows as i32, heads as i32, dh as i32, window as i32) }
+}
+
 /// One step of incremental decoding over PACKED projections (ours: the reference has no such node; semantics in
 /// `include/neuronika_hip.h`): `packed` is the `(batch*rows, 3*heads*dh)` output of one `Linear` over `[Wq; Wk; Wv]` for the NEW
 /// positions only - `(batch*rows, (query_heads + 2*heads)*dh)` for a grouped-query layer, where `geometry.heads` counts the kv heads
@@ -26,10 +32,15 @@ pub(crate) fn decode_workspace(batch: usize, rows: usize, heads: usize, dh: usiz
 /// (`nk_attention_decode_fwd`: split-KV partials merged in chunk order, no atomics; `nk_attention_decode_gqa_fwd` when
 /// `query_heads > heads`: the query heads of a group share one read of their keys and values).  `start` is fixed when the node is built,
 /// so a second `forward()` writes the same rows to the same places.  Inference only: there is no backward node.
+/// Sliding window (`window > 0`): every new row attends to the keys `max(0, n - window) .. n - 1`, `n = start[b] + t + 1`, through
+/// `nk_attention_decode_window_fwd` - at most `window` keys per kv head whatever the length.  `ring`: the caches are rolling, position
+/// `p` lives at slot `p % capacity` (`nk_kv_cache_append_ring`; `window + rows - 1 <= capacity`, checked where the node is built).
 pub(crate) struct PackedDecodeAttention {
     geometry: Heads, // `seq` = new rows per sample, `heads` = kv heads
     query_heads: i32,
     capacity: i32,
+    window: i32, // 0: off
+    ring: bool,
     packed: Shared<HipArray<Ix2>>,
     keys: Shared<HipArray<Ix4>>,
     values: Shared<HipArray<Ix4>>,
@@ -41,9 +52,10 @@ pub(crate) struct PackedDecodeAttention {
 
 impl PackedDecodeAttention {
     #[allow(clippy::too_many_arguments)]
-    pub(crate) fn new(geometry: Heads, query_heads: i32, capacity: i32, packed: Shared<HipArray<Ix2>>, keys: Shared<HipArray<Ix4>>, values: Shared<HipArray<Ix4>>,
-                      start: HipArray<Ix1>, workspace: Shared<HipArray<Ix1>>, data: Shared<HipArray<Ix2>>, scale: f32) -> Self {
-        Self { geometry, query_heads, capacity, packed, keys, values, start, workspace, data, scale }
+    pub(crate) fn new(geometry: Heads, query_heads: i32, capacity: i32, window: i32, ring: bool, packed: Shared<HipArray<Ix2>>,
+                      keys: Shared<HipArray<Ix4>>, values: Shared<HipArray<Ix4>>, start: HipArray<Ix1>, workspace: Shared<HipArray<Ix1>>,
+                      data: Shared<HipArray<Ix2>>, scale: f32) -> Self {
+        Self { geometry, query_heads, capacity, window, ring, packed, keys, values, start, workspace, data, scale }
     }
 }
 
@@ -58,11 +70,24 @@ impl Forward for PackedDecodeAttention {
         let ld = (d + 2 * dkv) as i32;
         let start = self.start.as_ptr() as *const i32;
         let dev = qkv.device().as_raw();
-        ffi::check(unsafe {
-            ffi::nk_kv_cache_append(dev, kc.as_mut_ptr(), vc.as_mut_ptr(), qkv.as_ptr().add(d), qkv.as_ptr().add(d + dkv), ld, start,
-                                    h.batch, h.seq, h.heads, h.dh, self.capacity)
-        });
-        if self.query_heads == h.heads {
+        if self.ring {
+            ffi::check(unsafe {
+                ffi::nk_kv_cache_append_ring(dev, kc.as_mut_ptr(), vc.as_mut_ptr(), qkv.as_ptr().add(d), qkv.as_ptr().add(d + dkv), ld, start,
+                                             h.batch, h.seq, h.heads, h.dh, self.capacity)
+            });
+        } else {
+            ffi::check(unsafe {
+                ffi::nk_kv_cache_append(dev, kc.as_mut_ptr(), vc.as_mut_ptr(), qkv.as_ptr().add(d), qkv.as_ptr().add(d + dkv), ld, start,
+                                        h.batch, h.seq, h.heads, h.dh, self.capacity)
+            });
+        }
+        if self.window > 0 {
+            ffi::check(unsafe {
+                ffi::nk_attention_decode_window_fwd(dev, qkv.as_ptr(), ld, kc.as_ptr(), vc.as_ptr(), start, out.as_mut_ptr(), ws.as_mut_ptr(),
+                                                    h.batch, h.seq, self.query_heads, h.heads, h.dh, self.capacity, self.window,
+                                                    self.ring as i32, self.scale)
+            });
+        } else if self.query_heads == h.heads {
             ffi::check(unsafe {
                 ffi::nk_attention_decode_fwd(dev, qkv.as_ptr(), ld, kc.as_ptr(), vc.as_ptr(), start, out.as_mut_ptr(), ws.as_mut_ptr(),
                                              h.batch, h.seq, h.heads, h.dh, self.capacity, self.scale)

@@ -216,6 +216,10 @@ _SIGS = {
     "nk_repeat_kv_fwd": [VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_repeat_kv_bwd": [VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_repeat_kv_bwd_assign": [VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_attention_decode_window_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_float],
+    "nk_attention_decode_window_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_kv_cache_append_ring": [VP, VP, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_rope_table": [VP, VP, C.c_int, C.c_int, C.c_double],
     "nk_rope_fwd": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_rope_bwd": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
@@ -261,7 +265,8 @@ _SIGS = {
     "nk_comm_size": [VP],
 }
 _RESTYPES = {"nk_last_error": C.c_char_p, "nk_version": C.c_char_p, "nk_stream_compute": VP, "nk_stream_comm": VP,
-             "nk_attention_decode_workspace": C.c_size_t, "nk_gemm_buffer_records": C.c_longlong}
+             "nk_attention_decode_workspace": C.c_size_t, "nk_attention_decode_window_workspace": C.c_size_t,
+             "nk_gemm_buffer_records": C.c_longlong}
 EXPORTED = tuple(_SIGS)
 
 for _name, _args in _SIGS.items():
@@ -1029,6 +1034,24 @@ def attention_decode_gqa_fwd(dev, Q, ldq, Kc, Vc, start, out, workspace, B, T, H
     """Grouped-query decode: the caches are (B, Hkv, cap, dh), query head h reads kv head h // (H // Hkv); everything else is
     `attention_decode_fwd`'s, its workspace included.  The heads of a group share one read of their K / V chunk."""
     check(lib.nk_attention_decode_gqa_fwd(dev.h, _p(Q), ldq, _p(Kc), _p(Vc), _p(start), _p(out), _p(workspace), B, T, H, Hkv, dh, cap, scale))
+
+
+def attention_decode_window_workspace(B, T, H, dh, window) -> int:
+    """Floats of caller-owned scratch nk_attention_decode_window_fwd needs: a function of the window, never of the capacity."""
+    return int(lib.nk_attention_decode_window_workspace(B, T, H, dh, window))
+
+
+def kv_cache_append_ring(dev, Kc, Vc, K, V, ld, start, B, T, H, dh, cap):
+    """`kv_cache_append` into a rolling cache: row b*T + t goes to slot (start[b] + t) % cap.  T <= cap."""
+    check(lib.nk_kv_cache_append_ring(dev.h, _p(Kc), _p(Vc), _p(K), _p(V), ld, _p(start), B, T, H, dh, cap))
+
+
+def attention_decode_window_fwd(dev, Q, ldq, Kc, Vc, start, out, workspace, B, T, H, Hkv, dh, cap, window, ring, scale):
+    """Sliding-window decode over (B, Hkv, cap, dh) caches: query (b, t), n = start[b] + t + 1, reads the keys at positions
+    max(0, n - window) .. n - 1; ring: position p is at slot p % cap (window + T - 1 <= cap), otherwise at slot p and n is clipped
+    to cap.  workspace: `attention_decode_window_workspace(B, T, H, dh, window)` floats."""
+    check(lib.nk_attention_decode_window_fwd(dev.h, _p(Q), ldq, _p(Kc), _p(Vc), _p(start), _p(out), _p(workspace), B, T, H, Hkv, dh, cap,
+                                             window, int(ring), scale))
 
 
 def repeat_kv_fwd(dev, x, ldx, y, ldy, rows, Hkv, G, dh):

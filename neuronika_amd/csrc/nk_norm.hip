@@ -14,6 +14,7 @@
 #include "nk_optim_multi.h"
 #include "nk_attention_decode.h"
 #include "nk_attention_gqa.h"
+#include "nk_attention_window.h"
 #include "nk_repeat_kv.h"
 #include "nk_rope.h"
 #include "nk_sampling.h"
