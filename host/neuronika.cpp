@@ -776,9 +776,16 @@ struct HeadsAttentionFwd : Forward {
     uint64_t seed;
     Shared<uint64_t> calls;  // each forward draws a fresh mask (the Philox offset advances), as AttnProbsFwd
     bool causal = false;     // nk_attention_causal_*: query r attends to keys <= r (same draws, same offset advance)
+    int window = 0;          // > 0: nk_attention_band_*, query r attends to keys r - window < k <= r; scores / mask are the banded scratch
     void forward() const override {
         const uint64_t sp = ((uint64_t)hg.S + 31) / 32 * 32;  // the draws are indexed in the padded (B*H, SP, SP) tensor (SP = S unless S is ragged)
         const uint64_t offset = (*calls) * (((uint64_t)hg.B * hg.H * sp * sp + 7) / 8);  // draws per forward, 8 per Philox call
+        if (window > 0) {  // (the band keeps its state in every graph: scores and stats are never null here)
+            check(nk_attention_band_fwd(D(q), q->ptr(), k->ptr(), v->ptr(), scores->ptr(), stats->ptr(), reinterpret_cast<uint32_t*>(mask->ptr()),
+                                        o->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p, *status ? 1 : 0, seed, offset, window));
+            ++(*calls);
+            return;
+        }
         // scores / stats / mask are null in a graph without gradients: nothing is kept, no (B*H, S, S) tensor exists
         check((causal ? nk_attention_causal_fwd : nk_attention_fwd)(D(q), q->ptr(), k->ptr(), v->ptr(), scores ? scores->ptr() : nullptr, stats ? stats->ptr() : nullptr,
                                mask ? reinterpret_cast<uint32_t*>(mask->ptr()) : nullptr, o->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
@@ -795,6 +802,7 @@ struct HeadsAttentionBwd : Backward {
     double p;
     Shared<bool> status;
     bool causal = false;
+    int window = 0;  // as the forward node
     void backward() const override {
         const HipArray& G = g->borrow();  // dO, flat layout
         nk_device* dev = D(q);
@@ -802,6 +810,12 @@ struct HeadsAttentionBwd : Backward {
         float* gq = first_write(dq, bq);
         float* gk = first_write(dk, bk);
         float* gv = first_write(dv, bv);
+        if (window > 0) {
+            check(nk_attention_band_bwd(dev, gq, gk, gv, ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
+                                        reinterpret_cast<const uint32_t*>(mask->ptr()), q->ptr(), k->ptr(), v->ptr(), hg.B, hg.S, hg.H, hg.dh, scale,
+                                        p, *status ? 1 : 0, bq == 0.f ? 1 : 0, bk == 0.f ? 1 : 0, bv == 0.f ? 1 : 0, window));
+            return;
+        }
         // dS and Pd are written by the fused kernel, dQ comes out of it; dK / dV are the two batched products on dS / Pd
         check((causal ? nk_attention_causal_bwd : nk_attention_bwd)(dev, gq, gk, gv, ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
                                reinterpret_cast<const uint32_t*>(mask->ptr()), q->ptr(), k->ptr(), v->ptr(), hg.B, hg.S, hg.H, hg.dh, scale,
@@ -840,6 +854,7 @@ struct QkvAttentionFwd : Forward {
     uint64_t seed;
     Shared<uint64_t> calls;
     bool causal = false;
+    int window = 0;         // > 0: nk_attention_qkv_band_* on the banded scratch
     Shared<HipArray> rope;  // the rotary table or null; rg: 2 H heads over the Q|K blocks
     RopeGeom rg;
     void forward() const override {
@@ -848,6 +863,12 @@ struct QkvAttentionFwd : Forward {
         if (rope) rope_inplace(D(x), qkv->ptr(), 3 * d, rope, nullptr, rg, false);
         const uint64_t sp = ((uint64_t)hg.S + 31) / 32 * 32;
         const uint64_t offset = (*calls) * (((uint64_t)hg.B * hg.H * sp * sp + 7) / 8);
+        if (window > 0) {
+            check(nk_attention_qkv_band_fwd(D(x), qkv->ptr(), scores->ptr(), stats->ptr(), reinterpret_cast<uint32_t*>(mask->ptr()), o->ptr(), hg.B,
+                                            hg.S, hg.H, hg.dh, scale, p, *status ? 1 : 0, seed, offset, window));
+            ++(*calls);
+            return;
+        }
         check((causal ? nk_attention_qkv_causal_fwd : nk_attention_qkv_fwd)(D(x), qkv->ptr(), scores ? scores->ptr() : nullptr, stats ? stats->ptr() : nullptr,
                                    mask ? reinterpret_cast<uint32_t*>(mask->ptr()) : nullptr, o->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
                                    *status ? 1 : 0, seed, offset));
@@ -864,6 +885,7 @@ struct QkvAttentionBwd : Backward {
     double p;
     Shared<bool> status;
     bool causal = false;
+    int window = 0;
     Shared<HipArray> rope;  // as in the forward node: [dQ | dK] of the rotated rows go back through R^T in place
     RopeGeom rg;
     // the three views are written by ONE kernel: it may assign only when all three still wait for their zero fill
@@ -881,9 +903,15 @@ struct QkvAttentionBwd : Backward {
         const HipArray& G = g->borrow();  // dO (B*S, d)
         nk_device* dev = D(x);
         const int n = hg.B * hg.S, d = hg.d();
-        check((causal ? nk_attention_qkv_causal_bwd : nk_attention_qkv_bwd)(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
-                                   reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
-                                   *status ? 1 : 0, 1));
+        if (window > 0) {
+            check(nk_attention_qkv_band_bwd(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
+                                            reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
+                                            *status ? 1 : 0, 1, window));
+        } else {
+            check((causal ? nk_attention_qkv_causal_bwd : nk_attention_qkv_bwd)(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
+                                       reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
+                                       *status ? 1 : 0, 1));
+        }
         if (rope) rope_inplace(dev, dqkv->ptr(), 3 * d, rope, nullptr, rg, true);
         float beta;
         if (dx) {  // dX (+)= [dQ | dK | dV] . [Wq; Wk; Wv]: one NN product, K = 3d
@@ -2115,8 +2143,20 @@ VarDiff VarDiff::heads_context(const VarDiff& values, int B, int S, int H, int d
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(h));
 }
 bool Var::attention_core_supported(int S, int dh, double p) { return nk_attention_supported(S, dh, p, 1) != 0; }
+// The banded scratch of the sliding-window core, sized by the library's three geometry functions and allocated WITHOUT a fill: the
+// kernels define every element they read, and an O(S * ld) memset per graph would be pure loss.
+struct BandScratch { Shape scores, mask; };
+static BandScratch band_scratch(int B, int S, int H, int window) {
+    const size_t ext = nk_attention_band_scratch(S, window), words = nk_attention_band_mask_words(S, window);
+    if (ext > 0x7fffffffu || words > 0x7fffffffu) panic("heads_attention: the banded scratch of one head exceeds 2^31 elements");
+    return {Shape{B * H, (int)ext}, Shape{B * H, (int)words}};
+}
+static Shared<HipArray> uninit_like(const Shared<HipArray>& a, Shape s) { return std::make_shared<HipArray>(a->device(), std::move(s), HipArray::Uninit{}); }
 static Var heads_attention_node(const Var& q, const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
-                                Shared<bool> status, bool keep, bool causal) {
+                                Shared<bool> status, bool keep, bool causal, int window) {
+    if (window < 0) panic("heads_attention: window must not be negative, got " + std::to_string(window));
+    if (window > 0 && !causal) panic("heads_attention: a sliding window is a band of the CAUSAL triangle: set causal = true");
+    const int band = window > 0 && S > window ? window : 0;  // S <= window: the band is the whole triangle, the causal kernels as they are
     if (!(p >= 0.0 && p <= 1.0)) panic("Wrong probability received: " + std::to_string(p) + ".");
     check_heads(q.shape(), {}, B, S, H, dh, false);
     check_heads(keys.shape(), {}, B, S, H, dh, false);
@@ -2127,26 +2167,31 @@ static Var heads_attention_node(const Var& q, const Var& keys, const Var& values
     h.merge(values.history);
     auto op = std::make_shared<HeadsAttentionFwd>();
     op->hg = {B, S, H, dh}; op->q = q.data; op->k = keys.data; op->v = values.data;
-    if (keep) {  // what the backward node reads; a graph without gradients keeps nothing
+    if (band) {  // the band kernels keep their state in every graph
+        const BandScratch bs = band_scratch(B, S, H, band);
+        op->scores = uninit_like(q.data, bs.scores);
+        op->stats = uninit_like(q.data, Shape{B * H, (S + 31) / 32 * 32, 2});
+        op->mask = uninit_like(q.data, bs.mask);
+    } else if (keep) {  // what the backward node reads; a graph without gradients keeps nothing
         const int SP = (S + 31) / 32 * 32;  // the scratch tensors are padded to whole 32 x 32 tiles (include/neuronika_hip.h)
         op->scores = zeros_like(q.data, Shape{B * H, SP, SP});
         op->stats = zeros_like(q.data, Shape{B * H, SP, 2});
         op->mask = zeros_like(q.data, Shape{B * H, SP, SP / 32});
     }
     op->o = zeros_like(q.data, Shape{B * S, H * dh});
-    op->scale = scale; op->p = p; op->status = std::move(status); op->causal = causal;
+    op->scale = scale; op->p = p; op->status = std::move(status); op->causal = causal; op->window = band;
     op->seed = next_node_seed();
     op->calls = std::make_shared<uint64_t>(0);
     auto y = op->o;
     return Var::node(y, op, std::move(h));
 }
 Var Var::heads_attention(const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
-                         Shared<bool> status, bool causal) const {
-    return heads_attention_node(*this, keys, values, B, S, H, dh, scale, p, std::move(status), false, causal);
+                         Shared<bool> status, bool causal, int window) const {
+    return heads_attention_node(*this, keys, values, B, S, H, dh, scale, p, std::move(status), false, causal, window);
 }
 VarDiff VarDiff::heads_attention(const VarDiff& keys, const VarDiff& values, int B, int S, int H, int dh, float scale, double p,
-                                 Shared<bool> status, bool causal) const {
-    Var out = heads_attention_node(var, keys.var, values.var, B, S, H, dh, scale, p, status, true, causal);
+                                 Shared<bool> status, bool causal, int window) const {
+    Var out = heads_attention_node(var, keys.var, values.var, B, S, H, dh, scale, p, status, true, causal, window);
     auto fwd = std::dynamic_pointer_cast<HeadsAttentionFwd>(out.history.to_vec().back().op);
     History<BackwardEntry> h = history;
     h.merge(keys.history);
@@ -2154,10 +2199,10 @@ VarDiff VarDiff::heads_attention(const VarDiff& keys, const VarDiff& values, int
     auto g = std::make_shared<Gradient>(out.device(), out.shape());
     auto bw = std::make_shared<HeadsAttentionBwd>();
     bw->hg = fwd->hg; bw->q = fwd->q; bw->k = fwd->k; bw->v = fwd->v; bw->scores = fwd->scores; bw->stats = fwd->stats; bw->mask = fwd->mask; bw->o = fwd->o;
-    bw->ds = zeros_like(fwd->scores, fwd->scores->shape());
-    bw->dropped = zeros_like(fwd->scores, fwd->scores->shape());
+    bw->ds = fwd->window ? uninit_like(fwd->scores, fwd->scores->shape()) : zeros_like(fwd->scores, fwd->scores->shape());
+    bw->dropped = fwd->window ? uninit_like(fwd->scores, fwd->scores->shape()) : zeros_like(fwd->scores, fwd->scores->shape());
     bw->dq = grad; bw->dk = keys.grad; bw->dv = values.grad; bw->g = g;
-    bw->scale = scale; bw->p = p; bw->status = status; bw->causal = causal;
+    bw->scale = scale; bw->p = p; bw->status = status; bw->causal = causal; bw->window = fwd->window;
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(h));
 }
 Var Var::bmm(const Var& rhs) const { return matmul_var(2, *this, rhs); }
@@ -3081,11 +3126,19 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     fw->hg = {B, S, H, dh}; fw->x = x.var.data; fw->w = w; fw->b = b;
     fw->qkv = zeros_like(x.var.data, Shape{B * S, 3 * d});
     const int SP = (S + 31) / 32 * 32;
-    fw->scores = zeros_like(x.var.data, Shape{B * H, SP, SP});
-    fw->stats = zeros_like(x.var.data, Shape{B * H, SP, 2});
-    fw->mask = zeros_like(x.var.data, Shape{B * H, SP, SP / 32});
+    const int band = m.window > 0 && S > m.window ? m.window : 0;  // (forward() checked window >= 0 and causal)
+    if (band) {
+        const BandScratch bs = band_scratch(B, S, H, band);
+        fw->scores = uninit_like(x.var.data, bs.scores);
+        fw->stats = uninit_like(x.var.data, Shape{B * H, SP, 2});
+        fw->mask = uninit_like(x.var.data, bs.mask);
+    } else {
+        fw->scores = zeros_like(x.var.data, Shape{B * H, SP, SP});
+        fw->stats = zeros_like(x.var.data, Shape{B * H, SP, 2});
+        fw->mask = zeros_like(x.var.data, Shape{B * H, SP, SP / 32});
+    }
     fw->o = zeros_like(x.var.data, Shape{B * S, d});
-    fw->scale = scale; fw->p = m.drop.p; fw->status = m.drop.status; fw->causal = m.causal;
+    fw->scale = scale; fw->p = m.drop.p; fw->status = m.drop.status; fw->causal = m.causal; fw->window = band;
     fw->seed = next_node_seed();
     fw->calls = std::make_shared<uint64_t>(0);
     if (m.rope) { fw->rope = m.rope->table; fw->rg = rope_geom(*m.rope, B, S, 2 * H); }
@@ -3096,13 +3149,13 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     auto bw = std::make_shared<QkvAttentionBwd>();
     bw->hg = fw->hg; bw->x = fw->x; bw->w = w; bw->qkv = fw->qkv; bw->scores = fw->scores; bw->stats = fw->stats; bw->mask = fw->mask; bw->o = fw->o;
     bw->dqkv = zeros_like(fw->qkv, fw->qkv->shape());
-    bw->ds = zeros_like(fw->scores, fw->scores->shape());
-    bw->dropped = zeros_like(fw->scores, fw->scores->shape());
+    bw->ds = band ? uninit_like(fw->scores, fw->scores->shape()) : zeros_like(fw->scores, fw->scores->shape());
+    bw->dropped = band ? uninit_like(fw->scores, fw->scores->shape()) : zeros_like(fw->scores, fw->scores->shape());
     bw->gw_all = gw; bw->gb_all = gb;
     bw->dx = x.grad;
     const Linear* ls[3] = {&m.q, &m.k, &m.v};
     for (int i = 0; i < 3; ++i) { bw->gw[i] = ls[i]->weight.grad; bw->gb[i] = ls[i]->bias.grad; }
-    bw->g = g; bw->scale = scale; bw->p = m.drop.p; bw->status = m.drop.status; bw->causal = m.causal;
+    bw->g = g; bw->scale = scale; bw->p = m.drop.p; bw->status = m.drop.status; bw->causal = m.causal; bw->window = band;
     bw->rope = fw->rope; bw->rg = fw->rg;
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(hb));
 }
@@ -3143,8 +3196,9 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
     // Causal, where the fused core does not apply: the composition spelled out - one Addition node (broadcast over B*H) of a
     // constant (S, S) leaf, 0 on and below the diagonal and -inf above, in front of the Softmax, whose -inf lanes come out exactly 0.
     // Uploaded once per graph build; the fused `attention_probs` node has no mask operand and is not used.
-    // With a window shorter than S the constant is banded - also -inf at k <= r - window - and the fused core, which has no window,
-    // is not taken; every row keeps its diagonal.
+    // With a window shorter than S the constant is banded - also -inf at k <= r - window; every row keeps its diagonal.  The fused
+    // core takes the window where it takes the head size (nk_attention_band_*: the key tiles left of the band are skipped too and the
+    // scratch is banded); this composition stays for the other head sizes and for fused_core = false.
     auto causal_mask = [&](int n) {
         std::vector<float> m((size_t)n * n, 0.f);
         for (int r = 0; r < n; ++r) {
@@ -3154,13 +3208,13 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
         }
         return from_host(x.var.device(), Shape{n, n}, m.data());
     };
-    if (!banded && G == 1 && packed_qkv && wqkv_ && strided_heads && fused && fused_core && q.fused && k.fused && v.fused && Var::attention_core_supported(S, dh, drop.p) &&
+    if (G == 1 && packed_qkv && wqkv_ && strided_heads && fused && fused_core && q.fused && k.fused && v.fused && Var::attention_core_supported(S, dh, drop.p) &&
         still_packed())
         return o.forward(qkv_attention_node(*this, wqkv_, bqkv_, gwqkv_, gbqkv_, x, batch, S, heads, dh, scale));
     if (strided_heads && dh % 4 == 0) {  // attention GEMMs address the heads inside the projection layout: no copies
         const VarDiff Qf = rotated(q, heads), Kf = keys(), Vf = values();
-        if (!banded && fused && fused_core && Var::attention_core_supported(S, dh, drop.p))
-            return o.forward(Qf.heads_attention(Kf, Vf, batch, S, heads, dh, scale, drop.p, drop.status, causal));
+        if (fused && fused_core && Var::attention_core_supported(S, dh, drop.p))
+            return o.forward(Qf.heads_attention(Kf, Vf, batch, S, heads, dh, scale, drop.p, drop.status, causal, window));
         const VarDiff scores = Qf.heads_scores(Kf, batch, S, heads, dh);
         const VarDiff P = causal ? drop.forward((scores * scale + causal_mask(S)).softmax(2))
                           : (fused && S % 4 == 0 && S <= 2048) ? scores.attention_probs(scale, drop.p, drop.status)

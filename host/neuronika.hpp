@@ -402,8 +402,11 @@ class Var {
     // attention kernels (nk_attention_fwd): self = Q, all three operands (B*S, H*dh) -> (B*S, H*dh).  The score tile
     // stays on chip between the two products; see attention_core_supported() for the shapes it takes.
     // causal: query r attends to keys <= r (nk_attention_causal_fwd; the composition gains one Addition node in front of the Softmax)
+    // window > 0 (needs causal): query r attends to keys r - window < k <= r.  S <= window is the causal node as it is; S > window
+    // runs nk_attention_band_* on banded scratch sized by nk_attention_band_scratch / _mask_words and allocated without a fill -
+    // in a graph without gradients too (the band kernels have no inference form).
     Var heads_attention(const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
-                        Shared<bool> status, bool causal = false) const;
+                        Shared<bool> status, bool causal = false, int window = 0) const;
     static bool attention_core_supported(int S, int dh, double p);
 };
 
@@ -534,7 +537,7 @@ class VarDiff {
     VarDiff heads_context(const VarDiff& values, int B, int S, int H, int dh) const;
     VarDiff attention_probs(float scale, double p, Shared<bool> status, bool store_probs = false) const;
     VarDiff heads_attention(const VarDiff& keys, const VarDiff& values, int B, int S, int H, int dh, float scale, double p,
-                            Shared<bool> status, bool causal = false) const;
+                            Shared<bool> status, bool causal = false, int window = 0) const;
 };
 
 // `Add/Sub/Mul/Div` with NumPy broadcasting, all four differentiability combinations
@@ -968,9 +971,12 @@ struct MultiheadAttention {
     // max(0, i - window + 1) .. i.  0 (the default) = off: every path as without it, bit for bit, same launches.  Read when
     // forward() / forward_step() build their nodes, like `causal`; window > 0 with causal == false panics.
     //   forward()       S <= window: the band is the causal triangle - the paths above untouched, fused core included.  S > window:
+    //                   where the fused core takes the head size (`Var::attention_core_supported`), the same ONE node - packed
+    //                   (`nk_attention_qkv_band_*`) or strided, GQA behind `repeat_kv` - on the band kernels: they walk the key tiles
+    //                   between the band's left edge and the diagonal only, O(S * window) work, and keep scores / dS / Pd in banded
+    //                   scratch of O(S * window) floats that is allocated without a fill.  Other head sizes and fused_core = false:
     //                   the node-by-node paths (`heads_scores` / `bmm_t`) with the banded constant M[r][k] = 0 for r - window < k <= r,
-    //                   -inf elsewhere, on the Addition node in place of the causal one: differentiable through the existing
-    //                   Addition / Softmax / Dropout nodes, not fast (the fused core takes no window).
+    //                   -inf elsewhere, on the Addition node in place of the causal one.
     //   forward_step()  a fresh prefill with 2 <= T <= window keeps the causal core; every other step runs
     //                   nk_attention_decode_window_fwd over its T rows, on a linear cache or a rolling one (`KvCache::rolling`,
     //                   appended through nk_kv_cache_append_ring).  A step reads at most `window` keys per kv head whatever the length.

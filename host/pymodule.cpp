@@ -100,9 +100,9 @@ PYBIND11_MODULE(_tape, m) {
         .def("mm_t", py::overload_cast<const Var&>(&Var::mm_t, py::const_))
         .def("mm_t", py::overload_cast<const VarDiff&>(&Var::mm_t, py::const_))
         .def("heads_attention", [](const Var& q, const Var& k, const Var& v, int B, int S, int H, int dh, float scale, double p, const Status& s,
-                                   bool causal) { return q.heads_attention(k, v, B, S, H, dh, scale, p, s.flag, causal); },
+                                   bool causal, int window) { return q.heads_attention(k, v, B, S, H, dh, scale, p, s.flag, causal, window); },
              py::arg("keys"), py::arg("values"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("dh"), py::arg("scale"), py::arg("p"),
-             py::arg("status"), py::arg("causal") = false)
+             py::arg("status"), py::arg("causal") = false, py::arg("window") = 0)
         .def_static("attention_core_supported", &Var::attention_core_supported)
         .def("convolution", &Var::convolution)
         .def("__add__", [](const Var& a, const Var& b) { return a + b; })
@@ -183,9 +183,9 @@ PYBIND11_MODULE(_tape, m) {
         .def("mm_t", py::overload_cast<const Var&>(&VarDiff::mm_t, py::const_))
         .def("mm_t", py::overload_cast<const VarDiff&>(&VarDiff::mm_t, py::const_))
         .def("heads_attention", [](const VarDiff& q, const VarDiff& k, const VarDiff& v, int B, int S, int H, int dh, float scale, double p,
-                                   const Status& s, bool causal) { return q.heads_attention(k, v, B, S, H, dh, scale, p, s.flag, causal); },
+                                   const Status& s, bool causal, int window) { return q.heads_attention(k, v, B, S, H, dh, scale, p, s.flag, causal, window); },
              py::arg("keys"), py::arg("values"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("dh"), py::arg("scale"), py::arg("p"),
-             py::arg("status"), py::arg("causal") = false)
+             py::arg("status"), py::arg("causal") = false, py::arg("window") = 0)
         .def("convolution", py::overload_cast<const Var&, const std::vector<int>&, const std::vector<int>&, int>(&VarDiff::convolution, py::const_))
         .def("convolution", py::overload_cast<const VarDiff&, const std::vector<int>&, const std::vector<int>&, int>(&VarDiff::convolution, py::const_))
         .def("__add__", [](const VarDiff& a, const Var& b) { return a + b; })

@@ -852,6 +852,44 @@ int nk_attention_qkv_causal_fwd(nk_device* dev, const float* QKV, float* scores,
 int nk_attention_qkv_causal_bwd(nk_device* dev, float* dQKV, float* dS, float* dropped, const float* dO, const float* O,
                                 const float* scores, const float* stats, const uint32_t* mask_bits, const float* QKV, int B, int S, int H,
                                 int dh, float scale, double p, int train, int assign);
+/* Sliding-window (banded causal) self-attention: query row r attends to the key rows max(0, r - window + 1) .. r.  As a composition
+ * it is the causal chain above with the BANDED constant M[r][k] = 0 for r - window < k <= r and -inf elsewhere; every row keeps its
+ * diagonal.  The causal entry points' parameter lists plus `window`, the same projection layouts, row statistics ((B*H, SP, 2), over
+ * the unmasked keys) and draw positions: score (bh, r, k) takes draw (bh*SP + r)*SP + k of the PADDED (B*H, SP, SP) index space and one
+ * forward consumes ceil(B*H*SP*SP / 8) calls, so the mask agrees with nk_dropout_fwd's and the composed path's position for position.
+ * Work and scratch are O(S * window).  With k_lo(qb) = max(0, 128 qb - window + 1) and js(qb) = k_lo(qb) / 128, the block of queries
+ * 128 qb .. stages the key tiles 4 js(qb) .. min(SP / 32, 4 qb + 4) - 1 only, and its wave of rows r0 = 128 qb + 32 w .. computes the
+ * tiles max(0, r0 - window + 1) / 32 .. 4 qb + w of them.
+ * Banded scratch: `scores`, `dS` and `dropped` hold, per (sample, head), nk_attention_band_scratch(S, window) = (SP - 1) * ld + SP
+ * floats; element (r, k) is at bh * that + r * ld + k with ld = nk_attention_band_ld(S, window) = min(SP, 128 * (ceil((window - 1) /
+ * 128) + 1)) - the (SP, SP) matrix with a row stride shorter than its width.  A row's touched columns start at 128 js(r / 128), which
+ * never decreases with r, and span at most ld, so no two touched elements share an address.  `mask_bits` holds, per (sample, head),
+ * nk_attention_band_mask_words(S, window) = SP * ld / 32 words laid out [SP/32 query tiles][ld/32 key tiles, counted from tile
+ * 4 js(qb) of the query tile's block][32 queries], bits as in nk_attention_fwd.  window >= S: ld = SP and the causal layouts.
+ * Scratch contract: scores are written on the computed tiles, -inf at masked positions (padded keys included); the backward defines
+ * dS and Pd - exactly 0 at masked positions - on every 128 x 128 block (qb, j) with js(qb) <= j <= qb.  Nothing else is written or
+ * read: the buffers need no initialisation.  dK_bh (+)= dS_bh^T.Q_bh and dV_bh (+)= Pd_bh^T.dO_bh run per strip of 128 keys over the
+ * queries of the blocks that staged the strip.  For window >= S every output and every scratch element on the triangle has the bits
+ * of the causal entry points.
+ * NK_ERR_INVALID, nothing written: window <= 0; `scores` or `stats` NULL (there is no inference form: the forward keeps its state);
+ * everything the causal entry points refuse, the 2^31 limit on the mask words taken on the banded extent.  The training-mode
+ * forward with dropout active refuses stream capture (the Philox offset would be frozen); the evaluation forward can be captured.
+ * The three geometry functions need no device and return 0 for S <= 0 or window <= 0. */
+int nk_attention_band_ld(int S, int window);
+size_t nk_attention_band_scratch(int S, int window);
+size_t nk_attention_band_mask_words(int S, int window);
+int nk_attention_band_fwd(nk_device* dev, const float* Q, const float* K, const float* V, float* scores, float* stats,
+                          uint32_t* mask_bits, float* O, int B, int S, int H, int dh, float scale, double p, int train,
+                          uint64_t seed, uint64_t offset, int window);
+int nk_attention_band_bwd(nk_device* dev, float* dQ, float* dK, float* dV, float* dS, float* dropped, const float* dO,
+                          const float* O, const float* scores, const float* stats, const uint32_t* mask_bits, const float* Q,
+                          const float* K, const float* V, int B, int S, int H, int dh, float scale, double p, int train,
+                          int assign_dq, int assign_dk, int assign_dv, int window);
+int nk_attention_qkv_band_fwd(nk_device* dev, const float* QKV, float* scores, float* stats, uint32_t* mask_bits, float* O, int B,
+                              int S, int H, int dh, float scale, double p, int train, uint64_t seed, uint64_t offset, int window);
+int nk_attention_qkv_band_bwd(nk_device* dev, float* dQKV, float* dS, float* dropped, const float* dO, const float* O,
+                              const float* scores, const float* stats, const uint32_t* mask_bits, const float* QKV, int B, int S, int H,
+                              int dh, float scale, double p, int train, int assign, int window);
 /* ------------------------------------------------------------------ incremental decoding --
  * The causal forward above, one slice of T positions at a time, in inference (no dropout, nothing kept for a backward pass): each
  * layer's keys and values stay on the device and the new rows attend to them.  For sample b, head h and the t-th new row

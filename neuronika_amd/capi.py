@@ -209,6 +209,17 @@ _SIGS = {
     "nk_attention_qkv_causal_fwd": [VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_attention_qkv_causal_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_int],
     "nk_kv_cache_append": [VP, VP, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_attention_band_ld": [C.c_int, C.c_int],
+    "nk_attention_band_scratch": [C.c_int, C.c_int],
+    "nk_attention_band_mask_words": [C.c_int, C.c_int],
+    "nk_attention_band_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64,
+                              C.c_int],
+    "nk_attention_band_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double,
+                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_attention_qkv_band_fwd": [VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64,
+                                  C.c_int],
+    "nk_attention_qkv_band_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_int,
+                                  C.c_int],
     "nk_attention_decode_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float],
     "nk_attention_decode_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_attention_decode_chunk": [C.c_int],
@@ -266,7 +277,7 @@ _SIGS = {
 }
 _RESTYPES = {"nk_last_error": C.c_char_p, "nk_version": C.c_char_p, "nk_stream_compute": VP, "nk_stream_comm": VP,
              "nk_attention_decode_workspace": C.c_size_t, "nk_attention_decode_window_workspace": C.c_size_t,
-             "nk_gemm_buffer_records": C.c_longlong}
+             "nk_gemm_buffer_records": C.c_longlong, "nk_attention_band_scratch": C.c_size_t, "nk_attention_band_mask_words": C.c_size_t}
 EXPORTED = tuple(_SIGS)
 
 for _name, _args in _SIGS.items():
@@ -1113,6 +1124,51 @@ def attention_qkv_bwd(dev, dQKV, dS, dropped, dO, out, scores, stats, mask_bits,
                       causal=False):
     check((lib.nk_attention_qkv_causal_bwd if causal else lib.nk_attention_qkv_bwd)(dev.h, dQKV.p, dS.p, dropped.p, dO.p, out.p, scores.p, stats.p,
                                    mask_bits.p if mask_bits is not None else None, QKV.p, B, S, H, dh, scale, float(p), int(train), int(assign)))
+
+
+def attention_band_ld(S, window) -> int:
+    """Row stride of the banded scores / dS / dropped scratch: min(SP, 128 * (ceil((window - 1) / 128) + 1)); needs no device."""
+    return int(lib.nk_attention_band_ld(int(S), int(window)))
+
+
+def attention_band_scratch(S, window) -> int:
+    """Floats per (sample, head) of each of scores / dS / dropped: (SP - 1) * ld + SP; element (r, k) is at r * ld + k."""
+    return int(lib.nk_attention_band_scratch(int(S), int(window)))
+
+
+def attention_band_mask_words(S, window) -> int:
+    """Mask words per (sample, head): [SP/32 query tiles][ld/32 key tiles from the block's first staged tile][32 queries]."""
+    return int(lib.nk_attention_band_mask_words(int(S), int(window)))
+
+
+def _opt(a):
+    return a.p if a is not None else None
+
+
+def attention_band_fwd(dev, Q, K, V, scores, stats, mask_bits, out, B, S, H, dh, scale, p, train=True, seed=0, offset=0, *, window):
+    """Sliding-window fused core: query r attends to keys max(0, r - window + 1) .. r.  scores: B*H*attention_band_scratch floats,
+    stats (B*H,SP,2), mask_bits: B*H*attention_band_mask_words words (None when dropout is inactive), out (B*S,H*dh)."""
+    check(lib.nk_attention_band_fwd(dev.h, Q.p, K.p, V.p, _opt(scores), _opt(stats), _opt(mask_bits), out.p, B, S, H, dh, scale, float(p),
+                                    int(train), seed, offset, int(window)))
+
+
+def attention_band_bwd(dev, dQ, dK, dV, dS, dropped, dO, out, scores, stats, mask_bits, Q, K, V, B, S, H, dh, scale, p, train=True,
+                       assign=(False, False, False), *, window):
+    """dS and dropped (banded scratch) are written on the 128 x 128 blocks the forward staged; dQ / dK / dV (+)= the gradients."""
+    check(lib.nk_attention_band_bwd(dev.h, dQ.p, dK.p, dV.p, dS.p, dropped.p, dO.p, out.p, scores.p, stats.p, _opt(mask_bits), Q.p, K.p, V.p,
+                                    B, S, H, dh, scale, float(p), int(train), int(assign[0]), int(assign[1]), int(assign[2]), int(window)))
+
+
+def attention_qkv_band_fwd(dev, QKV, scores, stats, mask_bits, out, B, S, H, dh, scale, p, train=True, seed=0, offset=0, *, window):
+    """attention_band_fwd with Q, K, V as the three column blocks of ONE (B*S, 3*H*dh) array."""
+    check(lib.nk_attention_qkv_band_fwd(dev.h, QKV.p, _opt(scores), _opt(stats), _opt(mask_bits), out.p, B, S, H, dh, scale, float(p),
+                                        int(train), seed, offset, int(window)))
+
+
+def attention_qkv_band_bwd(dev, dQKV, dS, dropped, dO, out, scores, stats, mask_bits, QKV, B, S, H, dh, scale, p, train=True, assign=False,
+                           *, window):
+    check(lib.nk_attention_qkv_band_bwd(dev.h, dQKV.p, dS.p, dropped.p, dO.p, out.p, scores.p, stats.p, _opt(mask_bits), QKV.p, B, S, H, dh,
+                                        scale, float(p), int(train), int(assign), int(window)))
 
 
 def chunk_fwd(dev, x, y, chunk_no):

@@ -15,6 +15,7 @@
 #include "nk_attention_decode.h"
 #include "nk_attention_gqa.h"
 #include "nk_attention_window.h"
+#include "nk_attention_band.h"
 #include "nk_repeat_kv.h"
 #include "nk_rope.h"
 #include "nk_sampling.h"
