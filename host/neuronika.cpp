@@ -777,9 +777,17 @@ struct HeadsAttentionFwd : Forward {
     Shared<uint64_t> calls;  // each forward draws a fresh mask (the Philox offset advances), as AttnProbsFwd
     bool causal = false;     // nk_attention_causal_*: query r attends to keys <= r (same draws, same offset advance)
     int window = 0;          // > 0: nk_attention_band_*, query r attends to keys r - window < k <= r; scores / mask are the banded scratch
+    Shared<HipArray> seg;    // (B, S) int32 left edges: nk_attention_seg_* with span = `window`, which sizes the same scratch
     void forward() const override {
         const uint64_t sp = ((uint64_t)hg.S + 31) / 32 * 32;  // the draws are indexed in the padded (B*H, SP, SP) tensor (SP = S unless S is ragged)
         const uint64_t offset = (*calls) * (((uint64_t)hg.B * hg.H * sp * sp + 7) / 8);  // draws per forward, 8 per Philox call
+        if (seg) {
+            check(nk_attention_seg_fwd(D(q), q->ptr(), k->ptr(), v->ptr(), reinterpret_cast<const int*>(seg->ptr()), scores->ptr(), stats->ptr(),
+                                       reinterpret_cast<uint32_t*>(mask->ptr()), o->ptr(), hg.B, hg.S, hg.H, hg.dh, window, scale, p, *status ? 1 : 0,
+                                       seed, offset));
+            ++(*calls);
+            return;
+        }
         if (window > 0) {  // (the band keeps its state in every graph: scores and stats are never null here)
             check(nk_attention_band_fwd(D(q), q->ptr(), k->ptr(), v->ptr(), scores->ptr(), stats->ptr(), reinterpret_cast<uint32_t*>(mask->ptr()),
                                         o->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p, *status ? 1 : 0, seed, offset, window));
@@ -803,6 +811,7 @@ struct HeadsAttentionBwd : Backward {
     Shared<bool> status;
     bool causal = false;
     int window = 0;  // as the forward node
+    Shared<HipArray> seg;
     void backward() const override {
         const HipArray& G = g->borrow();  // dO, flat layout
         nk_device* dev = D(q);
@@ -810,6 +819,13 @@ struct HeadsAttentionBwd : Backward {
         float* gq = first_write(dq, bq);
         float* gk = first_write(dk, bk);
         float* gv = first_write(dv, bv);
+        if (seg) {
+            check(nk_attention_seg_bwd(dev, gq, gk, gv, ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
+                                       reinterpret_cast<const uint32_t*>(mask->ptr()), q->ptr(), k->ptr(), v->ptr(),
+                                       reinterpret_cast<const int*>(seg->ptr()), hg.B, hg.S, hg.H, hg.dh, window, scale, p, *status ? 1 : 0,
+                                       bq == 0.f ? 1 : 0, bk == 0.f ? 1 : 0, bv == 0.f ? 1 : 0));
+            return;
+        }
         if (window > 0) {
             check(nk_attention_band_bwd(dev, gq, gk, gv, ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
                                         reinterpret_cast<const uint32_t*>(mask->ptr()), q->ptr(), k->ptr(), v->ptr(), hg.B, hg.S, hg.H, hg.dh, scale,
@@ -855,14 +871,23 @@ struct QkvAttentionFwd : Forward {
     Shared<uint64_t> calls;
     bool causal = false;
     int window = 0;         // > 0: nk_attention_qkv_band_* on the banded scratch
+    Shared<HipArray> seg;   // (B, S) int32 left edges: nk_attention_qkv_seg_* with span = `window`
     Shared<HipArray> rope;  // the rotary table or null; rg: 2 H heads over the Q|K blocks
     RopeGeom rg;
+    Shared<HipArray> rope_start;  // packed sequences: one position per row (rg.B = B*S, rg.T = 1)
     void forward() const override {
         const int n = hg.B * hg.S, d = hg.d();
         check(nk_linear_fwd(D(x), x->ptr(), w->ptr(), b->ptr(), qkv->ptr(), n, d, 3 * d));
-        if (rope) rope_inplace(D(x), qkv->ptr(), 3 * d, rope, nullptr, rg, false);
+        if (rope) rope_inplace(D(x), qkv->ptr(), 3 * d, rope, rope_start ? reinterpret_cast<const int*>(rope_start->ptr()) : nullptr, rg, false);
         const uint64_t sp = ((uint64_t)hg.S + 31) / 32 * 32;
         const uint64_t offset = (*calls) * (((uint64_t)hg.B * hg.H * sp * sp + 7) / 8);
+        if (seg) {
+            check(nk_attention_qkv_seg_fwd(D(x), qkv->ptr(), reinterpret_cast<const int*>(seg->ptr()), scores->ptr(), stats->ptr(),
+                                           reinterpret_cast<uint32_t*>(mask->ptr()), o->ptr(), hg.B, hg.S, hg.H, hg.dh, window, scale, p,
+                                           *status ? 1 : 0, seed, offset));
+            ++(*calls);
+            return;
+        }
         if (window > 0) {
             check(nk_attention_qkv_band_fwd(D(x), qkv->ptr(), scores->ptr(), stats->ptr(), reinterpret_cast<uint32_t*>(mask->ptr()), o->ptr(), hg.B,
                                             hg.S, hg.H, hg.dh, scale, p, *status ? 1 : 0, seed, offset, window));
@@ -886,8 +911,10 @@ struct QkvAttentionBwd : Backward {
     Shared<bool> status;
     bool causal = false;
     int window = 0;
+    Shared<HipArray> seg;
     Shared<HipArray> rope;  // as in the forward node: [dQ | dK] of the rotated rows go back through R^T in place
     RopeGeom rg;
+    Shared<HipArray> rope_start;
     // the three views are written by ONE kernel: it may assign only when all three still wait for their zero fill
     static float packed_beta(const Shared<Gradient> (&v)[3]) {
         bool all = true;
@@ -903,7 +930,11 @@ struct QkvAttentionBwd : Backward {
         const HipArray& G = g->borrow();  // dO (B*S, d)
         nk_device* dev = D(x);
         const int n = hg.B * hg.S, d = hg.d();
-        if (window > 0) {
+        if (seg) {
+            check(nk_attention_qkv_seg_bwd(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
+                                           reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), reinterpret_cast<const int*>(seg->ptr()), hg.B,
+                                           hg.S, hg.H, hg.dh, window, scale, p, *status ? 1 : 0, 1));
+        } else if (window > 0) {
             check(nk_attention_qkv_band_bwd(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
                                             reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
                                             *status ? 1 : 0, 1, window));
@@ -912,7 +943,7 @@ struct QkvAttentionBwd : Backward {
                                        reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
                                        *status ? 1 : 0, 1));
         }
-        if (rope) rope_inplace(dev, dqkv->ptr(), 3 * d, rope, nullptr, rg, true);
+        if (rope) rope_inplace(dev, dqkv->ptr(), 3 * d, rope, rope_start ? reinterpret_cast<const int*>(rope_start->ptr()) : nullptr, rg, true);
         float beta;
         if (dx) {  // dX (+)= [dQ | dK | dV] . [Wq; Wk; Wv]: one NN product, K = 3d
             float* q = first_write(dx, beta);
@@ -1049,21 +1080,23 @@ struct ActivationBwd : Backward {
 struct RopeFwd : Forward {
     RopeGeom rg;
     Shared<HipArray> x, y, table;
+    Shared<HipArray> start;  // null: positions 0 .. T-1 of every sample; else one int32 per sample (rg.T = 1: per row)
     void forward() const override {
         const int ld = rg.NH * rg.dh;
-        check(nk_rope_fwd(D(x), x->ptr(), ld, y->ptr(), ld, table->ptr(), nullptr, rg.B, rg.T, rg.NH, rg.dh, rg.rot, rg.max_pos, rg.interleaved));
+        check(nk_rope_fwd(D(x), x->ptr(), ld, y->ptr(), ld, table->ptr(), start ? reinterpret_cast<const int*>(start->ptr()) : nullptr, rg.B, rg.T, rg.NH, rg.dh, rg.rot, rg.max_pos, rg.interleaved));
     }
 };
 struct RopeBwd : Backward {
     RopeGeom rg;
-    Shared<HipArray> table;
+    Shared<HipArray> table, start;
     Shared<Gradient> dx, g;
     void backward() const override {
         const HipArray& G = g->borrow();
         bool assign = false;
         HipArray& d = dx->borrow_first_write(assign);
         const int ld = rg.NH * rg.dh;
-        check((assign ? nk_rope_bwd_assign : nk_rope_bwd)(D(table), d.ptr(), ld, G.ptr(), ld, table->ptr(), nullptr, rg.B, rg.T, rg.NH, rg.dh, rg.rot,
+        check((assign ? nk_rope_bwd_assign : nk_rope_bwd)(D(table), d.ptr(), ld, G.ptr(), ld, table->ptr(),
+                                                          start ? reinterpret_cast<const int*>(start->ptr()) : nullptr, rg.B, rg.T, rg.NH, rg.dh, rg.rot,
                                                           rg.max_pos, rg.interleaved));
     }
     void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
@@ -2153,10 +2186,18 @@ static BandScratch band_scratch(int B, int S, int H, int window) {
 }
 static Shared<HipArray> uninit_like(const Shared<HipArray>& a, Shape s) { return std::make_shared<HipArray>(a->device(), std::move(s), HipArray::Uninit{}); }
 static Var heads_attention_node(const Var& q, const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
-                                Shared<bool> status, bool keep, bool causal, int window) {
+                                Shared<bool> status, bool keep, bool causal, int window, const nn::Segments* segments) {
     if (window < 0) panic("heads_attention: window must not be negative, got " + std::to_string(window));
     if (window > 0 && !causal) panic("heads_attention: a sliding window is a band of the CAUSAL triangle: set causal = true");
-    const int band = window > 0 && S > window ? window : 0;  // S <= window: the band is the whole triangle, the causal kernels as they are
+    if (segments && !causal) panic("heads_attention: segments are blocks of the CAUSAL triangle: set causal = true");
+    if (segments && (segments->batch != B || segments->S != S))
+        panic("heads_attention: the segments were built for (batch " + std::to_string(segments->batch) + ", S " + std::to_string(segments->S) +
+              "), the call has (" + std::to_string(B) + ", " + std::to_string(S) + ")");
+    if (segments && segments->lo->device().get() != q.device().get()) panic("heads_attention: the segments live on another device");
+    int band = window > 0 && S > window ? window : 0;  // S <= window: the band is the whole triangle, the causal kernels as they are
+    // one document per sample is the call without segments; otherwise the seg kernels on the band's scratch for span = min(max_len, window)
+    const bool seg = segments && segments->max_len < S;
+    if (seg) band = band ? std::min(band, segments->max_len) : segments->max_len;
     if (!(p >= 0.0 && p <= 1.0)) panic("Wrong probability received: " + std::to_string(p) + ".");
     check_heads(q.shape(), {}, B, S, H, dh, false);
     check_heads(keys.shape(), {}, B, S, H, dh, false);
@@ -2180,18 +2221,19 @@ static Var heads_attention_node(const Var& q, const Var& keys, const Var& values
     }
     op->o = zeros_like(q.data, Shape{B * S, H * dh});
     op->scale = scale; op->p = p; op->status = std::move(status); op->causal = causal; op->window = band;
+    if (seg) op->seg = segments->lo;
     op->seed = next_node_seed();
     op->calls = std::make_shared<uint64_t>(0);
     auto y = op->o;
     return Var::node(y, op, std::move(h));
 }
 Var Var::heads_attention(const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
-                         Shared<bool> status, bool causal, int window) const {
-    return heads_attention_node(*this, keys, values, B, S, H, dh, scale, p, std::move(status), false, causal, window);
+                         Shared<bool> status, bool causal, int window, const nn::Segments* segments) const {
+    return heads_attention_node(*this, keys, values, B, S, H, dh, scale, p, std::move(status), false, causal, window, segments);
 }
 VarDiff VarDiff::heads_attention(const VarDiff& keys, const VarDiff& values, int B, int S, int H, int dh, float scale, double p,
-                                 Shared<bool> status, bool causal, int window) const {
-    Var out = heads_attention_node(var, keys.var, values.var, B, S, H, dh, scale, p, status, true, causal, window);
+                                 Shared<bool> status, bool causal, int window, const nn::Segments* segments) const {
+    Var out = heads_attention_node(var, keys.var, values.var, B, S, H, dh, scale, p, status, true, causal, window, segments);
     auto fwd = std::dynamic_pointer_cast<HeadsAttentionFwd>(out.history.to_vec().back().op);
     History<BackwardEntry> h = history;
     h.merge(keys.history);
@@ -2202,7 +2244,7 @@ VarDiff VarDiff::heads_attention(const VarDiff& keys, const VarDiff& values, int
     bw->ds = fwd->window ? uninit_like(fwd->scores, fwd->scores->shape()) : zeros_like(fwd->scores, fwd->scores->shape());
     bw->dropped = fwd->window ? uninit_like(fwd->scores, fwd->scores->shape()) : zeros_like(fwd->scores, fwd->scores->shape());
     bw->dq = grad; bw->dk = keys.grad; bw->dv = values.grad; bw->g = g;
-    bw->scale = scale; bw->p = p; bw->status = status; bw->causal = causal; bw->window = fwd->window;
+    bw->scale = scale; bw->p = p; bw->status = status; bw->causal = causal; bw->window = fwd->window; bw->seg = fwd->seg;
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(h));
 }
 Var Var::bmm(const Var& rhs) const { return matmul_var(2, *this, rhs); }
@@ -2392,6 +2434,19 @@ VarDiff VarDiff::rope(const nn::RotaryEmbedding& rotary, int batch, int heads) c
     auto bw = std::make_shared<RopeBwd>();
     bw->rg = n->rg; bw->table = n->table; bw->dx = grad; bw->g = g;
     return VarDiff::node(std::move(v), g, entry(bw, g), history);
+}
+// Packed sequences on the unpacked paths: the rope node with every ROW at its own position (nk_rope_* with B := rows, T := 1,
+// start := positions, one int32 per row).  File-local: the positions are nn::Segments' pos, which forward() holds below max_pos.
+static VarDiff rope_rows(const VarDiff& x, const nn::RotaryEmbedding& rotary, int heads, const Shared<HipArray>& positions) {
+    if (!positions || x.shape().empty() || (int)positions->len() != x.shape()[0]) panic("rope: one position per row expected");
+    auto n = rope_fwd_node(x.var, rotary, x.shape()[0], heads);
+    n->start = positions;
+    auto y = n->y;
+    Var v = Var::node(y, n, x.var.history);
+    auto g = std::make_shared<Gradient>(v.device(), v.shape());
+    auto bw = std::make_shared<RopeBwd>();
+    bw->rg = n->rg; bw->table = n->table; bw->start = n->start; bw->dx = x.grad; bw->g = g;
+    return VarDiff::node(std::move(v), g, entry(bw, g), x.history);
 }
 VarDiff VarDiff::repeat_kv(int groups, int head_dim) const {
     auto n = repeat_kv_fwd_node(var, groups, head_dim);
@@ -3118,7 +3173,7 @@ MultiheadAttention::MultiheadAttention(Linear q_, Linear k_, Linear v_, Linear o
     packed_qkv = false;
 }
 static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipArray>& w, const Shared<HipArray>& b, const Shared<HipArray>& gw,
-                                  const Shared<HipArray>& gb, const VarDiff& x, int B, int S, int H, int dh, float scale) {
+                                  const Shared<HipArray>& gb, const VarDiff& x, int B, int S, int H, int dh, float scale, const Segments* seg) {
     const int d = H * dh;
     History<ForwardEntry> hf = x.var.history;
     for (const Linear* l : {&m.q, &m.k, &m.v}) { hf.merge(l->weight.var.history); hf.merge(l->bias.var.history); }
@@ -3126,7 +3181,8 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     fw->hg = {B, S, H, dh}; fw->x = x.var.data; fw->w = w; fw->b = b;
     fw->qkv = zeros_like(x.var.data, Shape{B * S, 3 * d});
     const int SP = (S + 31) / 32 * 32;
-    const int band = m.window > 0 && S > m.window ? m.window : 0;  // (forward() checked window >= 0 and causal)
+    int band = m.window > 0 && S > m.window ? m.window : 0;  // (forward() checked window >= 0 and causal)
+    if (seg) band = band ? std::min(band, seg->max_len) : seg->max_len;  // packed sequences (max_len < S): the band's scratch at the span
     if (band) {
         const BandScratch bs = band_scratch(B, S, H, band);
         fw->scores = uninit_like(x.var.data, bs.scores);
@@ -3139,9 +3195,14 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     }
     fw->o = zeros_like(x.var.data, Shape{B * S, d});
     fw->scale = scale; fw->p = m.drop.p; fw->status = m.drop.status; fw->causal = m.causal; fw->window = band;
+    if (seg) fw->seg = seg->lo;
     fw->seed = next_node_seed();
     fw->calls = std::make_shared<uint64_t>(0);
-    if (m.rope) { fw->rope = m.rope->table; fw->rg = rope_geom(*m.rope, B, S, 2 * H); }
+    if (m.rope) {
+        fw->rope = m.rope->table;
+        fw->rg = seg ? rope_geom(*m.rope, B * S, 1, 2 * H) : rope_geom(*m.rope, B, S, 2 * H);  // packed sequences: every row at its own position
+        if (seg) fw->rope_start = seg->pos;
+    }
     Var out = Var::node(fw->o, fw, std::move(hf));
     History<BackwardEntry> hb = x.history;
     for (const Linear* l : {&m.q, &m.k, &m.v}) { hb.merge(l->weight.history); hb.merge(l->bias.history); }
@@ -3156,7 +3217,7 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     const Linear* ls[3] = {&m.q, &m.k, &m.v};
     for (int i = 0; i < 3; ++i) { bw->gw[i] = ls[i]->weight.grad; bw->gb[i] = ls[i]->bias.grad; }
     bw->g = g; bw->scale = scale; bw->p = m.drop.p; bw->status = m.drop.status; bw->causal = m.causal; bw->window = band;
-    bw->rope = fw->rope; bw->rg = fw->rg;
+    bw->rope = fw->rope; bw->rg = fw->rg; bw->rope_start = fw->rope_start; bw->seg = fw->seg;
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(hb));
 }
 // q / k / v are public members: the packed path is only valid while they still ARE the views of the packed storage
@@ -3174,9 +3235,21 @@ bool MultiheadAttention::still_packed() const {
     }
     return true;
 }
-VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
+VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const { return forward_impl(x, batch, nullptr); }
+VarDiff MultiheadAttention::forward(const VarDiff& x, int batch, const Segments& segments) const { return forward_impl(x, batch, &segments); }
+VarDiff MultiheadAttention::forward_impl(const VarDiff& x, int batch, const Segments* seg) const {
     const int rows = x.shape()[0], S = rows / batch, dh = d_model / heads;
     if (rows % batch != 0 || x.shape()[1] != d_model) panic("MultiheadAttention: bad input shape");
+    if (seg) {
+        if (!causal) panic("MultiheadAttention: segments are blocks of the CAUSAL triangle: set causal = true");
+        if (seg->batch != batch || seg->S != S)
+            panic("MultiheadAttention: the segments were built for (batch " + std::to_string(seg->batch) + ", S " + std::to_string(seg->S) +
+                  "), the call has (" + std::to_string(batch) + ", " + std::to_string(S) + ")");
+        if (seg->lo->device().get() != x.var.device().get()) panic("MultiheadAttention: the segments live on another device");
+        if (rope && seg->max_len > rope->max_pos)
+            panic("MultiheadAttention: a document of " + std::to_string(seg->max_len) + " positions exceeds rope's table of " + std::to_string(rope->max_pos));
+        if (seg->max_len >= S) seg = nullptr;  // one document per sample: lo = 0 and pos = t - the call without segments, node for node
+    }
     const float scale = 1.f / std::sqrt((float)dh);
     if (window < 0) panic("MultiheadAttention: window must not be negative, got " + std::to_string(window));
     if (window > 0 && !causal) panic("MultiheadAttention: a sliding window is a band of the CAUSAL triangle: set causal = true");
@@ -3184,10 +3257,12 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
     if (rope) {
         if (rope->head_dim != dh)
             panic("MultiheadAttention: rope was built for heads of " + std::to_string(rope->head_dim) + ", the module has heads of " + std::to_string(dh));
-        if (S > rope->max_pos) panic("MultiheadAttention: " + std::to_string(S) + " positions exceed rope's table of " + std::to_string(rope->max_pos));
+        if (!seg && S > rope->max_pos) panic("MultiheadAttention: " + std::to_string(S) + " positions exceed rope's table of " + std::to_string(rope->max_pos));
     }
     // the projections of the unpacked paths: queries and keys rotated when `rope` is set
-    auto rotated = [&](const Linear& l, int nh) { return rope ? l.forward(x).rope(*rope, batch, nh) : l.forward(x); };
+    auto rotated = [&](const Linear& l, int nh) {
+        return !rope ? l.forward(x) : seg ? rope_rows(l.forward(x), *rope, nh, seg->pos) : l.forward(x).rope(*rope, batch, nh);
+    };
     // Grouped-query attention: kv head k written G times in front of the branches below, which then run on `heads` heads as they
     // are (kv_heads == heads: no node is added)
     const int G = heads / kv_heads;
@@ -3208,15 +3283,27 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
         }
         return from_host(x.var.device(), Shape{n, n}, m.data());
     };
+    // Packed sequences on these paths: the per-sample constant, M_b[r][k] = 0 for max(lo[b][r], r - window + 1) <= k <= r and -inf
+    // elsewhere, written out for every (sample, head) - a (batch*heads, S, S) leaf, acceptable where the fused core does not apply.
+    auto segment_mask = [&](int n) {
+        std::vector<float> m((size_t)batch * heads * n * n, -INFINITY);
+        for (int bh = 0; bh < batch * heads; ++bh)
+            for (int r = 0; r < n; ++r) {
+                const int first = std::max(seg->lo_host[(size_t)(bh / heads) * n + r], banded ? r - window + 1 : 0);
+                for (int c = first; c <= r; ++c) m[((size_t)bh * n + r) * n + c] = 0.f;
+            }
+        return from_host(x.var.device(), Shape{batch * heads, n, n}, m.data());
+    };
+    auto mask_leaf = [&](int n) { return seg ? segment_mask(n) : causal_mask(n); };
     if (G == 1 && packed_qkv && wqkv_ && strided_heads && fused && fused_core && q.fused && k.fused && v.fused && Var::attention_core_supported(S, dh, drop.p) &&
         still_packed())
-        return o.forward(qkv_attention_node(*this, wqkv_, bqkv_, gwqkv_, gbqkv_, x, batch, S, heads, dh, scale));
+        return o.forward(qkv_attention_node(*this, wqkv_, bqkv_, gwqkv_, gbqkv_, x, batch, S, heads, dh, scale, seg));
     if (strided_heads && dh % 4 == 0) {  // attention GEMMs address the heads inside the projection layout: no copies
         const VarDiff Qf = rotated(q, heads), Kf = keys(), Vf = values();
         if (fused && fused_core && Var::attention_core_supported(S, dh, drop.p))
-            return o.forward(Qf.heads_attention(Kf, Vf, batch, S, heads, dh, scale, drop.p, drop.status, causal, window));
+            return o.forward(Qf.heads_attention(Kf, Vf, batch, S, heads, dh, scale, drop.p, drop.status, causal, window, seg));
         const VarDiff scores = Qf.heads_scores(Kf, batch, S, heads, dh);
-        const VarDiff P = causal ? drop.forward((scores * scale + causal_mask(S)).softmax(2))
+        const VarDiff P = causal ? drop.forward((scores * scale + mask_leaf(S)).softmax(2))
                           : (fused && S % 4 == 0 && S <= 2048) ? scores.attention_probs(scale, drop.p, drop.status)
                                                                : drop.forward((scores * scale).softmax(2));
         return o.forward(P.heads_context(Vf, batch, S, heads, dh));
@@ -3224,7 +3311,7 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch) const {
     const VarDiff Q = rotated(q, heads).split_heads(batch, S, heads, dh);
     const VarDiff K = keys().split_heads(batch, S, heads, dh);
     const VarDiff V = values().split_heads(batch, S, heads, dh);
-    const VarDiff P = causal ? drop.forward((Q.bmm_t(K) * scale + causal_mask(S)).softmax(2))
+    const VarDiff P = causal ? drop.forward((Q.bmm_t(K) * scale + mask_leaf(S)).softmax(2))
                       : (fused && S % 4 == 0 && S <= 2048) ? Q.bmm_t(K).attention_probs(scale, drop.p, drop.status)
                                                            : drop.forward((Q.bmm_t(K) * scale).softmax(2));
     const VarDiff O = P.bmm(V).merge_heads(batch, S, heads, dh);
@@ -3239,6 +3326,37 @@ Sampler::Sampler(DevicePtr dev_, float temperature_, int top_k_, float top_p_, u
 }
 Var Sampler::forward(const Var& logits, int batch) const { return logits.sample(*this, batch); }
 Var Sampler::forward(const VarDiff& logits, int batch) const { return logits.var.sample(*this, batch); }
+
+Segments::Segments(DevicePtr dev, int batch_, int S_, const std::vector<std::vector<int>>& doc_lens) : batch(batch_), S(S_), max_len(0) {
+    if (!dev) panic("Segments: null device");
+    check(nk_graph_refuse_capture(dev->raw(), "nn::Segments (its arrays are uploaded with a synchronising copy)"));  // before anything touches the stream
+    if (batch <= 0 || S <= 0) panic("Segments: batch and S must be positive");
+    if ((long long)batch * S > (long long)INT_MAX) panic("Segments: batch * S must fit 31 bits");
+    if ((int)doc_lens.size() != batch)
+        panic("Segments: " + std::to_string(doc_lens.size()) + " lists of document lengths for a batch of " + std::to_string(batch));
+    lo_host.assign((size_t)batch * S, 0);
+    pos_host.assign((size_t)batch * S, 0);
+    for (int b = 0; b < batch; ++b) {
+        long long t = 0;
+        auto document = [&](int n) {
+            for (int i = 0; i < n; ++i) { lo_host[(size_t)b * S + t + i] = (int)t; pos_host[(size_t)b * S + t + i] = i; }
+            t += n;
+            max_len = std::max(max_len, n);
+        };
+        for (int n : doc_lens[(size_t)b]) {
+            if (n <= 0) panic("Segments: sample " + std::to_string(b) + " has a document of length " + std::to_string(n) + " (must be positive)");
+            if (t + n > S)
+                panic("Segments: the documents of sample " + std::to_string(b) + " hold more than S = " + std::to_string(S) + " positions");
+            document(n);
+        }
+        if (t < S) document((int)(S - t));  // the padding tail: one more document
+    }
+    static_assert(sizeof(int) == sizeof(float), "the int32 arrays travel in f32 storage");
+    lo = std::make_shared<HipArray>(dev, Shape{batch, S}, HipArray::Uninit{});
+    pos = std::make_shared<HipArray>(dev, Shape{batch, S}, HipArray::Uninit{});
+    lo->upload(reinterpret_cast<const float*>(lo_host.data()));
+    pos->upload(reinterpret_cast<const float*>(pos_host.data()));
+}
 
 RotaryEmbedding::RotaryEmbedding(DevicePtr dev, int head_dim_, int max_pos_, double base_, int rot_, bool interleaved_)
     : head_dim(head_dim_), max_pos(max_pos_), rot(rot_ == 0 ? head_dim_ : rot_), base(base_), interleaved(interleaved_) {

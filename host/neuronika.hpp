@@ -260,6 +260,7 @@ class VarDiff;
 namespace nn {
 struct RotaryEmbedding;
 struct Sampler;
+struct Segments;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -405,8 +406,11 @@ class Var {
     // window > 0 (needs causal): query r attends to keys r - window < k <= r.  S <= window is the causal node as it is; S > window
     // runs nk_attention_band_* on banded scratch sized by nk_attention_band_scratch / _mask_words and allocated without a fill -
     // in a graph without gradients too (the band kernels have no inference form).
+    // segments (needs causal; batch and S must be B and S): query r attends to the keys of its own document only, max(lo[r], r -
+    // window + 1) .. r.  One document per sample (max_len >= S) is the call without segments; otherwise nk_attention_seg_* on the
+    // band's scratch at window := span = min(max_len, window), allocated without a fill, in every graph.
     Var heads_attention(const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
-                        Shared<bool> status, bool causal = false, int window = 0) const;
+                        Shared<bool> status, bool causal = false, int window = 0, const nn::Segments* segments = nullptr) const;
     static bool attention_core_supported(int S, int dh, double p);
 };
 
@@ -537,7 +541,7 @@ class VarDiff {
     VarDiff heads_context(const VarDiff& values, int B, int S, int H, int dh) const;
     VarDiff attention_probs(float scale, double p, Shared<bool> status, bool store_probs = false) const;
     VarDiff heads_attention(const VarDiff& keys, const VarDiff& values, int B, int S, int H, int dh, float scale, double p,
-                            Shared<bool> status, bool causal = false, int window = 0) const;
+                            Shared<bool> status, bool causal = false, int window = 0, const nn::Segments* segments = nullptr) const;
 };
 
 // `Add/Sub/Mul/Div` with NumPy broadcasting, all four differentiability combinations
@@ -890,6 +894,21 @@ struct RotaryEmbedding {
     Shared<HipArray> table;
 };
 
+// Packed sequences (ours; semantics at nk_attention_seg_fwd in neuronika_hip.h): several documents concatenated in one row of the
+// batch.  doc_lens holds, per sample, the positive lengths of its documents in order, with sum <= S; a remainder forms one more
+// document, the padding tail, whose targets the user masks with `CrossEntropyLoss::ignore_index`.  Holds two device arrays of
+// batch*S int32 (in f32 storage, as the decode step's start positions travel) - lo[b][t], the start of t's document inside the
+// sample, and pos[b][t] = t - lo[b][t], the position rope restarts at - their host copies, and max_len, the longest document.  Both
+// are uploaded ONCE, at construction, by a synchronising upload: construction REFUSES stream capture (a panic before anything
+// touches the stream - the capture stays valid - as nk_rope_table); the nodes built with it read nothing on the host and can be captured.  Shared between the layers of a model and the steps that use the same layout.
+// Panics: batch or S not positive, doc_lens.size() != batch, a length <= 0, a sample's sum above S.
+struct Segments {
+    Segments(DevicePtr dev, int batch, int S, const std::vector<std::vector<int>>& doc_lens);
+    int batch, S, max_len;
+    Shared<HipArray> lo, pos;
+    std::vector<int> lo_host, pos_host;
+};
+
 // The keys and values of one causal attention layer, kept on the device between the steps of incremental decoding (ours: the
 // reference has no such thing; semantics at nk_kv_cache_append / nk_attention_decode_fwd in neuronika_hip.h).  Kc, Vc are
 // (batch, heads, capacity, head_dim) - `heads` is the layer's kv_heads - head-major, allocated once and never initialised: nothing past a sample's length is read
@@ -992,6 +1011,15 @@ struct MultiheadAttention {
     // k and v must be (kv_heads * d_model / heads, d_model)
     MultiheadAttention(Linear q, Linear k, Linear v, Linear o, int heads, double p, int kv_heads = 0);
     VarDiff forward(const VarDiff& x, int batch) const;  // x: (batch*seq, d_model)
+    // Packed sequences: every token attends to its own document only - keys max(seg.lo, r - window + 1) .. r - and, with `rope`,
+    // Q and K rows are rotated at seg.pos, the position INSIDE the document (nk_rope_* with B := batch*S, T := 1, start := pos).
+    // One document per sample (seg.max_len >= S) is forward(x, batch): the same nodes, launches and bits.  Otherwise, where the
+    // fused core takes the head size, ONE node on nk_attention_qkv_seg_* (packed) or nk_attention_seg_* (strided, GQA behind
+    // `repeat_kv`) with span = min(max_len, window), on the band's scratch for that span allocated without a fill; other head
+    // sizes and fused_core = false take the node-by-node paths with the per-sample constant M_b[r][k] = 0 for lo_eff <= k <= r, -inf
+    // elsewhere (a (batch*heads, S, S) leaf).  forward_step() knows no segments.
+    // Panics: causal == false; seg.batch / seg.S differ from the call's; seg.max_len > rope->max_pos.
+    VarDiff forward(const VarDiff& x, int batch, const Segments& seg) const;
     // Incremental decoding: the causal forward, one slice of T = rows / batch positions at a time, in inference.  x holds the NEW
     // positions only, (batch*T, d_model); the result, (batch*T, d_model) without a gradient, equals rows lens[b] .. lens[b] + T - 1
     // of `forward` over each sample's whole prefix up to summation order.  ONE forward node: projections (the packed single GEMM
@@ -1007,6 +1035,7 @@ struct MultiheadAttention {
     Var forward_step(const Var& x, int batch, KvCache& cache) const;
 
    private:
+    VarDiff forward_impl(const VarDiff& x, int batch, const Segments* seg) const;
     bool still_packed() const;
     Shared<HipArray> wqkv_, bqkv_, gwqkv_, gbqkv_;  // packed storage (null when the layers were handed in)
 };

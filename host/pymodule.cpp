@@ -498,6 +498,15 @@ PYBIND11_MODULE(_tape, m) {
         .def("reset", &nn::KvCache::reset, "every length back to 0")
         .def("truncate", &nn::KvCache::truncate, py::arg("lens"),
              "Give every sample a length no longer than its current one: ragged prompts after a right-padded prefill, roll-back.");
+    py::class_<nn::Segments>(nn, "Segments")
+        .def(py::init<DevicePtr, int, int, const std::vector<std::vector<int>>&>(), py::arg("dev"), py::arg("batch"), py::arg("S"), py::arg("doc_lens"),
+             "Packed sequences: per sample the lengths of its documents (positive, sum <= S; a remainder is one more document). Holds the "
+             "device arrays lo (start of the row's document) and pos (position inside it), uploaded once, for MultiheadAttention.forward.")
+        .def_readonly("batch", &nn::Segments::batch)
+        .def_readonly("S", &nn::Segments::S)
+        .def_readonly("max_len", &nn::Segments::max_len)
+        .def("lo", [](const nn::Segments& s) { return py::array_t<int>({s.batch, s.S}, s.lo_host.data()); }, "the host copy of lo, (batch, S) int32")
+        .def("pos", [](const nn::Segments& s) { return py::array_t<int>({s.batch, s.S}, s.pos_host.data()); }, "the host copy of pos, (batch, S) int32");
     py::class_<nn::RotaryEmbedding, std::shared_ptr<nn::RotaryEmbedding>>(nn, "RotaryEmbedding")
         .def(py::init<DevicePtr, int, int, double, int, bool>(), py::arg("dev"), py::arg("head_dim"), py::arg("max_pos"), py::arg("base") = 10000.0,
              py::arg("rot") = 0, py::arg("interleaved") = false,
@@ -515,6 +524,19 @@ PYBIND11_MODULE(_tape, m) {
              "Rotate the first `rot` columns of every head of a (batch*T, heads*head_dim) value by the angles of positions 0 .. T-1.");
     py::reinterpret_borrow<py::class_<VarDiff>>(m.attr("VarDiff"))
         .def("rope", &VarDiff::rope, py::arg("rotary"), py::arg("batch"), py::arg("heads"));
+    // packed sequences: the trailing segments argument, as a second signature (the first one and its defaults stay as they are)
+    py::reinterpret_borrow<py::class_<Var>>(m.attr("Var"))
+        .def("heads_attention", [](const Var& q, const Var& k, const Var& v, int B, int S, int H, int dh, float scale, double p, const Status& s,
+                                   bool causal, int window, const nn::Segments& seg) {
+                 return q.heads_attention(k, v, B, S, H, dh, scale, p, s.flag, causal, window, &seg); },
+             py::arg("keys"), py::arg("values"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("dh"), py::arg("scale"), py::arg("p"),
+             py::arg("status"), py::arg("causal"), py::arg("window"), py::arg("segments"));
+    py::reinterpret_borrow<py::class_<VarDiff>>(m.attr("VarDiff"))
+        .def("heads_attention", [](const VarDiff& q, const VarDiff& k, const VarDiff& v, int B, int S, int H, int dh, float scale, double p,
+                                   const Status& s, bool causal, int window, const nn::Segments& seg) {
+                 return q.heads_attention(k, v, B, S, H, dh, scale, p, s.flag, causal, window, &seg); },
+             py::arg("keys"), py::arg("values"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("dh"), py::arg("scale"), py::arg("p"),
+             py::arg("status"), py::arg("causal"), py::arg("window"), py::arg("segments"));
     py::reinterpret_borrow<py::class_<Var>>(m.attr("Var"))
         .def("repeat_kv", &Var::repeat_kv, py::arg("groups"), py::arg("head_dim"),
              "Every head of a (rows, kv_heads*head_dim) value written `groups` times: (rows, kv_heads*groups*head_dim), a bit-exact copy.");
@@ -560,7 +582,10 @@ PYBIND11_MODULE(_tape, m) {
         .def_readonly("d_model", &nn::MultiheadAttention::d_model)
         .def_readonly("heads", &nn::MultiheadAttention::heads)
         .def_readonly("kv_heads", &nn::MultiheadAttention::kv_heads)
-        .def("forward", &nn::MultiheadAttention::forward)
+        .def("forward", py::overload_cast<const VarDiff&, int>(&nn::MultiheadAttention::forward, py::const_), py::arg("x"), py::arg("batch"))
+        .def("forward", py::overload_cast<const VarDiff&, int, const nn::Segments&>(&nn::MultiheadAttention::forward, py::const_), py::arg("x"),
+             py::arg("batch"), py::arg("segments"),
+             "Packed sequences: every token attends to its own document only and rope restarts at every document start.")
         .def("forward_step", &nn::MultiheadAttention::forward_step, py::arg("x"), py::arg("batch"), py::arg("cache"),
              "Incremental decoding: x holds the new positions only, (batch*T, d_model); returns (batch*T, d_model) without a gradient. "
              "The cache's lengths advance when the node is built. Needs causal = True and inactive dropout (drop.eval()).")

@@ -179,6 +179,10 @@ int nk_graph_begin(nk_device* dev);
 int nk_graph_end(nk_device* dev, nk_graph** out);
 int nk_graph_launch(nk_graph* graph);
 int nk_graph_destroy(nk_graph* graph);
+/* For host-side set-up that uploads with a synchronising copy (nn::Segments): NK_ERR_INVALID, with `what` in the message, while the
+ * compute stream is being captured - checked BEFORE anything touches the stream, so the capture stays valid, as nk_rope_table's
+ * own refusal; NK_OK otherwise.  Nothing is launched or copied. */
+int nk_graph_refuse_capture(nk_device* dev, const char* what);
 
 /* ------------------------------------------------------------------ kernel timing ------ */
 /* Bench instrumentation: between nk_profile_begin and nk_profile_end every launch of the
@@ -890,6 +894,43 @@ int nk_attention_qkv_band_fwd(nk_device* dev, const float* QKV, float* scores, f
 int nk_attention_qkv_band_bwd(nk_device* dev, float* dQKV, float* dS, float* dropped, const float* dO, const float* O,
                               const float* scores, const float* stats, const uint32_t* mask_bits, const float* QKV, int B, int S, int H,
                               int dh, float scale, double p, int train, int assign, int window);
+/* Packed sequences (document-masked causal self-attention): query row r of sample b attends to the key rows lo_eff[r] .. r with
+ *   lo_eff[r] = min(r, max(lo[b][r], r - span + 1, 0)),
+ * `lo` a device array of (B, S) int32 shared by the heads of a sample - for packed documents, the start of the row's document - and
+ * `span` the longest run lo_eff .. r any row may keep (the longest document, or min(that, window) under a sliding window).  As a
+ * composition it is the causal chain above with the per-sample constant M_b[r][k] = 0 for lo_eff[r] <= k <= r and -inf elsewhere.
+ * The clamp is the memory-safety guarantee: no content of `lo` makes the call read or write outside what the band geometry for
+ * (S, span) defines.  PRECONDITION: lo_eff never decreases with r inside a sample; with an array that breaks it the call stays
+ * memory-safe and its results are unspecified.  A padded query (r >= S inside the last tile of 32) uses the clamped row S - 1.
+ * Geometry: there are no functions of its own.  `scores`, `dS` and `dropped` hold nk_attention_band_scratch(S, span) floats per
+ * (sample, head), element (r, k) at r * nk_attention_band_ld(S, span) + k; `mask_bits` holds nk_attention_band_mask_words(S, span)
+ * words per (sample, head) in the band's layout; statistics (B*H, SP, 2); draws at (bh*SP + r)*SP + k.  The walk is the band's with
+ * window := span for what a block stages, and per wave of 32 rows r0 .. the tiles lo_eff[r0] / 32 .. r0 / 32 are computed.  Scratch
+ * contract, the band's: scores are written on the computed tiles, -inf at masked positions; the backward defines dS and Pd - exactly
+ * 0 at masked positions - on every 128 x 128 block (qb, j) with js(qb) <= j <= qb; nothing else is written or read.  dK / dV run
+ * per strip of 128 keys as the band's with window := span.  No entry point reads `lo` on the host or allocates.
+ * Bit contracts:
+ *  1. lo[b][r] = max(0, r - span + 1) for all b, r - or any array the clamp turns into that, such as every entry -7 - gives every
+ *     buffer the bits nk_attention_band_* gives with window = span; with span >= S those are the causal entry points' layouts and bits.
+ *  2. With documents (lo[b][r] = the start of r's document), a row's bits in O and dQ depend on its own document's queries, keys and
+ *     values only - on the keys / values of lo_eff[r] .. r and, through the forward's lazy softmax shift, which the 32 rows of a tile
+ *     move together, on the scores of its own document's rows; the same holds for the rows of its document in dK / dV.  They do not
+ *     depend on the finite contents of other documents: masked products are exact zeros, adding them changes no bit, and a row of
+ *     a later document asks for the shift only in the tile's diagonal tile, where it asks whatever it holds.
+ * NK_ERR_INVALID, nothing written: lo == NULL, span <= 0, and everything nk_attention_band_* refuses with window = span. */
+int nk_attention_seg_fwd(nk_device* dev, const float* Q, const float* K, const float* V, const int* lo, float* scores, float* stats,
+                         uint32_t* mask_bits, float* O, int B, int S, int H, int dh, int span, float scale, double p, int train,
+                         uint64_t seed, uint64_t offset);
+int nk_attention_seg_bwd(nk_device* dev, float* dQ, float* dK, float* dV, float* dS, float* dropped, const float* dO,
+                         const float* O, const float* scores, const float* stats, const uint32_t* mask_bits, const float* Q,
+                         const float* K, const float* V, const int* lo, int B, int S, int H, int dh, int span, float scale, double p,
+                         int train, int assign_dq, int assign_dk, int assign_dv);
+int nk_attention_qkv_seg_fwd(nk_device* dev, const float* QKV, const int* lo, float* scores, float* stats, uint32_t* mask_bits,
+                             float* O, int B, int S, int H, int dh, int span, float scale, double p, int train, uint64_t seed,
+                             uint64_t offset);
+int nk_attention_qkv_seg_bwd(nk_device* dev, float* dQKV, float* dS, float* dropped, const float* dO, const float* O,
+                             const float* scores, const float* stats, const uint32_t* mask_bits, const float* QKV, const int* lo, int B,
+                             int S, int H, int dh, int span, float scale, double p, int train, int assign);
 /* ------------------------------------------------------------------ incremental decoding --
  * The causal forward above, one slice of T positions at a time, in inference (no dropout, nothing kept for a backward pass): each
  * layer's keys and values stay on the device and the new rows attend to them.  For sample b, head h and the t-th new row

@@ -56,6 +56,7 @@ _SIGS = {
     "nk_free": [VP, VP],
     "nk_upload": [VP, VP, VP, C.c_size_t],
     "nk_graph_begin": [VP],
+    "nk_graph_refuse_capture": [VP, C.c_char_p],
     "nk_graph_end": [VP, C.POINTER(C.c_void_p)],
     "nk_graph_launch": [VP],
     "nk_graph_destroy": [VP],
@@ -220,6 +221,14 @@ _SIGS = {
                                   C.c_int],
     "nk_attention_qkv_band_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_int,
                                   C.c_int],
+    "nk_attention_seg_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64,
+                             C.c_uint64],
+    "nk_attention_seg_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                             C.c_double, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_attention_qkv_seg_fwd": [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64,
+                                 C.c_uint64],
+    "nk_attention_qkv_seg_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double,
+                                 C.c_int, C.c_int],
     "nk_attention_decode_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float],
     "nk_attention_decode_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_attention_decode_chunk": [C.c_int],
@@ -1169,6 +1178,34 @@ def attention_qkv_band_bwd(dev, dQKV, dS, dropped, dO, out, scores, stats, mask_
                            *, window):
     check(lib.nk_attention_qkv_band_bwd(dev.h, dQKV.p, dS.p, dropped.p, dO.p, out.p, scores.p, stats.p, _opt(mask_bits), QKV.p, B, S, H, dh,
                                         scale, float(p), int(train), int(assign), int(window)))
+
+
+def attention_seg_fwd(dev, Q, K, V, lo, scores, stats, mask_bits, out, B, S, H, dh, scale, p, train=True, seed=0, offset=0, *, span):
+    """Document-masked fused core: query r of sample b attends to keys lo_eff[r] .. r, lo_eff = min(r, max(lo[b][r], r - span + 1, 0)).
+    lo: (B, S) int32 device array, non-decreasing after the clamp.  The scratch is the band's at window = span: scores
+    B*H*attention_band_scratch(S, span) floats, stats (B*H,SP,2), mask_bits B*H*attention_band_mask_words(S, span) words or None."""
+    check(lib.nk_attention_seg_fwd(dev.h, Q.p, K.p, V.p, _opt(lo), _opt(scores), _opt(stats), _opt(mask_bits), out.p, B, S, H, dh, int(span),
+                                   scale, float(p), int(train), seed, offset))
+
+
+def attention_seg_bwd(dev, dQ, dK, dV, dS, dropped, dO, out, scores, stats, mask_bits, Q, K, V, lo, B, S, H, dh, scale, p, train=True,
+                      assign=(False, False, False), *, span):
+    """dS and dropped (banded scratch at window = span) are written on the 128 x 128 blocks the forward staged; dQ / dK / dV (+)=."""
+    check(lib.nk_attention_seg_bwd(dev.h, dQ.p, dK.p, dV.p, dS.p, dropped.p, dO.p, out.p, scores.p, stats.p, _opt(mask_bits), Q.p, K.p, V.p,
+                                   _opt(lo), B, S, H, dh, int(span), scale, float(p), int(train), int(assign[0]), int(assign[1]),
+                                   int(assign[2])))
+
+
+def attention_qkv_seg_fwd(dev, QKV, lo, scores, stats, mask_bits, out, B, S, H, dh, scale, p, train=True, seed=0, offset=0, *, span):
+    """attention_seg_fwd with Q, K, V as the three column blocks of ONE (B*S, 3*H*dh) array."""
+    check(lib.nk_attention_qkv_seg_fwd(dev.h, QKV.p, _opt(lo), _opt(scores), _opt(stats), _opt(mask_bits), out.p, B, S, H, dh, int(span),
+                                       scale, float(p), int(train), seed, offset))
+
+
+def attention_qkv_seg_bwd(dev, dQKV, dS, dropped, dO, out, scores, stats, mask_bits, QKV, lo, B, S, H, dh, scale, p, train=True, assign=False,
+                          *, span):
+    check(lib.nk_attention_qkv_seg_bwd(dev.h, dQKV.p, dS.p, dropped.p, dO.p, out.p, scores.p, stats.p, _opt(mask_bits), QKV.p, _opt(lo), B, S, H,
+                                       dh, int(span), scale, float(p), int(train), int(assign)))
 
 
 def chunk_fwd(dev, x, y, chunk_no):

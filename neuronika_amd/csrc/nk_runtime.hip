@@ -286,6 +286,12 @@ struct nk_graph {
     hipGraphExec_t exec;
 };
 
+int nk_graph_refuse_capture(nk_device* dev, const char* what) {
+    NK_CHECK(dev != nullptr && what != nullptr, "null pointer in nk_graph_refuse_capture");
+    NK_USE(dev);
+    return nk_refuse_capture(dev, what, "build it before the capture begins");
+}
+
 int nk_graph_begin(nk_device* dev) {
     NK_USE(dev);
     NK_HIP(hipStreamBeginCapture(dev->compute, hipStreamCaptureModeRelaxed));
