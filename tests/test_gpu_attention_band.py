@@ -13,7 +13,8 @@ Instantiations of attention_band_kernel<BWD, MASKED, OCC, DH, RAGGED> and the ca
 them (forward and backward alike; MASKED = the (0.1, True) case, unmasked = (0.0, True) and (0.35, False)):
   DH 64  whole  (2,160,2,64,7) (1,160,2,64,32) (1,256,2,64,33) (1,384,1,64,100) (1,512,1,64,129) (1,640,1,64,256)
   DH 64  ragged (2,197,2,64,40) (1,1000,1,64,130)          DH 32  whole (1,384,2,32,128)    DH 32  ragged (2,129,1,32,5)
-  DH 128 whole  (1,512,1,128,200)                          DH 128 ragged (1,300,2,128,96)"""
+  DH 128 whole  (1,512,1,128,200)                          DH 128 ragged (1,300,2,128,96)
+Non-uniform rows - the ones that move the softmax shift after a row's first finite tile: tests/test_gpu_attention_band_rows.py."""
 import numpy as np
 import pytest
 

@@ -24,7 +24,8 @@ Loop regions (block qb, wave w, tiles of 32 keys):
   whole tiles [left_end, 4 qb)  split-384 (block 2: tiles 5 .. 7 behind the edge at 130), long-1000 (blocks 5 .. 7 of the last document),
                                 three-512 (block 3: tiles 8 .. 11)
   the diagonal square           every case
-  span < longest document       window-320: lo from documents of 200 and 120 with span = 48 (the clamp adds the sliding window)"""
+  span < longest document       window-320: lo from documents of 200 and 120 with span = 48 (the clamp adds the sliding window)
+Non-uniform rows - the ones that move the softmax shift after a row's first finite tile: tests/test_gpu_attention_band_rows.py."""
 import numpy as np
 import pytest
 
