@@ -26,86 +26,9 @@
 // P = exp2(S * c1 - m2) / sum from the stored scores with those.  Against the node-by-node composition this changes the order
 // of the row sum and replaces two divisions by a reciprocal and a product - inside the f32 tolerance of SURVEY.md 8c (ii),
 // checked against the oracle, not bit-equal to the three-node path.
-#include <cmath>
-#include <cstdlib>
-
-#include "nk_mma.h"
+#include "nk_attention_core.h"
 
 namespace {
-
-using nkmma::f32x16;
-
-// Head dimension DH in {32, 64, 128} (template parameter): DH / 32 MFMA column tiles of the output, DH / 8 b128 k-groups of the
-// score product.  64 is the C5 geometry the register / LDS budgets were tuned for (three forward blocks per CU); 128 holds 64 + 64
-// VGPRs of per-query operand and output accumulators and 66 KB of staged K / V per block - one block per CU, still one kernel per
-// direction instead of the node-by-node path; 32 halves everything.
-constexpr int A_NT = 256;   // 4 waves, 32 queries each
-constexpr int A_QB = 128;   // queries per block
-constexpr int SCR_LD = 36;  // per-wave 32 x 32 transposition scratch
-// pass-1 operand image [mfma row][dh], padded by 4: b128 fragment reads of 16 rows hit 16 distinct slots
-constexpr int x1_ld(int dh) { return dh + 4; }
-// pass-2 operand image [key][dh rotated by 32 for keys >= 16]: the two lane halves read disjoint banks (DH = 32: no rotation
-// possible, the halves share banks - a two-way conflict on 16 of the tile's LDS reads)
-constexpr int x2_ld(int dh) { return dh; }
-
-struct AttnArgs {
-    const float* x1;   // pass-1 operand, flat (B*S) x (H*dh) layout: forward K, backward V
-    const float* x2;   // pass-2 operand:                               forward V, backward K
-    const float* bq;   // per-query operand:                            forward Q, backward dO
-    const float* ctx;  // backward only: the forward output O (for sum_k dP * P = keep * dO . O)
-    float* out;        // forward O, backward dQ
-    float* scores;     // (B*H, S, S) raw scores: written forward, read backward
-    float* ds;         // backward: dS
-    float* dropped;    // backward: Pd
-    unsigned* maskbits;  // (B*H, S/32 query tiles, S/32 key tiles, 32 queries) words: the dropout draws, 1 bit per score (bit 16h + e of
-                         // word [bh][qt][kt][q] = key 32 kt + 16 h + e of query 32 qt + q kept): written forward, read backward.  A wave's
-                         // 32 words of one tile are ONE 128-byte line (row-major (B*H, S, S/32) made every tile 32 scattered 4-byte stores:
-                         // 16.8 M partial-line write requests per C5 forward next to the 33.5 M of the scores)
-    float* stats;      // (B*H, S, 2): the shift m2 (log2 units; row max of s*c1 minus at most 6) and 1 / sum_k exp2(s*c1 - m2)
-    int S, H, nqb, ntile;
-    // row strides (floats) of the projection-layout operands: a (B*S, H*dh) matrix of its own has ld = H*dh; Q, K, V (and dQ,
-    // dK, dV) that are column blocks of ONE packed (B*S, 3*H*dh) projection output have ld = 3*H*dh
-    int ldx;           // x1, x2
-    int ldq;           // bq
-    int ldc;           // ctx
-    int ldo;           // out
-    float scale, keep, dscale;
-    float c1;          // scale * log2(e): exponents are taken in base 2
-    unsigned keep_lt;  // a draw v is kept iff v < keep_lt = floor((1 - p) * 2^32)  (nk_common.h: the Bernoulli construction)
-    int rev;           // causal: a head's query blocks in descending order (longest walk first); sits in the 4 bytes of padding in front of `seed`
-    unsigned long long seed, offset;
-    int assign;        // backward: dQ = (1) or += (0)
-    int SP;            // S rounded up to a multiple of 32: row count and row stride of the (B*H, SP, SP) scratch tensors (scores, dS, Pd,
-                       // statistics, mask words).  SP == S except for ragged sequence lengths (read by the RAGGED instantiations only)
-};
-
-// Wave-private LDS round trip: every lane's ds_write is issued before any lane's ds_read (LDS is in-order per wave); the
-// fences keep the compiler from reordering across the hand-over.
-__device__ __forceinline__ void wave_lds_handover() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// registers (lane = query q, half h, 16 consecutive keys 16h..16h+15) -> 32 x 32 tile of a row-major (.., S) tensor, as
-// 128-byte row segments (8 lanes x 16 B) instead of 64 scattered 16-byte pieces per store instruction.  Two halves, issued
-// far apart: the tile goes to the wave's LDS scratch as soon as it is computed, and is read back and stored to HBM after
-// the second MFMA product of the iteration - the ds_write -> ds_read round trip (a few hundred cycles, and there are only
-// two or three waves per SIMD to hide it) then runs under 32 MFMAs instead of stalling the wave.
-__device__ __forceinline__ void tile_write(float* scrw, const float (&v)[16], int lane) {
-    const int q = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        *reinterpret_cast<float4*>(&scrw[q * SCR_LD + 16 * h + 4 * c]) = make_float4(v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);
-}
-__device__ __forceinline__ void tile_flush(const float* scrw, float* g /* &T[row0][kt*32] */, int S, int lane) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = 8 * i + (lane >> 3), c = 4 * (lane & 7);
-        const float4 t = *reinterpret_cast<const float4*>(&scrw[r * SCR_LD + c]);
-        nk_store_stream(reinterpret_cast<float4*>(g + (long long)r * S + c), t);
-    }
-}
 
 // FULL: S is a multiple of 128, every wave of every block has queries.  Not a micro-optimisation: with a run-time `on`
 // the loop body sits under a branch, the compiler's wait-count bookkeeping merges the two paths at the join and waits for
@@ -130,6 +53,7 @@ __device__ __forceinline__ void tile_flush(const float* scrw, float* g /* &T[row
 // touches or lies below the diagonal (what the dK / dV products read).  Score, dS, Pd and mask-word tiles above that are neither
 // written nor read.  Dropout draws keep their positions in the padded tensor (a masked position's draw is unused).  The blocks of a
 // head are handed out longest first (p.rev): they differ in length by nqb x and the short ones fill the end of the grid.
+#define NK_ATT_LEFT false   // rows start at key 0 (nk_attention_tile.h)
 template <bool BWD, bool MASKED, bool FULL, int OCC, bool KEEP = true, int DH = 64, bool RAGGED = false, bool CAUSAL = false>
 __global__ __launch_bounds__(A_NT, OCC) void attention_kernel(const AttnArgs p) {
     static_assert(!(RAGGED && FULL), "ragged sequence lengths take the guarded instantiation");
@@ -167,37 +91,7 @@ __global__ __launch_bounds__(A_NT, OCC) void attention_kernel(const AttnArgs p) 
         s1[r] = (unsigned)((8 * ((key >> 2) & 3) + 4 * (key >> 4) + (key & 3)) * X1_LD + 4 * c4);
         s2[r] = (unsigned)(key * X2_LD + ((4 * c4 + 32 * (key >> 4)) & (DH - 1)));
     }
-    // NAMED registers (up to four float4 per operand), not arrays: `float4 st[NR]` written under `if (more)` and read a loop
-    // body later is kept in scratch memory by the compiler (measured: 64 bytes of private segment, four scratch stores and
-    // loads per tile), and so is a small array of LDS pointers.
-    float4 sa0, sa1, sa2, sa3, sb0, sb1, sb2, sb3;
-#define A_STAGE_LOAD(KT)                                                                                         \
-    do {                                                                                                         \
-        const long long t0_ = (long long)(KT) * 32 * p.ldx;                                                      \
-        const bool lt_ = RAGGED && (KT) == p.ntile - 1;   /* wave-uniform */                                     \
-        const unsigned g0_ = lt_ ? goff_last[0] : goff[0], g1_ = lt_ ? goff_last[NR > 1 ? 1 : 0] : goff[NR > 1 ? 1 : 0],         \
-                       g2_ = lt_ ? goff_last[NR > 2 ? 2 : 0] : goff[NR > 2 ? 2 : 0], g3_ = lt_ ? goff_last[NR > 2 ? 3 : 0] : goff[NR > 2 ? 3 : 0]; \
-        sa0 = *reinterpret_cast<const float4*>(x1 + t0_ + g0_);                                                 \
-        if constexpr (NR > 1) sa1 = *reinterpret_cast<const float4*>(x1 + t0_ + g1_);                           \
-        if constexpr (NR > 2) { sa2 = *reinterpret_cast<const float4*>(x1 + t0_ + g2_);                         \
-                                sa3 = *reinterpret_cast<const float4*>(x1 + t0_ + g3_); }                       \
-        sb0 = *reinterpret_cast<const float4*>(x2 + t0_ + g0_);                                                 \
-        if constexpr (NR > 1) sb1 = *reinterpret_cast<const float4*>(x2 + t0_ + g1_);                           \
-        if constexpr (NR > 2) { sb2 = *reinterpret_cast<const float4*>(x2 + t0_ + g2_);                         \
-                                sb3 = *reinterpret_cast<const float4*>(x2 + t0_ + g3_); }                       \
-        (void)g1_; (void)g2_; (void)g3_;                                                                         \
-    } while (0)
-#define A_STAGE_STORE(BUF)                                                                                       \
-    do {                                                                                                         \
-        *reinterpret_cast<float4*>(&x1s[BUF][s1[0]]) = sa0;                                                      \
-        if constexpr (NR > 1) *reinterpret_cast<float4*>(&x1s[BUF][s1[NR > 1 ? 1 : 0]]) = sa1;                   \
-        if constexpr (NR > 2) { *reinterpret_cast<float4*>(&x1s[BUF][s1[NR > 2 ? 2 : 0]]) = sa2;                 \
-                                *reinterpret_cast<float4*>(&x1s[BUF][s1[NR > 2 ? 3 : 0]]) = sa3; }               \
-        *reinterpret_cast<float4*>(&x2s[BUF][s2[0]]) = sb0;                                                      \
-        if constexpr (NR > 1) *reinterpret_cast<float4*>(&x2s[BUF][s2[NR > 1 ? 1 : 0]]) = sb1;                   \
-        if constexpr (NR > 2) { *reinterpret_cast<float4*>(&x2s[BUF][s2[NR > 2 ? 2 : 0]]) = sb2;                 \
-                                *reinterpret_cast<float4*>(&x2s[BUF][s2[NR > 2 ? 3 : 0]]) = sb3; }               \
-    } while (0)
+    float4 sa0, sa1, sa2, sa3, sb0, sb1, sb2, sb3;   // the staged tile on its way to LDS (A_STAGE_LOAD / A_STAGE_STORE)
 
     // ---- per-query state ----------------------------------------------------------------------------------------
     const int qrow = on ? q0 + q : 0;                        // row of the scratch tensors (padded rows exist there)
@@ -241,23 +135,9 @@ __global__ __launch_bounds__(A_NT, OCC) void attention_kernel(const AttnArgs p) 
     unsigned* const mwave = MASKED ? p.maskbits + (((long long)bh * (SP / 32) + (on ? q0 / 32 : 0)) * p.ntile) * 32 + q : nullptr;
     const unsigned* mload = mwave;
     const float* sload = p.scores + rowbase + (long long)(lane >> 3) * SP + 4 * (lane & 7);
-#define A_SCORES_LOAD(KT)                                                                        \
-    do {                                                                                         \
-        sn0 = *reinterpret_cast<const float4*>(sload + (KT) * 32);                               \
-        sn1 = *reinterpret_cast<const float4*>(sload + (long long)8 * SP + (KT) * 32);           \
-        sn2 = *reinterpret_cast<const float4*>(sload + (long long)16 * SP + (KT) * 32);          \
-        sn3 = *reinterpret_cast<const float4*>(sload + (long long)24 * SP + (KT) * 32);          \
-        if (MASKED) mkn = mload[(KT) * 32];                                                      \
-    } while (0)
-
-#define A_SCORES_TO_LDS()                                                                        \
-    do {                                                                                         \
-        float* sw_ = &scrw[(lane >> 3) * SCR_LD + 4 * (lane & 7)];                               \
-        *reinterpret_cast<float4*>(sw_) = sn0;                                                   \
-        *reinterpret_cast<float4*>(sw_ + 8 * SCR_LD) = sn1;                                      \
-        *reinterpret_cast<float4*>(sw_ + 16 * SCR_LD) = sn2;                                     \
-        *reinterpret_cast<float4*>(sw_ + 24 * SCR_LD) = sn3;                                     \
-    } while (0)
+    // no left edge: what the tile body and the macros name of one is constant, and unused under NK_ATT_LEFT false
+    constexpr int lo_w = 0, hi_w = -1, kt0 = 0, lo_row = 0;
+    const int sld = SP;
     A_STAGE_LOAD(0);
     if (BWD && on) A_SCORES_LOAD(0);
     A_STAGE_STORE(0);
@@ -279,10 +159,7 @@ __global__ __launch_bounds__(A_NT, OCC) void attention_kernel(const AttnArgs p) 
 #undef NK_ATT_TAIL
         }
     }
-#undef A_STAGE_LOAD
-#undef A_STAGE_STORE
-#undef A_SCORES_LOAD
-#undef A_SCORES_TO_LDS
+#undef NK_ATT_LEFT
     if (!on) return;
     // ---- epilogue: lane (query q, half h) owns dh = 32 d + 8 c + 4 h + {0..3} ----------------------------------------
     float* orow = p.out + samp * p.ldo + hoff + (long long)row * p.ldo + 4 * h;
@@ -315,18 +192,6 @@ __global__ __launch_bounds__(A_NT, OCC) void attention_kernel(const AttnArgs p) 
                     make_float4(old[d][c].x + oacc[d][4 * c], old[d][c].y + oacc[d][4 * c + 1], old[d][c].z + oacc[d][4 * c + 2],
                                 old[d][c].w + oacc[d][4 * c + 3]);
     }
-}
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-int attention_check(int B, int S, int H, int dh, double p, int train, float scale) {
-    NK_CHECK(p >= 0.0 && p <= 1.0, "Wrong probability received: %g.", p);
-    NK_CHECK(scale > 0.f && scale < 1e30f, "fused attention needs a positive finite scale (the row max is taken before scaling), got %g", (double)scale);
-    NK_CHECK(B > 0 && S > 0 && H > 0, "attention: non-positive geometry");
-    NK_CHECK(nk_attention_supported(S, dh, p, train), "fused attention needs dh in {32, 64, 128} and p < 1 in training (S=%d dh=%d p=%g)", S, dh, p);
-    NK_CHECK((long long)B * H * ((S + 31) / 32) * ((S + 31) / 32) < (1ll << 31) / 32, "attention: the mask words exceed 2^31");
-    NK_CHECK((long long)B * S * H * dh < (1ll << 31), "attention: the projection layout exceeds 2^31 elements");
-    return NK_OK;
 }
 
 template <bool BWD, int DH, bool CAUSAL>
@@ -397,11 +262,12 @@ static int attention_fwd_impl(nk_device* dev, bool causal, const float* Q, const
                               uint32_t* mask_bits, float* O, int B, int S, int H, int dh, float scale, double p, int train, uint64_t seed,
                               uint64_t offset) {
     NK_USE(dev);
-    if (int rc = attention_check(B, S, H, dh, p, train, scale)) return rc;
+    if (int rc = attention_check(B, S, H, dh, p, train, scale, (S + 31) / 32 * 32)) return rc;
     NK_CHECK(Q && K && V && O, "null pointer in nk_attention_fwd");
     NK_CHECK((scores != nullptr) == (stats != nullptr), "nk_attention_fwd: scores and stats are kept together or not at all");
     NK_CHECK(!scores || mask_bits || !(train && p != 0.0), "nk_attention_fwd: dropout is active, the mask_bits buffer is needed");
-    NK_CHECK(al16(Q) && al16(K) && al16(V) && al16(scores) && al16(O) && al16(stats), "nk_attention_fwd needs 16-byte aligned buffers");
+    NK_CHECK(attn_al16(Q) && attn_al16(K) && attn_al16(V) && attn_al16(scores) && attn_al16(O) && attn_al16(stats),
+             "nk_attention_fwd needs 16-byte aligned buffers");
     NK_CHECK((long long)B * S * ld_qkv < (1ll << 31), "attention: the packed projection layout exceeds 2^31 elements");
     nk_prof_start(dev, NK_KERNEL_ATTENTION, attention_flops(causal, B, S, H, dh));
     AttnArgs a{};
@@ -442,11 +308,11 @@ static int attention_bwd_impl(nk_device* dev, bool causal, float* dQ, float* dK,
                               const float* V, int ld_qkv, int B, int S, int H, int dh, float scale, double p, int train, int assign_dq,
                               int assign_dk, int assign_dv) {
     NK_USE(dev);
-    if (int rc = attention_check(B, S, H, dh, p, train, scale)) return rc;
+    if (int rc = attention_check(B, S, H, dh, p, train, scale, (S + 31) / 32 * 32)) return rc;
     NK_CHECK(dQ && dK && dV && dS && dropped && dO && O && scores && stats && Q && K && V, "null pointer in nk_attention_bwd");
     NK_CHECK(mask_bits || !(train && p != 0.0), "nk_attention_bwd: dropout is active, the forward's mask_bits are needed");
-    NK_CHECK(al16(dQ) && al16(dK) && al16(dV) && al16(dS) && al16(dropped) && al16(dO) && al16(O) && al16(scores) && al16(stats) &&
-                 al16(Q) && al16(K) && al16(V),
+    NK_CHECK(attn_al16(dQ) && attn_al16(dK) && attn_al16(dV) && attn_al16(dS) && attn_al16(dropped) && attn_al16(dO) && attn_al16(O) &&
+                 attn_al16(scores) && attn_al16(stats) && attn_al16(Q) && attn_al16(K) && attn_al16(V),
              "nk_attention_bwd needs 16-byte aligned buffers");
     NK_CHECK((long long)B * S * ld_qkv < (1ll << 31), "attention: the packed projection layout exceeds 2^31 elements");
     nk_prof_start(dev, NK_KERNEL_ATTENTION, attention_flops(causal, B, S, H, dh));
@@ -462,21 +328,9 @@ static int attention_bwd_impl(nk_device* dev, bool causal, float* dQ, float* dK,
     // 128 x 32 tiles are single 16 KB runs for these products - was built and measured: kernel and products unchanged.)
     const int d = H * dh, SP = (S + 31) / 32 * 32;  // row stride of the scratch tensors (== S unless S is ragged)
     const long long so = (long long)S * d, sq = (long long)S * ld_qkv, po = (long long)H * SP * SP, pi = (long long)SP * SP;
-    // Causal: dS and Pd are defined on the 128 x 128 blocks that touch or lie below the diagonal and UNDEFINED above (the kernel never
-    // visits those tiles; garbage times zero is NaN), so the key strip [128 j, 128 j + 128) reduces over the queries >= 128 j only: one
-    // pair of products per strip with A, B and C advanced to (128 j, 128 j) and K = S - 128 j.  S / 128 launches of B*H (pairs of)
-    // blocks; the chained-launch rule for reductions longer than 2048 products is nk_sgemm's own and applies per strip.
-    if (causal) {
-        for (int j0 = 0; j0 < S; j0 += A_QB) {
-            const int m = S - j0 < A_QB ? S - j0 : A_QB, k = S - j0;
-            const long long da = (long long)j0 * SP + j0, dq = (long long)j0 * ld_qkv, dd = (long long)j0 * d;
-            rc = nk_sgemm_pair_batched(dev, B, H, 1, 0, m, dh, k, dS + da, SP, po, pi, Q + dq, ld_qkv, sq, dh, assign_dk ? 0.f : 1.f, dK + dq,
-                                       ld_qkv, sq, dh, 1, 0, m, dh, k, dropped + da, SP, po, pi, dO + dd, d, so, dh, assign_dv ? 0.f : 1.f,
-                                       dV + dq, ld_qkv, sq, dh);
-            if (rc) return rc;
-        }
-        return NK_OK;
-    }
+    // Causal: dS and Pd are defined on the 128 x 128 blocks that touch or lie below the diagonal and UNDEFINED above, so the key strip
+    // [128 j, 128 j + 128) reduces over the queries >= 128 j only: K = S - 128 j
+    if (causal) return strip_products(dev, dK, dV, dS, dropped, dO, Q, ld_qkv, B, S, H, dh, assign_dk, assign_dv, SP, pi, a.nqb);
     // (one launch for both when nk_sgemm_pair's rule says so: the two grids share their last wave of resident blocks)
     return nk_sgemm_pair_batched(dev, B, H, 1, 0, S, dh, S, dS, SP, po, pi, Q, ld_qkv, sq, dh, assign_dk ? 0.f : 1.f, dK, ld_qkv, sq, dh,
                                  1, 0, S, dh, S, dropped, SP, po, pi, dO, d, so, dh, assign_dv ? 0.f : 1.f, dV, ld_qkv, sq, dh);

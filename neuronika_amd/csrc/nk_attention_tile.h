@@ -1,16 +1,25 @@
-// One key tile of attention_kernel's walk: the loop body, textually shared by the loop over the whole tiles and (causal
-// instantiations) the loop over the block's diagonal tiles - nk_attention.hip includes this file inside both, as nk_gemm.hip does
-// with nk_gemm_body.h and for the same reason: the non-causal kernels must stay the SAME source the compiler saw before the causal
-// walk existed (the body as a force-inlined generic lambda moved every instantiation's register allocation and instruction count).
+// One key tile of the walk of attention_kernel (nk_attention.hip) and attention_band_kernel (nk_attention_band.h): the loop body, included
+// inside every loop of both kernels, as nk_gemm.hip does with nk_gemm_body.h and for the same reason: a body under a run-time branch
+// makes the compiler wait for every outstanding vector memory operation at the join, so the tiles that are whole for all four waves get
+// a copy without any predicate - and the body as a force-inlined generic lambda moved every instantiation's register allocation and
+// instruction count.  Not a stand-alone header.  The including loop sets
 //   NK_ATT_TAIL   false: the tile is whole for every wave of the block that has queries (the body under `on` alone)
-//                 true:  one of the last four tiles of a causal block - per-wave predicate kt <= dk, element mask when kt == dk,
-//                        zero tiles of dS / Pd beyond (see CAUSAL in nk_attention.hip)
-// In scope: everything attention_kernel declares above its loop, and the loop variable `kt`.  Not a stand-alone header.
+//                 true:  an edge tile - of a causal block's diagonal square (see CAUSAL in nk_attention.hip) or of a band block's left edge
+//                        (nk_attention_band.h) - per-wave predicate, element masks, zero tiles of dS / Pd where the wave computes nothing
+//   NK_ATT_LEFT   false: rows start at key 0 (nk_attention.hip).  Predicate kt <= dk, element mask k > r when kt == dk.  The left-edge
+//                        names below are declared all the same and never read: a `kt >= 0` the compiler cannot prove costs a compare
+//                 true:  rows have a left edge.  Predicate lo_w <= kt <= dk, element mask k < lo_row where kt <= hi_w as well
+// and has in scope everything the kernel declares above its loops, the loop variable `kt`, and
+//   lo_w, hi_w    this wave's first tile, and its last tile that holds a key left of some row's edge (-1: none)
+//   lo_row        this lane's row's first key
+//   kt0           the first key tile the block stages: the mask words of a query tile are counted from it
+//   sld           row stride of scores, dS and Pd
+//   KEEP          (forward) scores, row statistics and dropout bits are written for a backward pass
         const int cur = kt & 1;
         const bool more = kt + 1 < nt;
         if (more) A_STAGE_LOAD(kt + 1);
         const bool next = NK_ATT_TAIL ? kt < dk : more;   // this wave computes tile kt + 1 (main part: every tile up to the diagonal exists)
-        if (NK_ATT_TAIL ? on && kt <= dk : on) {
+        if (NK_ATT_TAIL ? on && (!NK_ATT_LEFT || kt >= lo_w) && kt <= dk : on) {
             float sv[16];
             unsigned mybits = 0;
             if (BWD) {  // score tile (put into the scratch at the end of the previous iteration) -> lane layout; fetch the next one
@@ -61,7 +70,7 @@
                     }
                 }
                 const unsigned other = (unsigned)__shfl_xor((int)bits, 32, 64);
-                if (KEEP && h == 0) mwave[kt * 32] = bits | (other << 16);
+                if (KEEP && h == 0) mwave[(kt - kt0) * 32] = bits | (other << 16);
             }
             if (MASKED && BWD) {
 #pragma unroll
@@ -77,7 +86,16 @@
 #pragma unroll
                     for (int e = 0; e < 16; ++e) raw[e] = e < nvalid ? raw[e] : -INFINITY;
                 }
-                if (NK_ATT_TAIL && kt == dk) {  // the diagonal tile: keys above the query (every row keeps its diagonal, no row is empty)
+                if (NK_ATT_LEFT) {
+                    if (NK_ATT_TAIL && (kt <= hi_w || kt == dk)) {  // (wave-uniform) an edge of the band crosses this tile
+                        // key 32 kt + 16 h + e is kept iff lo_row <= key <= qrow: e in (elo, ehi].  The left bound is the CLAMPED row's, so a
+                        // padded query stays a copy of row S - 1 and no row is empty; every row keeps its diagonal
+                        const int elo = kt <= hi_w ? lo_row - 1 - 32 * kt - 16 * h : -1;
+                        const int ehi = kt == dk ? q - 16 * h : 15;
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) raw[e] = (e > elo && e <= ehi) ? raw[e] : -INFINITY;
+                    }
+                } else if (NK_ATT_TAIL && kt == dk) {  // the diagonal tile: keys above the query (every row keeps its diagonal, no row is empty)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) raw[e] = 16 * h + e <= q ? raw[e] : -INFINITY;
                 }
@@ -149,16 +167,16 @@
             __builtin_amdgcn_sched_barrier(0);
             wave_lds_handover();
             if (!BWD) {
-                if (KEEP) tile_flush(scrw, p.scores + rowbase + kt * 32, SP, lane);
+                if (KEEP) tile_flush(scrw, p.scores + rowbase + kt * 32, sld, lane);
             } else {
-                tile_flush(scrw, p.ds + rowbase + kt * 32, SP, lane);
-                tile_flush(scrb, p.dropped + rowbase + kt * 32, SP, lane);
+                tile_flush(scrw, p.ds + rowbase + kt * 32, sld, lane);
+                tile_flush(scrb, p.dropped + rowbase + kt * 32, sld, lane);
                 if (next) { wave_lds_handover(); A_SCORES_TO_LDS(); }   // next tile's scores (loaded during this iteration)
             }
-        } else if (NK_ATT_TAIL && BWD && on) {   // above this wave's diagonal, inside the block's 128 x 128 diagonal square: dS = Pd = 0
+        } else if (NK_ATT_TAIL && BWD && on) {   // staged by the block, left of this wave's first tile or right of its diagonal: dS = Pd = 0
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const long long o = rowbase + kt * 32 + (long long)(8 * i + (lane >> 3)) * SP + 4 * (lane & 7);
+                const long long o = rowbase + kt * 32 + (long long)(8 * i + (lane >> 3)) * sld + 4 * (lane & 7);
                 nk_store_stream(reinterpret_cast<float4*>(p.ds + o), make_float4(0.f, 0.f, 0.f, 0.f));
                 nk_store_stream(reinterpret_cast<float4*>(p.dropped + o), make_float4(0.f, 0.f, 0.f, 0.f));
             }

@@ -16,7 +16,6 @@
 #include "nk_attention_gqa.h"
 #include "nk_attention_window.h"
 #include "nk_attention_band.h"
-#include "nk_attention_seg.h"
 #include "nk_repeat_kv.h"
 #include "nk_rope.h"
 #include "nk_sampling.h"

@@ -1,5 +1,5 @@
-"""tests/attention_rows.py's score rows under a MOVING LEFT EDGE: the sliding-window kernels (nk_attention_band.h, tile body
-nk_attention_band_tile.h) and the packed-sequence kernels (nk_attention_seg.h, nk_attention_seg_tile.h) carry their own compiled
+"""tests/attention_rows.py's score rows under a MOVING LEFT EDGE: the sliding-window and the packed-sequence kernels (the two forms
+of nk_attention_band.h's attention_band_kernel, tile body nk_attention_tile.h) carry their own compiled
 copies of the online-softmax tile body, each included twice (edge tiles, whole tiles), and every other test of them draws q and k from
 uniform [-1, 1): the lazy shift then moves in a row's first finite tile only, where the running sum and the accumulator are 0.
 
@@ -211,7 +211,7 @@ def settled_max(sc2, le):
 
 def walk(S, lo, span):
     """(act, cls), each (B, SP / 32 waves, SP / 32 tiles): the tiles a wave computes, lo_w .. dk inside its block's staged range
-    [kt0, nt), and each one's class (index into CLASSES, -1 where not computed) by `left_end` as attention_seg_kernel computes it."""
+    [kt0, nt), and each one's class (index into CLASSES, -1 where not computed) by `left_end` as attention_band_kernel<..., SEG = true> computes it."""
     le = SO.lo_eff(lo, span)
     B = le.shape[0]
     ntile = (S + 31) // 32

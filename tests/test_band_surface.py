@@ -154,9 +154,15 @@ def test_kernels_live_in_their_own_header_outside_the_inventoried_units():
     assert includers == ["nk_norm.hip"] and includers[0] in [u for u, _ in dispatch_paths_mfma.NOT_INVENTORIED]
     for u in dispatch_paths.UNITS + dispatch_paths_mfma.UNITS:
         assert "attention_band_kernel" not in luk.source_kernels(u), u
-    src = re.sub(r"//[^\n]*", "", open(os.path.join(luk.CSRC, header)).read())
-    assert not re.search(r"atomic(Add|Max|Min|CAS|Exch)|__hip_atomic|__atomic_(fetch|load|store)", src)   # (fences only)
-    assert "hipMalloc" not in src and "hipMemset" not in src and "Synchronize" not in src
+    # the helpers and the tile body it shares with nk_attention.hip define no kernel
+    shared = ("nk_attention_core.h", "nk_attention_tile.h")
+    for name in shared:
+        assert luk.file_kernels(os.path.join(luk.CSRC, name)) == set(), name
+    assert "nk_attention_core.h" in luk.unit_sources("nk_norm.hip") and "nk_attention_core.h" in luk.unit_sources("nk_attention.hip")
+    for name in (header,) + shared:
+        src = re.sub(r"//[^\n]*", "", open(os.path.join(luk.CSRC, name)).read())
+        assert not re.search(r"atomic(Add|Max|Min|CAS|Exch)|__hip_atomic|__atomic_(fetch|load|store)", src), name   # (fences only)
+        assert "hipMalloc" not in src and "hipMemset" not in src and "Synchronize" not in src, name
 
 
 def test_tape_and_rust_take_the_window():

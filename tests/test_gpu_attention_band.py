@@ -9,7 +9,7 @@ Scratch contract checked here (include/neuronika_hip.h): element (r, k) of score
 nk_attention_band_scratch floats; scores are written on the tiles a wave computes (-inf at masked positions), dS and Pd are defined
 - exactly 0 at masked positions - on the 128 x 128 blocks a block of queries staged, everything else keeps the sentinel.
 
-Instantiations of attention_band_kernel<BWD, MASKED, OCC, DH, RAGGED> and the case of test_band_core_equals_oracle that reaches
+Instantiations of attention_band_kernel<BWD, MASKED, OCC, DH, RAGGED, SEG = false> and the case of test_band_core_equals_oracle that reaches
 them (forward and backward alike; MASKED = the (0.1, True) case, unmasked = (0.0, True) and (0.35, False)):
   DH 64  whole  (2,160,2,64,7) (1,160,2,64,32) (1,256,2,64,33) (1,384,1,64,100) (1,512,1,64,129) (1,640,1,64,256)
   DH 64  ragged (2,197,2,64,40) (1,1000,1,64,130)          DH 32  whole (1,384,2,32,128)    DH 32  ragged (2,129,1,32,5)

@@ -2,7 +2,7 @@
 on score rows that MOVE the online softmax's lazy shift after a row's first finite tile (tests/attention_band_rows.py: kinds,
 geometries, the exact-score grid), against tests/segment_oracle.py's composition, through the C ABI.  tests/test_gpu_attention_band.py,
 tests/test_gpu_attention_seg.py and the tape tests draw q and k from uniform [-1, 1): in these kernels' own compiled copies of the tile
-body (nk_attention_band_tile.h, nk_attention_seg_tile.h, each included for edge tiles and for whole tiles) the rescale of the running
+body (nk_attention_tile.h, included by attention_band_kernel for edge tiles and for whole tiles) the rescale of the running
 sum and of the out accumulator then only ever multiplied zeros.  tests/test_gpu_attention_rows.py covers the causal copy alone.
 
 Tolerance: the rule of tests/test_gpu_attention.py, unchanged - kernels and f32 oracle both measured against the f64 oracle fed the
@@ -16,7 +16,7 @@ units) must end with a stored shift above that tile's maximum (attention_band_ro
 attention_band_rows.settled_max - under a moving left edge a wave's rows start in different tiles, every start moves the whole wave,
 and a `plain` row does NOT end at its own first tile's maximum (the CPU file measures that on the replay).
 
-Instantiations.  attention_band_kernel / attention_seg_kernel <BWD, MASKED, OCC, DH, RAGGED>: 2 x 2 x 3 x 2 = 24 each (OCC follows).
+Instantiations.  attention_band_kernel<BWD, MASKED, OCC, DH, RAGGED, SEG>, SEG = false / true: 2 x 2 x 3 x 2 = 24 each (OCC follows).
 test_band_rows_equal_oracle[kind-geometry-p] and test_seg_rows_equal_oracle[kind-geometry-p] run forward (BWD = false) and backward
 (BWD = true) of every kind, so of `climbing`, `mixed` and (W, span >= 64) `peaked_in`, at p = 0.0 (MASKED = false) and p = 0.2 (MASKED =
 true) on every geometry:
@@ -26,7 +26,7 @@ true) on every geometry:
   seg   DH 64 whole   1x256x2x64-d40.216 1x320x1x64-d200.120-s48       DH 64 ragged   2x197x2x64-d40.40.117_5.100.92
         DH 32 whole   1x384x2x32-d170.214                              DH 32 ragged   2x129x1x32-d5.124_64.65
         DH 128 whole  1x256x1x128-d96.160                              DH 128 ragged  1x300x2x128-d96.96.108
-e.g. attention_seg_kernel<true, true, 1, 128, true> is test_seg_rows_equal_oracle[climbing-1x300x2x128-d96.96.108-0.2].  Which tile
+e.g. attention_band_kernel<true, true, 1, 128, true, true> is test_seg_rows_equal_oracle[climbing-1x300x2x128-d96.96.108-0.2].  Which tile
 class (left-edge, whole, diagonal square) the moves of each geometry fall into: tests/test_oracle_attention_band_rows.py.
 
 Worst err_gpu / bound per label on an MI355X (`vs_stated_policy` of the margins file), kinds in the order plain, climbing, falling,
@@ -265,7 +265,7 @@ def test_a_document_of_moving_rows_does_not_see_its_neighbours(dev, geometry, ke
     it shares with its neighbours (rows 40 .. 79, 105 .. 196, 5 .. 128, 170 .. 383; 96 .. 191, the dh = 128 case, lies on tile edges).  Every OTHER document is switched between
     the two `handover` orientations - the rest of a shared wave tens of nats above the kept rows, then tens of nats below - and
     then to finite values of magnitude up to 1e3: out, dq, dk, dv AND the stored statistics of the kept rows are bit-identical.  (For the
-    rows of a later document in a straddling wave that is nk_attention_seg.h's claim: they ask unconditionally in the diagonal tile.)"""
+    rows of a later document in a straddling wave that is nk_attention_band.h's claim: they ask unconditionally in the diagonal tile.)"""
     B, S, H, dh, lo, span = BR.edges(geometry)
     zero = np.zeros((B * S, H * dh), np.float32)
     runs, inputs = [], []

@@ -10,7 +10,7 @@ dropped at r * nk_attention_band_ld(S, span) + k of its head's nk_attention_band
 a wave computes (lo_eff[r0] / 32 .. r0 / 32, -inf at masked positions), dS and Pd defined - exactly 0 at masked positions - on the
 128 x 128 blocks a block of queries staged, everything else keeps the sentinel.
 
-Instantiations of attention_seg_kernel<BWD, MASKED, OCC, DH, RAGGED> and the case of test_seg_core_equals_oracle that reaches them
+Instantiations of attention_band_kernel<BWD, MASKED, OCC, DH, RAGGED, SEG = true> and the case of test_seg_core_equals_oracle that reaches them
 (forward and backward alike; MASKED = the (0.1, True) case, unmasked = (0.0, True) and (0.35, False)), ids `p-train-case`:
   DH 64  whole  mixed-160 two-128-256 ones-384 window-320        DH 64  ragged three-197 long-1000
   DH 32  whole  split-384                                       DH 32  ragged small-129

@@ -199,7 +199,7 @@ STRADDLING = [g_ for g_ in BR.SEG if BR.later_rows(*BR.edges(g_)[4:]).any()]
 
 @pytest.mark.parametrize("geometry", STRADDLING, ids=BR.gid)
 def test_later_rows_ask_in_the_diagonal_tile_whatever_their_neighbours_hold(geometry):
-    """nk_attention_seg.h: "a row of a LATER document of the same wave has all its keys in the wave's diagonal tile, where it asks
+    """nk_attention_band.h: "a row of a LATER document of the same wave has all its keys in the wave's diagonal tile, where it asks
     unconditionally (its first finite tile), so what it holds changes no decision".  On `handover`, in both orientations - the earlier
     rows of the wave tens of nats above, and tens of nats below - the replayed shift of every such row is f32(row maximum * c1), the
     value of one unconditional move from -1e30; and with a later document held fixed (`climbing`) while every other document switches

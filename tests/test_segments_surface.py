@@ -80,13 +80,17 @@ def test_kernels_live_in_their_own_header_outside_the_inventoried_units():
     import dispatch_paths
     import dispatch_paths_mfma
     import list_unit_kernels as luk
-    header = "nk_attention_seg.h"
-    assert luk.file_kernels(os.path.join(luk.CSRC, header)) == {"attention_seg_kernel"}
+    header = "nk_attention_band.h"   # the packed-sequence form is attention_band_kernel<..., SEG = true>: one kernel, one header
+    assert luk.file_kernels(os.path.join(luk.CSRC, header)) == {"attention_band_kernel"}
+    assert re.search(r"template <[^>]*\bbool SEG>\s*__global__[^\n]*\battention_band_kernel\(", open(os.path.join(luk.CSRC, header)).read())
     includers = [u for u in luk.all_units() if header in luk.unit_sources(u)]
     assert includers == ["nk_norm.hip"] and includers[0] in [u for u, _ in dispatch_paths_mfma.NOT_INVENTORIED]
     for u in dispatch_paths.UNITS + dispatch_paths_mfma.UNITS:
-        assert "attention_seg_kernel" not in luk.source_kernels(u), u
-    for name in (header, "nk_attention_seg_tile.h"):
+        assert "attention_band_kernel" not in luk.source_kernels(u), u
+    shared = ("nk_attention_core.h", "nk_attention_tile.h")
+    for name in shared:
+        assert luk.file_kernels(os.path.join(luk.CSRC, name)) == set(), name
+    for name in (header,) + shared:
         src = re.sub(r"//[^\n]*", "", open(os.path.join(luk.CSRC, name)).read())
         assert not re.search(r"atomic(Add|Max|Min|CAS|Exch)|__hip_atomic|__atomic_(fetch|load|store)", src)   # (fences only)
         # no host read of `lo`, no allocation, no synchronisation: the node can be captured
