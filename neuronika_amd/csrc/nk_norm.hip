@@ -13,8 +13,6 @@
 #include "nk_activation.h"
 #include "nk_optim_multi.h"
 #include "nk_attention_decode.h"
-#include "nk_attention_gqa.h"
-#include "nk_attention_window.h"
 #include "nk_attention_band.h"
 #include "nk_repeat_kv.h"
 #include "nk_rope.h"

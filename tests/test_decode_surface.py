@@ -71,24 +71,43 @@ def test_host_classes_exist():
     assert "void truncate(const std::vector<int>& lens);" in hpp
 
 
+DECODE_HEADER = "nk_attention_decode.h"
+DECODE_BODIES = ("nk_attention_decode_body.h", "nk_attention_decode_generic_body.h", "nk_attention_decode_combine_body.h")
+DECODE_KERNELS = {"kv_append_kernel", "kv_append_ring_kernel", "adec_partial_kernel", "adec_gqa_partial_kernel", "adw_partial_kernel",
+                  "adec_generic_kernel", "adec_gqa_generic_kernel", "adw_generic_kernel", "adec_combine_kernel", "adw_combine_kernel"}
+
+
 def test_kernels_live_in_their_own_header_outside_the_inventoried_units():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import dispatch_paths
     import dispatch_paths_mfma
     import list_unit_kernels as luk
-    header = os.path.join(luk.CSRC, "nk_attention_decode.h")
-    mine = luk.file_kernels(header)
-    assert {"kv_append_kernel", "adec_partial_kernel", "adec_generic_kernel", "adec_combine_kernel"} <= mine
-    includers = [u for u in luk.all_units() if "nk_attention_decode.h" in luk.unit_sources(u)]
-    assert len(includers) == 1 and includers[0] in [u for u, _ in dispatch_paths_mfma.NOT_INVENTORIED]
+    # one header holds every kernel signature of the three decode forms; the bodies they include hold no kernel of their own
+    mine = luk.file_kernels(os.path.join(luk.CSRC, DECODE_HEADER))
+    assert mine == DECODE_KERNELS
+    for body in DECODE_BODIES:
+        assert luk.file_kernels(os.path.join(luk.CSRC, body)) == set(), body
+    assert not os.path.exists(os.path.join(luk.CSRC, "nk_attention_gqa.h")) and not os.path.exists(os.path.join(luk.CSRC, "nk_attention_window.h"))
+    norm = _read("neuronika_amd", "csrc", "nk_norm.hip")
+    for f in (DECODE_HEADER,) + DECODE_BODIES:
+        includers = [u for u in luk.all_units() if f in luk.unit_sources(u)]     # a body included inside a kernel is found too
+        assert includers == ["nk_norm.hip"] and includers[0] in [u for u, _ in dispatch_paths_mfma.NOT_INVENTORIED], f
+        assert norm.count('#include "%s"' % f) == (1 if f == DECODE_HEADER else 0), f
+    assert mine <= luk.source_kernels("nk_norm.hip")
     for u in dispatch_paths.UNITS + dispatch_paths_mfma.UNITS:
         assert not (mine & luk.source_kernels(u)), u
-    src = re.sub(r"//[^\n]*", "", open(header).read())
-    assert "atomic" not in src.lower()                                   # partials are merged in chunk order
+    assert not [f for f in os.listdir(luk.CSRC) if f.endswith(".hip") and "decode" in f]       # no translation unit of its own
+    for f in (DECODE_HEADER,) + DECODE_BODIES:
+        src = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", f))
+        assert "atomic" not in src.lower(), f                            # partials are merged in chunk order
+        assert "num_cus" not in src and "tune_" not in src and "hipMalloc" not in src and "Synchronize" not in src, f
     # the chunk is a compile-time constant per head size: nothing of the device handle reaches it
-    body = src[src.index("constexpr int adec_chunk_of"):]
-    assert "num_cus" not in src and "tune_" not in src and "constexpr int adec_chunk_of(int dh)" in body
+    src = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", DECODE_HEADER))
+    fn = src[src.index("constexpr int adec_chunk_of"):]
+    fn = fn[:fn.index("}") + 1]
+    assert fn.startswith("constexpr int adec_chunk_of(int dh) {") and not (set(re.findall(r"[A-Za-z_]\w*", fn)) - {
+        "constexpr", "int", "adec_chunk_of", "dh", "return", "ADEC_THREADS", "ADEC_KPG", "ADEC_CHUNK_GENERIC"}), fn
 
 
 def test_rust_mirror_names_the_ffi_calls():

@@ -81,17 +81,24 @@ def test_host_classes_exist():
     assert step.index("rope_inplace(") < step.index("nk_kv_cache_append(") < step.index("nk_attention_decode_gqa_fwd(")
 
 
+def _kernel_text(src, name):
+    """a kernel's own text in the decode header: from its `__global__` to the closing brace in column 0"""
+    at = src.index(name + "(")
+    start = src.rindex("__global__", 0, at)
+    return src[start:src.index("\n}\n", at) + 1]
+
+
 def test_kernels_live_in_their_own_headers_outside_the_inventoried_units():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import dispatch_paths
     import dispatch_paths_mfma
     import list_unit_kernels as luk
-    mine = set()
-    for header, kernels in (("nk_attention_gqa.h", {"adec_gqa_partial_kernel", "adec_gqa_generic_kernel"}), ("nk_repeat_kv.h", {"repeat_kv_kernel"})):
+    mine = {"adec_gqa_partial_kernel", "adec_gqa_generic_kernel", "repeat_kv_kernel"}
+    assert mine - {"repeat_kv_kernel"} <= luk.file_kernels(os.path.join(luk.CSRC, "nk_attention_decode.h"))
+    assert luk.file_kernels(os.path.join(luk.CSRC, "nk_repeat_kv.h")) == {"repeat_kv_kernel"}
+    for header in ("nk_attention_decode.h", "nk_repeat_kv.h"):
         path = os.path.join(luk.CSRC, header)
-        assert luk.file_kernels(path) == kernels, header
-        mine |= kernels
         includers = [u for u in luk.all_units() if header in luk.unit_sources(u)]
         assert includers == ["nk_norm.hip"] and includers[0] in [u for u, _ in dispatch_paths_mfma.NOT_INVENTORIED], header
         assert _read("neuronika_amd", "csrc", "nk_norm.hip").count('#include "%s"' % header) == 1
@@ -103,11 +110,30 @@ def test_kernels_live_in_their_own_headers_outside_the_inventoried_units():
     assert not [f for f in os.listdir(luk.CSRC) if f.endswith(".hip") and ("gqa" in f or "repeat" in f)]   # no new translation unit
     rkv = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", "nk_repeat_kv.h"))
     assert "__shared__" not in rkv and "__syncthreads" not in rkv and "float4" in rkv and "nk_stream_grid" in rkv
-    gqa = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", "nk_attention_gqa.h"))
-    assert "constexpr int ADEC_GQA_HEADS = 8;" in gqa and "adec_combine_kernel" in gqa and "adec_chunk_of(" in gqa
-    # the existing decode kernels are not edited: the grouped header only includes theirs
-    dec = _read("neuronika_amd", "csrc", "nk_attention_decode.h")
-    assert "gqa" not in dec.lower() and "Hkv" not in dec
+    dec = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", "nk_attention_decode.h"))
+    assert "constexpr int ADEC_GQA_HEADS = 8;" in dec and "adec_combine_kernel" in dec and "adec_chunk_of(" in dec
+    # the grouped result is the plain result by construction: the arithmetic is stated once, in the bodies the kernels include, and in
+    # no kernel's own text
+    body = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", "nk_attention_decode_body.h"))
+    generic = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", "nk_attention_decode_generic_body.h"))
+    combine = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", "nk_attention_decode_combine_body.h"))
+    for txt in (body, generic):
+        assert txt.count("? __builtin_amdgcn_exp2f(") == 1 and txt.count("__builtin_amdgcn_exp2f") == 1       # the select of a probability
+        assert txt.count("for (int k = 1; k < G; ++k)") == 1                                                    # the groups in order
+        assert "__global__" not in txt and "#pragma once" not in txt
+    assert body.count("__shfl_xor(") == 1 and body.count("nk_wave_max(") == 1 and body.count("o / ls") == 1
+    assert combine.count("__builtin_amdgcn_exp2f") == 1 and "__global__" not in combine
+    for word in ("__builtin_amdgcn_exp2f", "__builtin_fmaf", "__shfl_xor", "fmaxf", "for (int k = 1;"):
+        assert word not in dec, word
+    for kernel, inc in (("adec_partial_kernel", "nk_attention_decode_body.h"), ("adec_gqa_partial_kernel", "nk_attention_decode_body.h"),
+                        ("adec_generic_kernel", "nk_attention_decode_generic_body.h"),
+                        ("adec_gqa_generic_kernel", "nk_attention_decode_generic_body.h")):
+        own = _kernel_text(dec, kernel)
+        assert own.count("#include") == 1 and '#include "%s"' % inc in own, kernel
+        assert not re.search(r"\b(for|if|return)\b", own), kernel                   # switches and the include, no statement of its own
+    assert "#define ADEC_GROUPED 0" in _kernel_text(dec, "adec_partial_kernel") and "#define ADEC_NH 1" in _kernel_text(dec, "adec_partial_kernel")
+    assert "#define ADEC_GROUPED 1" in _kernel_text(dec, "adec_gqa_partial_kernel")
+    assert "#define ADEC_NH ADEC_GQA_HEADS" in _kernel_text(dec, "adec_gqa_partial_kernel")
 
 
 def test_rust_mirror_names_the_ffi_calls():

@@ -104,16 +104,25 @@ def test_host_classes_exist():
         assert msg in fs, msg
 
 
+def _kernel_text(src, name):
+    """a kernel's own text in the decode header: from its `__global__` to the closing brace in column 0"""
+    at = src.index(name + "(")
+    start = src.rindex("__global__", 0, at)
+    return src[start:src.index("\n}\n", at) + 1]
+
+
 def test_kernels_live_in_their_own_header_outside_the_inventoried_units():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import dispatch_paths
     import dispatch_paths_mfma
     import list_unit_kernels as luk
-    header = "nk_attention_window.h"
+    header = "nk_attention_decode.h"
+    bodies = {"partial": "nk_attention_decode_body.h", "generic": "nk_attention_decode_generic_body.h",
+              "combine": "nk_attention_decode_combine_body.h"}
     mine = {"adw_partial_kernel", "adw_generic_kernel", "adw_combine_kernel", "kv_append_ring_kernel"}
     path = os.path.join(luk.CSRC, header)
-    assert luk.file_kernels(path) == mine
+    assert mine <= luk.file_kernels(path) and len(luk.file_kernels(path)) == 10
     includers = [u for u in luk.all_units() if header in luk.unit_sources(u)]
     assert includers == ["nk_norm.hip"] and includers[0] in [u for u, _ in dispatch_paths_mfma.NOT_INVENTORIED]
     assert _read("neuronika_amd", "csrc", "nk_norm.hip").count('#include "%s"' % header) == 1
@@ -121,17 +130,37 @@ def test_kernels_live_in_their_own_header_outside_the_inventoried_units():
         assert not (mine & luk.source_kernels(u)), u
     assert not [f for f in os.listdir(luk.CSRC) if f.endswith(".hip") and "window" in f]       # no new translation unit
     src = re.sub(r"//[^\n]*", "", open(path).read())
-    assert "atomic" not in src.lower() and "num_cus" not in src and "tune_" not in src
-    assert "hipMalloc" not in src and "Synchronize" not in src
+    for f in (header,) + tuple(bodies.values()):
+        txt = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", f))
+        assert "atomic" not in txt.lower() and "num_cus" not in txt and "tune_" not in txt, f
+        assert "hipMalloc" not in txt and "Synchronize" not in txt, f
     assert "float4" in src and "adec_chunk_of(" in src and "ADEC_GQA_HEADS" in src and "adw_chunks_of(" in src
-    for inst in ("adw_partial_kernel<DH, 1>", "adw_partial_kernel<DH, ADEC_GQA_HEADS>", "kv_append_ring_kernel<float4>", "kv_append_ring_kernel<float>"):
+    for inst in ("adw_partial_kernel<DH, 1>", "adw_partial_kernel<DH, ADEC_GQA_HEADS>", "kv_append_ring_kernel<float4>", "kv_append_ring_kernel<float>",
+                 "kv_append_kernel<float4>", "kv_append_kernel<float>", "adec_partial_kernel<DH>", "adec_gqa_partial_kernel<DH>"):
         assert inst in src, inst
     for dh in (32, 64, 128):
-        assert "NK_ADW_LAUNCH(%d);" % dh in src
-    # the existing decode kernels are not edited: the window header only includes theirs
-    for old in ("nk_attention_decode.h", "nk_attention_gqa.h"):
-        txt = _read("neuronika_amd", "csrc", old)
-        assert "window" not in txt.lower() and "% cap" not in txt and "adw_" not in txt, old
+        assert "ADEC_LAUNCH(%d);" % dh in src
+    # the windowed result at n <= W is the plain and the grouped result by construction: each of the three partial kernels and each of
+    # the three generic kernels is its switches around the ONE body, with no statement of its own
+    switches = {"adec_partial_kernel": ("partial", "0", "1", "0"), "adec_gqa_partial_kernel": ("partial", "1", "ADEC_GQA_HEADS", "0"),
+                "adw_partial_kernel": ("partial", "1", "NH", "1"), "adec_generic_kernel": ("generic", "0", None, "0"),
+                "adec_gqa_generic_kernel": ("generic", "1", None, "0"), "adw_generic_kernel": ("generic", "1", None, "1"),
+                "adec_combine_kernel": ("combine", None, None, "0"), "adw_combine_kernel": ("combine", None, None, "1")}
+    for kernel, (body, grouped, nh, window) in switches.items():
+        own = _kernel_text(src, kernel)
+        assert own.count("#include") == 1 and '#include "%s"' % bodies[body] in own, kernel
+        assert not re.search(r"\b(for|if|return)\b", own) and "__builtin" not in own, kernel
+        for macro, value in (("ADEC_GROUPED", grouped), ("ADEC_NH", nh), ("ADEC_WINDOW", window)):
+            assert (value is None and macro not in own) or "#define %s %s\n" % (macro, value) in own, (kernel, macro)
+            assert value is None or "#undef %s\n" % macro in own, (kernel, macro)
+    # the window and the slots live in the bodies, behind the switch
+    partial = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", bodies["partial"]))
+    assert "#if ADEC_WINDOW" in partial and "lo % cap" in partial and "(unsigned)" in partial and "adec_wrap(" in partial
+    ring = src[src.index("void kv_append_body("):]
+    ring = ring[:ring.index("\n}\n")]
+    assert "RING ? pos % cap : pos" in ring and "!RING && pos >= cap" in ring
+    for kernel, flag in (("kv_append_kernel", "false"), ("kv_append_ring_kernel", "true")):
+        assert "kv_append_body<T, %s>(" % flag in _kernel_text(src, kernel), kernel
 
 
 def test_rust_mirror_names_the_ffi_calls():
