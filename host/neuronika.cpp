@@ -980,6 +980,9 @@ struct DecodeStepFwd : Forward {
     bool core = false;  // every start 0, T >= 2, head size of the fused core
     Shared<HipArray> rope;  // the rotary table or null: the new Q and K rows are rotated at start[b] + t before the append
     RopeGeom rg, rgk;       // rg: NH = H + Hkv when packed (Q|K in one launch), H otherwise; rgk: the K launch of the unpacked form, NH = Hkv
+    // page > 0: kc / vc are the pools of a PagedKvCache, cap is unused.  `start` then holds, in one upload, the B starts, the
+    // (B, max_pages) table rows and the ncopy (src | dst) page ids of the copies reserve() asked for
+    int page = 0, max_pages = 0, num_pages = 0, ncopy = 0;
     void forward() const override {
         nk_device* dev = D(x);
         const int n = B * T, d = H * dh, dkv = Hkv * dh;
@@ -998,7 +1001,12 @@ struct DecodeStepFwd : Forward {
             rope_inplace(dev, const_cast<float*>(Q), ld, rope, st, rg, false);
             if (!qkv) rope_inplace(dev, const_cast<float*>(K), ldkv, rope, st, rgk, false);
         }
-        if (ring) check(nk_kv_cache_append_ring(dev, kc->ptr(), vc->ptr(), K, V, ldkv, st, B, T, Hkv, dh, cap));
+        const int* tab = st + B;
+        if (page > 0) {  // the copies first: a page reserve() made private must hold its prefix before the new rows land in it
+            const int* cp = tab + (size_t)B * max_pages;
+            if (ncopy > 0) check(nk_kv_pages_copy(dev, kc->ptr(), vc->ptr(), cp, cp + ncopy, ncopy, Hkv, dh, page, num_pages));
+            check(nk_kv_pages_append(dev, kc->ptr(), vc->ptr(), K, V, ldkv, st, tab, max_pages, B, T, Hkv, dh, page, num_pages));
+        } else if (ring) check(nk_kv_cache_append_ring(dev, kc->ptr(), vc->ptr(), K, V, ldkv, st, B, T, Hkv, dh, cap));
         else check(nk_kv_cache_append(dev, kc->ptr(), vc->ptr(), K, V, ldkv, st, B, T, Hkv, dh, cap));
         if (core && Hkv != H) {  // the core runs on H heads of K and V: the step's rows repeated into the node's temporaries
             const int G = H / Hkv;
@@ -1013,6 +1021,9 @@ struct DecodeStepFwd : Forward {
             check(nk_attention_qkv_causal_fwd(dev, qkv->ptr(), nullptr, nullptr, nullptr, ctx->ptr(), B, T, H, dh, scale, 0.0, 0, 0, 0));
         else if (core)
             check(nk_attention_causal_fwd(dev, Q, K, V, nullptr, nullptr, nullptr, ctx->ptr(), B, T, H, dh, scale, 0.0, 0, 0, 0));
+        else if (page > 0)
+            check(nk_attention_decode_paged_fwd(dev, Q, ld, kc->ptr(), vc->ptr(), st, tab, max_pages, ctx->ptr(), ws->ptr(), B, T, H, Hkv, dh, page,
+                                                num_pages, window, scale));
         else if (window > 0)
             check(nk_attention_decode_window_fwd(dev, Q, ld, kc->ptr(), vc->ptr(), st, ctx->ptr(), ws->ptr(), B, T, H, Hkv, dh, cap, window, ring ? 1 : 0,
                                                  scale));
@@ -3424,6 +3435,9 @@ void KvCache::truncate(const std::vector<int>& lens) {
     lens_ = lens;
 }
 
+static std::shared_ptr<DecodeStepFwd> decode_step_node(const MultiheadAttention& m, const Var& x, int batch, int T, bool fresh, bool packed,
+                                                       const Shared<HipArray>& wqkv, const Shared<HipArray>& bqkv, History<ForwardEntry>& hf);
+
 Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) const {
     if (!causal) panic("MultiheadAttention::forward_step is the incremental form of the CAUSAL forward: set causal = true");
     if (*drop.status && drop.p > 0.0) panic("MultiheadAttention::forward_step runs in inference: dropout is active (p > 0 in train mode), call drop.eval() first");
@@ -3462,15 +3476,40 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
                   std::to_string(T) + " more exceed the cache's capacity of " + std::to_string(cache.capacity));
         fresh = fresh && cache.lens()[b] == 0;
     }
-    auto fw = std::make_shared<DecodeStepFwd>();
-    fw->B = batch; fw->T = T; fw->H = heads; fw->Hkv = kv_heads; fw->dh = dh; fw->cap = cache.capacity;
-    fw->window = window; fw->ring = cache.rolling;
-    fw->x = x.data;
     History<ForwardEntry> hf = x.history;
+    auto fw = decode_step_node(*this, x, batch, T, fresh, packed_qkv && still_packed(), wqkv_, bqkv_, hf);
+    fw->cap = cache.capacity;
+    fw->ring = cache.rolling;
+    fw->kc = cache.k; fw->vc = cache.v;
+    if (!fw->core && cache.rolling && (long long)window + T - 1 > cache.capacity)
+        panic("MultiheadAttention::forward_step: a rolling cache of " + std::to_string(cache.capacity) + " slots cannot hold a window of " +
+              std::to_string(window) + " keys and " + std::to_string(T) + " new rows (window + T - 1 <= capacity): chunk the prompt into slices of at most " +
+              std::to_string(std::max(0, cache.capacity - window + 1)) + " rows");
+    if (!fw->core) fw->ws = cache.workspace(T, heads, window);  // one partial per QUERY head
+    if (window > 0) cache.remember_window(window);              // for truncate(): the core path asks for no scratch
+    static_assert(sizeof(int) == sizeof(float), "the start positions travel in an f32 array");
+    fw->start = std::make_shared<HipArray>(x.device(), Shape{batch}, HipArray::Uninit{});
+    fw->start->upload(reinterpret_cast<const float*>(cache.lens().data()));
+    cache.advance(T);
+    auto y = fw->out;
+    return Var::node(y, fw, std::move(hf));
+}
+
+// The part of the step's node both forward_step overloads build the same way: the projections, the temporaries, rope and the
+// decision for the causal core.  The caller adds the cache, the scratch and the start positions.
+static std::shared_ptr<DecodeStepFwd> decode_step_node(const MultiheadAttention& m, const Var& x, int batch, int T, bool fresh, bool packed,
+                                                const Shared<HipArray>& wqkv, const Shared<HipArray>& bqkv, History<ForwardEntry>& hf) {
+    const int d_model = m.d_model, heads = m.heads, kv_heads = m.kv_heads, window = m.window, dh = d_model / heads;
+    const Linear &q = m.q, &k = m.k, &v = m.v, &o = m.o;
+    const Shared<RotaryEmbedding>& rope = m.rope;
+    auto fw = std::make_shared<DecodeStepFwd>();
+    fw->B = batch; fw->T = T; fw->H = heads; fw->Hkv = kv_heads; fw->dh = dh;
+    fw->window = window;
+    fw->x = x.data;
     for (const Linear* l : {&q, &k, &v, &o}) { hf.merge(l->weight.var.history); hf.merge(l->bias.var.history); }
     const int n = batch * T, dkv = kv_heads * dh;
-    if (packed_qkv && still_packed()) {
-        fw->w[0] = wqkv_; fw->b[0] = bqkv_;
+    if (packed) {
+        fw->w[0] = wqkv; fw->b[0] = bqkv;
         fw->qkv = zeros_like(x.data, Shape{n, d_model + 2 * dkv});
     } else {
         const Linear* ls[3] = {&q, &k, &v};
@@ -3487,7 +3526,6 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
     fw->wo = o.weight.var.data; fw->bo = o.bias.var.data;
     fw->ctx = zeros_like(x.data, Shape{n, d_model});
     fw->out = zeros_like(x.data, Shape{n, d_model});
-    fw->kc = cache.k; fw->vc = cache.v;
     if (rope) {
         fw->rope = rope->table;
         fw->rg = rope_geom(*rope, batch, T, fw->qkv ? heads + kv_heads : heads);  // packed: the Q and K heads are contiguous columns
@@ -3500,22 +3538,239 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
     const bool core_fits = (long long)batch * heads * tiles * tiles < (1ll << 31) / 32 && (long long)n * 3 * d_model < (1ll << 31);
     // with a window the core, which has none, takes the prefill only while the band is the whole triangle
     fw->core = fresh && T >= 2 && core_fits && nk_attention_supported(T, dh, 0.0, 0) != 0 && (window == 0 || T <= window);
-    if (!fw->core && cache.rolling && (long long)window + T - 1 > cache.capacity)
-        panic("MultiheadAttention::forward_step: a rolling cache of " + std::to_string(cache.capacity) + " slots cannot hold a window of " +
-              std::to_string(window) + " keys and " + std::to_string(T) + " new rows (window + T - 1 <= capacity): chunk the prompt into slices of at most " +
-              std::to_string(std::max(0, cache.capacity - window + 1)) + " rows");
-    if (!fw->core) fw->ws = cache.workspace(T, heads, window);  // one partial per QUERY head
-    if (window > 0) cache.remember_window(window);              // for truncate(): the core path asks for no scratch
     if (fw->core && kv_heads != heads) {  // nothing is allocated inside forward()
         fw->kf = zeros_like(x.data, Shape{n, d_model}); fw->vf = zeros_like(x.data, Shape{n, d_model});
         if (fw->qkv) fw->qf = zeros_like(x.data, Shape{n, d_model});
     }
+    return fw;
+}
+
+Var MultiheadAttention::forward_step(const Var& x, const std::vector<int>& seqs, PagedKvCache& cache) const {
+    if (!causal) panic("MultiheadAttention::forward_step is the incremental form of the CAUSAL forward: set causal = true");
+    if (*drop.status && drop.p > 0.0) panic("MultiheadAttention::forward_step runs in inference: dropout is active (p > 0 in train mode), call drop.eval() first");
+    const int batch = (int)seqs.size();
+    if (x.shape().size() != 2 || batch <= 0 || x.shape()[0] % batch != 0 || x.shape()[0] == 0 || x.shape()[1] != d_model)
+        panic("MultiheadAttention::forward_step: bad input shape");
+    const int T = x.shape()[0] / batch, dh = d_model / heads;
+    if (cache.heads != kv_heads || cache.head_dim != dh)
+        panic("MultiheadAttention::forward_step: the paged cache was built for " + std::to_string(cache.heads) + " heads of " +
+              std::to_string(cache.head_dim) + ", the step has " + std::to_string(kv_heads) + " kv heads (of " + std::to_string(heads) +
+              " query heads) of " + std::to_string(dh));
+    if (cache.k->device().get() != x.device().get()) panic("MultiheadAttention::forward_step: the cache lives on another device");
+    if (rope && rope->head_dim != dh)
+        panic("MultiheadAttention::forward_step: rope was built for heads of " + std::to_string(rope->head_dim) + ", the module has heads of " +
+              std::to_string(dh));
+    if (window < 0) panic("MultiheadAttention::forward_step: window must not be negative, got " + std::to_string(window));
+    bool fresh = true;
+    for (int b = 0; b < batch; ++b) {
+        const int s = seqs[b];
+        if (s < 0 || s >= cache.max_seqs)
+            panic("MultiheadAttention::forward_step: sequence id " + std::to_string(s) + " is outside [0, " + std::to_string(cache.max_seqs) + ")");
+        const int len = cache.lens()[s], behind = cache.behind(s);
+        if (rope && (long long)len + T > rope->max_pos)
+            panic("MultiheadAttention::forward_step: sequence " + std::to_string(s) + " holds " + std::to_string(len) + " positions, " +
+                  std::to_string(T) + " more exceed rope's table of " + std::to_string(rope->max_pos));
+        if (behind > 0 && window == 0)
+            panic("MultiheadAttention::forward_step: sequence " + std::to_string(s) + " released the pages below position " +
+                  std::to_string(behind) + ": it needs a layer with window > 0");
+        // row 0 of the step reads from position len + 1 - window on
+        if (behind > 0 && std::max(0, len + 1 - window) < behind)
+            panic("MultiheadAttention::forward_step: sequence " + std::to_string(s) + " released the pages below position " +
+                  std::to_string(behind) + ", a window of " + std::to_string(window) + " at length " + std::to_string(len) +
+                  " would read below it");
+        fresh = fresh && len == 0;
+    }
+    const std::vector<int> starts_before = cache.lens();
+    // the node and the scratch first (their panics: projection shapes, a scratch past 31 bits), then reserve(), which panics before
+    // it changes anything (out of pages, max_pages exceeded, duplicate ids); after it nothing panics
+    History<ForwardEntry> hf = x.history;
+    auto fw = decode_step_node(*this, x, batch, T, fresh, packed_qkv && still_packed(), wqkv_, bqkv_, hf);
+    if (!fw->core) fw->ws = cache.workspace(batch, T, heads, window);  // one partial per QUERY head
+    const std::vector<std::pair<int, int>> copies = cache.reserve(seqs, T);
+    fw->cap = 0;
+    fw->kc = cache.k; fw->vc = cache.v;
+    fw->page = cache.page; fw->max_pages = cache.max_pages; fw->num_pages = cache.num_pages; fw->ncopy = (int)copies.size();
     static_assert(sizeof(int) == sizeof(float), "the start positions travel in an f32 array");
-    fw->start = std::make_shared<HipArray>(x.device(), Shape{batch}, HipArray::Uninit{});
-    fw->start->upload(reinterpret_cast<const float*>(cache.lens().data()));
-    cache.advance(T);
+    std::vector<int> img((size_t)batch * (1 + cache.max_pages) + 2 * copies.size());
+    for (int b = 0; b < batch; ++b) {
+        img[b] = starts_before[seqs[b]];
+        std::copy_n(cache.table.rows().begin() + (size_t)seqs[b] * cache.max_pages, cache.max_pages, img.begin() + batch + (size_t)b * cache.max_pages);
+    }
+    for (size_t i = 0; i < copies.size(); ++i) {
+        img[(size_t)batch * (1 + cache.max_pages) + i] = copies[i].first;
+        img[(size_t)batch * (1 + cache.max_pages) + copies.size() + i] = copies[i].second;
+    }
+    fw->start = std::make_shared<HipArray>(x.device(), Shape{(int)img.size()}, HipArray::Uninit{});
+    fw->start->upload(reinterpret_cast<const float*>(img.data()));
     auto y = fw->out;
     return Var::node(y, fw, std::move(hf));
+}
+
+PageTable::PageTable(int num_pages_, int page_, int max_seqs_, int max_pages_)
+    : num_pages(num_pages_), page(page_), max_seqs(max_seqs_), max_pages(max_pages_) {
+    if (num_pages <= 0 || max_seqs <= 0 || max_pages <= 0) panic("PageTable: num_pages, max_seqs and max_pages must be positive");
+    if (page < 16 || (page & (page - 1)) != 0) panic("PageTable: page must be a power of two and at least 16, got " + std::to_string(page));
+    if ((long long)max_pages * page > (long long)INT_MAX - 1024) panic("PageTable: max_pages * page must stay below 2^31 - 1024");
+    if ((long long)max_seqs * max_pages > (long long)INT_MAX) panic("PageTable: max_seqs * max_pages must fit 31 bits");
+    reset();
+}
+void PageTable::reset() {
+    lens_.assign((size_t)max_seqs, 0);
+    behind_.assign((size_t)max_seqs, 0);
+    rows_.assign((size_t)max_seqs * max_pages, -1);
+    ref_.assign((size_t)num_pages, 0);
+    free_.clear();
+    for (int p = 0; p < num_pages; ++p) free_.insert(free_.end(), p);
+}
+void PageTable::check_seq(int seq, const char* what) const {
+    if (seq < 0 || seq >= max_seqs)
+        panic(std::string("PageTable::") + what + ": sequence id " + std::to_string(seq) + " is outside [0, " + std::to_string(max_seqs) + ")");
+}
+void PageTable::unref(int p) {
+    if (--ref_[(size_t)p] == 0) free_.insert(p);
+}
+std::vector<int> PageTable::row(int seq) const {
+    check_seq(seq, "row");
+    return std::vector<int>(rows_.begin() + (size_t)seq * max_pages, rows_.begin() + (size_t)(seq + 1) * max_pages);
+}
+std::vector<int> PageTable::pages(int seq) const {
+    std::vector<int> out;
+    for (int p : row(seq))
+        if (p >= 0) out.push_back(p);
+    return out;
+}
+int PageTable::refcount(int p) const {
+    if (p < 0 || p >= num_pages) panic("PageTable::refcount: page id " + std::to_string(p) + " is outside [0, " + std::to_string(num_pages) + ")");
+    return ref_[(size_t)p];
+}
+std::vector<int> PageTable::free_pages() const { return std::vector<int>(free_.begin(), free_.end()); }
+int PageTable::behind(int seq) const {
+    check_seq(seq, "behind");
+    return behind_[(size_t)seq];
+}
+std::vector<std::pair<int, int>> PageTable::reserve(const std::vector<int>& seqs, int T) {
+    if (T <= 0) panic("PageTable::reserve: T must be positive, got " + std::to_string(T));
+    // a dry run first: ids, duplicates, max_pages, and the pages needed - a shared partial last page costs one more, unless an
+    // earlier sequence of this call already left it to this one
+    std::vector<char> seen((size_t)max_seqs, 0);
+    std::unordered_map<int, int> left;  // shared page -> owners other sequences of this call have taken away
+    size_t need = 0;
+    for (int s : seqs) {
+        check_seq(s, "reserve");
+        if (seen[(size_t)s]) panic("PageTable::reserve: sequence " + std::to_string(s) + " is listed twice");
+        seen[(size_t)s] = 1;
+        const long long len = lens_[(size_t)s], have = (len + page - 1) / page, want = (len + T + page - 1) / page;
+        if (want > max_pages)
+            panic("PageTable::reserve: sequence " + std::to_string(s) + " holds " + std::to_string(len) + " positions, " + std::to_string(T) +
+                  " more exceed max_pages = " + std::to_string(max_pages) + " pages of " + std::to_string(page));
+        need += (size_t)(want - have);
+        if (len % page != 0) {
+            const int last = rows_[(size_t)s * max_pages + (size_t)(have - 1)];
+            if (ref_[(size_t)last] - left[last] > 1) {
+                ++left[last];
+                ++need;
+            }
+        }
+    }
+    if (need > free_.size())
+        panic("PageTable::reserve: " + std::to_string(need) + " pages needed, " + std::to_string(free_.size()) + " of " + std::to_string(num_pages) +
+              " are free");
+    std::vector<std::pair<int, int>> copies;
+    auto take = [this]() {
+        const int p = *free_.begin();
+        free_.erase(free_.begin());
+        ref_[(size_t)p] = 1;
+        return p;
+    };
+    for (int s : seqs) {
+        int* r = rows_.data() + (size_t)s * max_pages;
+        const int len = lens_[(size_t)s], have = (len + page - 1) / page, want = (int)(((long long)len + T + page - 1) / page);
+        if (len % page != 0 && ref_[(size_t)r[have - 1]] > 1) {
+            const int old = r[have - 1];
+            --ref_[(size_t)old];  // still owned by another
+            r[have - 1] = take();
+            copies.emplace_back(old, r[have - 1]);
+        }
+        for (int i = have; i < want; ++i) r[i] = take();
+        lens_[(size_t)s] = len + T;
+    }
+    return copies;
+}
+void PageTable::truncate(int seq, int len) {
+    check_seq(seq, "truncate");
+    if (len < 0 || len > lens_[(size_t)seq] || len < behind_[(size_t)seq])
+        panic("PageTable::truncate: sequence " + std::to_string(seq) + " holds positions [" + std::to_string(behind_[(size_t)seq]) + ", " +
+              std::to_string(lens_[(size_t)seq]) + "), asked for " + std::to_string(len));
+    int* r = rows_.data() + (size_t)seq * max_pages;
+    const int have = (lens_[(size_t)seq] + page - 1) / page;
+    for (int i = (len + page - 1) / page; i < have; ++i)
+        if (r[i] >= 0) {
+            unref(r[i]);
+            r[i] = -1;
+        }
+    lens_[(size_t)seq] = len;
+}
+void PageTable::release(int seq) {
+    check_seq(seq, "release");
+    int* r = rows_.data() + (size_t)seq * max_pages;
+    for (int i = 0; i < max_pages; ++i)
+        if (r[i] >= 0) {
+            unref(r[i]);
+            r[i] = -1;
+        }
+    lens_[(size_t)seq] = 0;
+    behind_[(size_t)seq] = 0;
+}
+void PageTable::fork(int src, int dst) {
+    check_seq(src, "fork");
+    check_seq(dst, "fork");
+    if (src == dst) panic("PageTable::fork: source and destination are both sequence " + std::to_string(src));
+    if (lens_[(size_t)dst] != 0 || behind_[(size_t)dst] != 0)
+        panic("PageTable::fork: sequence " + std::to_string(dst) + " is not empty: release it first");
+    const int* from = rows_.data() + (size_t)src * max_pages;
+    int* to = rows_.data() + (size_t)dst * max_pages;
+    for (int i = 0; i < max_pages; ++i) {
+        to[i] = from[i];
+        if (from[i] >= 0) ++ref_[(size_t)from[i]];
+    }
+    lens_[(size_t)dst] = lens_[(size_t)src];
+    behind_[(size_t)dst] = behind_[(size_t)src];
+}
+void PageTable::release_behind(int seq, int pos) {
+    check_seq(seq, "release_behind");
+    if (pos < 0 || pos > lens_[(size_t)seq])
+        panic("PageTable::release_behind: sequence " + std::to_string(seq) + " holds " + std::to_string(lens_[(size_t)seq]) +
+              " positions, asked to release below " + std::to_string(pos));
+    int* r = rows_.data() + (size_t)seq * max_pages;
+    for (int i = 0; i < pos / page; ++i)
+        if (r[i] >= 0) {
+            unref(r[i]);
+            r[i] = -1;
+        }
+    behind_[(size_t)seq] = std::max(behind_[(size_t)seq], pos / page * page);
+}
+
+PagedKvCache::PagedKvCache(DevicePtr dev, int num_pages_, int page_, int kv_heads_, int head_dim_, int max_seqs_, int max_pages_)
+    : num_pages(num_pages_), page(page_), heads(kv_heads_), head_dim(head_dim_), max_seqs(max_seqs_), max_pages(max_pages_),
+      table(num_pages_, page_, max_seqs_, max_pages_) {
+    if (heads <= 0 || head_dim <= 0) panic("PagedKvCache: kv_heads and head_dim must be positive");
+    // KvCache's limit, on one pool
+    if ((unsigned long long)num_pages * heads * page * head_dim > (unsigned long long)INT_MAX)
+        panic("PagedKvCache: num_pages * kv_heads * page * head_dim must fit 31 bits");
+    const Shape s{num_pages, heads, page, head_dim};
+    k = std::make_shared<HipArray>(dev, s, HipArray::Uninit{});
+    v = std::make_shared<HipArray>(dev, s, HipArray::Uninit{});
+}
+void PagedKvCache::fork(int src, int dst) { table.fork(src, dst); }
+Shared<HipArray> PagedKvCache::workspace(int batch, int T, int query_heads, int window) {
+    const size_t n = nk_attention_decode_paged_workspace(batch, T, query_heads, head_dim, max_pages, page, window);
+    if (n == 0 || n > (size_t)INT_MAX)
+        panic("PagedKvCache: the decode workspace for " + std::to_string(batch) + " sequences of " + std::to_string(T) + " rows does not fit 31 bits");
+    if (n > ws_n_) {  // a node keeps the one it was built with alive
+        ws_ = std::make_shared<HipArray>(k->device(), Shape{(int)n}, HipArray::Uninit{});
+        ws_n_ = n;
+    }
+    return ws_;
 }
 
 }  // namespace nn

@@ -31,6 +31,7 @@
 #include <cstdint>
 #include <functional>
 #include <memory>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -952,6 +953,74 @@ struct KvCache {
     int window_ = 0;  // of the layer that last stepped the cache (0: none yet)
 };
 
+// The page table of a paged key / value cache (ours; layout at nk_attention_decode_paged_fwd in neuronika_hip.h): which of `num_pages`
+// physical pages of `page` positions holds which positions of which of `max_seqs` sequences.  Pure host state, no device: sequence s
+// has a length, a row of `max_pages` page ids (-1 where it owns nothing) and `behind`, the first position it still holds; every page
+// has a reference count, and the pages nobody references are the free set.  Every operation that can fail panics BEFORE it changes
+// any state: out of pages, max_pages exceeded, an id out of range, duplicate ids.
+//   reserve(seqs, T)         grows every listed sequence by T positions, sequence by sequence in the order of `seqs`, taking the
+//                            lowest-numbered free page each time.  A sequence whose last page is partial and shared (refcount > 1)
+//                            first gets a page of its own there, and the pair (old, new) is returned as a copy to make before the
+//                            append: a page with more than one owner is never written.
+//   truncate(seq, len)       releases the pages wholly past `len`; panics for len > the length or len < behind(seq)
+//   release(seq)             releases everything the sequence owns; length and behind back to 0
+//   fork(src, dst)           dst must be empty: it shares every page of src by reference count and takes its length and behind
+//   release_behind(seq, pos) releases the pages wholly below `pos` (<= the length) and sets their entries to -1: how a windowed
+//                            layer bounds its memory.  behind(seq) becomes the first position of the first page kept
+//   reset()                  back to the empty table
+struct PageTable {
+    PageTable(int num_pages, int page, int max_seqs, int max_pages);
+    int num_pages, page, max_seqs, max_pages;
+    const std::vector<int>& lens() const { return lens_; }
+    std::vector<int> pages(int seq) const;  // the ids the sequence owns, in position order
+    std::vector<int> row(int seq) const;    // max_pages ints
+    const std::vector<int>& rows() const { return rows_; }  // (max_seqs, max_pages)
+    int refcount(int page_id) const;
+    std::vector<int> free_pages() const;  // ascending
+    int behind(int seq) const;
+    std::vector<std::pair<int, int>> reserve(const std::vector<int>& seqs, int T);
+    void truncate(int seq, int len);
+    void release(int seq);
+    void fork(int src, int dst);
+    void release_behind(int seq, int pos);
+    void reset();
+
+   private:
+    void check_seq(int seq, const char* what) const;
+    void unref(int page_id);
+    std::vector<int> lens_, behind_, rows_, ref_;
+    std::set<int> free_;
+};
+
+// A paged key / value cache: the two pools (num_pages, kv_heads, page, head_dim), allocated once and never initialised, a PageTable,
+// and the decode scratch, regrown like KvCache::workspace.  The PageTable operations are forwarded.  As in KvCache, the elements of
+// one pool must fit 31 bits (num_pages * kv_heads * page * head_dim <= INT_MAX).
+struct PagedKvCache {
+    PagedKvCache(DevicePtr dev, int num_pages, int page, int kv_heads, int head_dim, int max_seqs, int max_pages);
+    int num_pages, page, heads, head_dim, max_seqs, max_pages;
+    PageTable table;
+    Shared<HipArray> k, v;
+    const std::vector<int>& lens() const { return table.lens(); }
+    std::vector<int> pages(int seq) const { return table.pages(seq); }
+    std::vector<int> row(int seq) const { return table.row(seq); }
+    int refcount(int page_id) const { return table.refcount(page_id); }
+    std::vector<int> free_pages() const { return table.free_pages(); }
+    int behind(int seq) const { return table.behind(seq); }
+    std::vector<std::pair<int, int>> reserve(const std::vector<int>& seqs, int T) { return table.reserve(seqs, T); }
+    void truncate(int seq, int len) { table.truncate(seq, len); }
+    void release(int seq) { table.release(seq); }
+    void fork(int src, int dst);  // the table's fork; the pages stay where they are
+    void release_behind(int seq, int pos) { table.release_behind(seq, pos); }
+    void reset() { table.reset(); }
+    // at least nk_attention_decode_paged_workspace(batch, T, query_heads, head_dim, max_pages, page, window) floats
+    Shared<HipArray> workspace(int batch, int T, int query_heads, int window);
+    size_t workspace_floats() const { return ws_ ? ws_->len() : 0; }
+
+   private:
+    Shared<HipArray> ws_;
+    size_t ws_n_ = 0;
+};
+
 // Multi-head attention composed from reference ops (the module does not exist in the reference;
 // SURVEY.md 8a note): Q,K,V = x.mm_t(W)+b; per (b,h): P = dropout(softmax(Q.mm_t(K)*dh^-1/2, 1));
 // O = P.mm(V); out = cat(O).mm_t(Wo)+bo.
@@ -1033,6 +1102,17 @@ struct MultiheadAttention {
     // Panics: causal == false; dropout active (train mode and p > 0: call drop.eval() first); any lens[b] + T > capacity; a
     // batch / head size that differs from the cache's; cache.heads != kv_heads.
     Var forward_step(const Var& x, int batch, KvCache& cache) const;
+    // The same node over a PAGED cache: the batch is seqs.size(), any subset of the cache's sequences in any order (continuous
+    // batching); row b*T + t of x is position lens[seqs[b]] + t of sequence seqs[b].  Same preconditions (causal, dropout off) and
+    // rope at lens + t.  When the node is built, `cache.reserve(seqs, T)` runs, then ONE upload of the starts, the seqs.size() *
+    // max_pages table rows and the copy pairs reserve returned, if any.  forward() runs the page copies, then
+    // nk_kv_pages_append, then the attention; running it again repeats the same writes.  A fresh prefill (T >= 2, every length 0, a
+    // head size of the fused core, T <= window if windowed) keeps the causal core; every other step takes
+    // nk_attention_decode_paged_fwd with the module's `window`.
+    // Panics, all before any state changes: what reserve refuses (out of pages, max_pages, ids); a cache built for other kv heads /
+    // head size; a sequence with behind > 0 stepped by a layer with window == 0, or whose window would reach below behind;
+    // lens + T beyond rope's table.
+    Var forward_step(const Var& x, const std::vector<int>& seqs, PagedKvCache& cache) const;
 
    private:
     VarDiff forward_impl(const VarDiff& x, int batch, const Segments* seg) const;

@@ -498,6 +498,53 @@ PYBIND11_MODULE(_tape, m) {
         .def("reset", &nn::KvCache::reset, "every length back to 0")
         .def("truncate", &nn::KvCache::truncate, py::arg("lens"),
              "Give every sample a length no longer than its current one: ragged prompts after a right-padded prefill, roll-back.");
+    py::class_<nn::PageTable>(nn, "PageTable")
+        .def(py::init<int, int, int, int>(), py::arg("num_pages"), py::arg("page"), py::arg("max_seqs"), py::arg("max_pages"),
+             "The page table of a paged key / value cache, on the host: per sequence a length and a row of page ids (-1: none), per "
+             "page a reference count. Every operation that can fail raises before it changes anything.")
+        .def_readonly("num_pages", &nn::PageTable::num_pages)
+        .def_readonly("page", &nn::PageTable::page)
+        .def_readonly("max_seqs", &nn::PageTable::max_seqs)
+        .def_readonly("max_pages", &nn::PageTable::max_pages)
+        .def("lens", [](const nn::PageTable& t) { return t.lens(); }, "positions held per sequence")
+        .def("pages", &nn::PageTable::pages, py::arg("seq"), "the page ids the sequence owns, in position order")
+        .def("row", &nn::PageTable::row, py::arg("seq"), "max_pages ints, -1 where the sequence owns nothing")
+        .def("refcount", &nn::PageTable::refcount, py::arg("page"))
+        .def("free_pages", &nn::PageTable::free_pages, "the free page ids, ascending")
+        .def("behind", &nn::PageTable::behind, py::arg("seq"), "the first position the sequence still holds")
+        .def("reserve", &nn::PageTable::reserve, py::arg("seqs"), py::arg("T"),
+             "Grow every listed sequence by T positions, lowest free page first; returns the (old, new) page copies to make.")
+        .def("truncate", &nn::PageTable::truncate, py::arg("seq"), py::arg("len"))
+        .def("release", &nn::PageTable::release, py::arg("seq"))
+        .def("fork", &nn::PageTable::fork, py::arg("src"), py::arg("dst"))
+        .def("release_behind", &nn::PageTable::release_behind, py::arg("seq"), py::arg("pos"))
+        .def("reset", &nn::PageTable::reset);
+    py::class_<nn::PagedKvCache>(nn, "PagedKvCache")
+        .def(py::init<DevicePtr, int, int, int, int, int, int>(), py::arg("dev"), py::arg("num_pages"), py::arg("page"), py::arg("kv_heads"),
+             py::arg("head_dim"), py::arg("max_seqs"), py::arg("max_pages"),
+             "Keys and values of one causal attention layer in pages: two pools (num_pages, kv_heads, page, head_dim) and a PageTable, "
+             "for MultiheadAttention.forward_step(x, seqs, cache).")
+        .def_readonly("num_pages", &nn::PagedKvCache::num_pages)
+        .def_readonly("page", &nn::PagedKvCache::page)
+        .def_readonly("heads", &nn::PagedKvCache::heads)
+        .def_readonly("head_dim", &nn::PagedKvCache::head_dim)
+        .def_readonly("max_seqs", &nn::PagedKvCache::max_seqs)
+        .def_readonly("max_pages", &nn::PagedKvCache::max_pages)
+        .def("workspace_floats", &nn::PagedKvCache::workspace_floats, "floats of decode scratch the cache holds now")
+        .def("k_data", [](const nn::PagedKvCache& c) { return to_numpy(*c.k); }, "the key pool, downloaded")
+        .def("v_data", [](const nn::PagedKvCache& c) { return to_numpy(*c.v); }, "the value pool, downloaded")
+        .def("lens", [](const nn::PagedKvCache& c) { return c.lens(); }, "positions held per sequence")
+        .def("pages", &nn::PagedKvCache::pages, py::arg("seq"))
+        .def("row", &nn::PagedKvCache::row, py::arg("seq"))
+        .def("refcount", &nn::PagedKvCache::refcount, py::arg("page"))
+        .def("free_pages", &nn::PagedKvCache::free_pages)
+        .def("behind", &nn::PagedKvCache::behind, py::arg("seq"))
+        .def("reserve", &nn::PagedKvCache::reserve, py::arg("seqs"), py::arg("T"))
+        .def("truncate", &nn::PagedKvCache::truncate, py::arg("seq"), py::arg("len"))
+        .def("release", &nn::PagedKvCache::release, py::arg("seq"))
+        .def("fork", &nn::PagedKvCache::fork, py::arg("src"), py::arg("dst"))
+        .def("release_behind", &nn::PagedKvCache::release_behind, py::arg("seq"), py::arg("pos"))
+        .def("reset", &nn::PagedKvCache::reset);
     py::class_<nn::Segments>(nn, "Segments")
         .def(py::init<DevicePtr, int, int, const std::vector<std::vector<int>>&>(), py::arg("dev"), py::arg("batch"), py::arg("S"), py::arg("doc_lens"),
              "Packed sequences: per sample the lengths of its documents (positive, sum <= S; a remainder is one more document). Holds the "
@@ -586,12 +633,19 @@ PYBIND11_MODULE(_tape, m) {
         .def("forward", py::overload_cast<const VarDiff&, int, const nn::Segments&>(&nn::MultiheadAttention::forward, py::const_), py::arg("x"),
              py::arg("batch"), py::arg("segments"),
              "Packed sequences: every token attends to its own document only and rope restarts at every document start.")
-        .def("forward_step", &nn::MultiheadAttention::forward_step, py::arg("x"), py::arg("batch"), py::arg("cache"),
+        .def("forward_step", py::overload_cast<const Var&, int, nn::KvCache&>(&nn::MultiheadAttention::forward_step, py::const_), py::arg("x"),
+             py::arg("batch"), py::arg("cache"),
              "Incremental decoding: x holds the new positions only, (batch*T, d_model); returns (batch*T, d_model) without a gradient. "
              "The cache's lengths advance when the node is built. Needs causal = True and inactive dropout (drop.eval()).")
         // a differentiable input (what the other layers return) enters through its data and forward tape; still no gradient out
         .def("forward_step", [](const nn::MultiheadAttention& m, const VarDiff& x, int batch, nn::KvCache& cache) {
-                 return m.forward_step(x.var, batch, cache); }, py::arg("x"), py::arg("batch"), py::arg("cache"));
+                 return m.forward_step(x.var, batch, cache); }, py::arg("x"), py::arg("batch"), py::arg("cache"))
+        .def("forward_step", py::overload_cast<const Var&, const std::vector<int>&, nn::PagedKvCache&>(&nn::MultiheadAttention::forward_step, py::const_),
+             py::arg("x"), py::arg("seqs"), py::arg("cache"),
+             "The same step over a paged cache: the batch is len(seqs), any subset of the cache's sequences in any order. Pages are "
+             "reserved when the node is built; forward() runs the page copies, the append and the attention.")
+        .def("forward_step", [](const nn::MultiheadAttention& m, const VarDiff& x, const std::vector<int>& seqs, nn::PagedKvCache& cache) {
+                 return m.forward_step(x.var, seqs, cache); }, py::arg("x"), py::arg("seqs"), py::arg("cache"));
 
     py::module_ optim = m.def_submodule("optim");
     {

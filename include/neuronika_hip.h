@@ -1041,6 +1041,51 @@ int nk_attention_decode_window_fwd(nk_device* dev, const float* Q, int ldq, cons
 size_t nk_attention_decode_window_workspace(int B, int T, int H, int dh, int window);
 int nk_kv_cache_append_ring(nk_device* dev, float* Kc, float* Vc, const float* K, const float* V, int ld, const int* start, int B, int T,
                             int H, int dh, int cap);
+/* ------------------------------------------------------------------ paged decoding --
+ * Ours: the block table of vLLM's PagedAttention (Kwon et al. 2023) under the decode kernels above.  The keys and values of every
+ * sequence live in fixed-size pages of two pools instead of one (B, Hkv, cap, dh) slab per batch, so memory is the sum of the lengths
+ * held, a sequence can join or leave a running batch, and sequences with a common prefix can name the same pages.
+ * Layout: Kp, Vp are (num_pages, Hkv, page, dh): one head's slice of a page is contiguous, a lane group still reads runs of
+ *   consecutive keys.  `table` is a DEVICE int32 (B, max_pages): position p of sample b lives in page table[b*max_pages + p / page] at
+ *   slot p % page.  `page` is a power of two, 16 <= page: every chunk size of the library is a power of two, so a chunk is either
+ *   inside one page or made of whole pages.  The virtual capacity cap_v = max_pages * page must stay below 2^31 - 1024, the position
+ *   limit of the window kernels.
+ * nk_kv_pages_append: row b*T + t of K / V (row stride ld, H = the kv heads) goes to position start[b] + t, K and V in one launch, a
+ *   bit-exact copy; 16-byte accesses under nk_kv_cache_append's conditions.  Rows with a negative position or one >= cap_v are
+ *   dropped, and so is a row whose table entry is outside [0, num_pages).  Nothing else of the pools is touched.
+ * nk_kv_pages_copy: whole pages src[i] -> dst[i], 0 <= i < n (DEVICE int32 arrays), all H heads, K and V, one streaming launch.  A
+ *   pair with an id outside [0, num_pages) is dropped; src[i] == dst[i] is a no-op; a page that is the destination of one pair must
+ *   not appear in another.  n == 0 is NK_OK without a launch.
+ * nk_attention_decode_paged_fwd: for sample b, query head h and the t-th new row, n = min(start[b] + t + 1, cap_v);
+ *   window == 0: o = softmax(q . K[0:n]^T * scale) . V[0:n], the rule of nk_attention_decode_gqa_fwd with cap := cap_v;
+ *   window  > 0: the keys max(0, n - W) .. n - 1 in chunks aligned to absolute positions, the rule of nk_attention_decode_window_fwd
+ *   with ring = 0.  Hkv <= H divides H; the heads of a group share one read of their chunk, 8 per block.  Q, ldq, O, start and
+ *   scale are nk_attention_decode_fwd's.
+ *   The kernels are the bodies of the contiguous ones with one more switch - where a position lives - and the contiguous forms'
+ *   combine kernels, so the summation order is by position, never by page.  Bit contract:
+ *   (1) the bits equal those of nk_attention_decode_gqa_fwd (window == 0) or nk_attention_decode_window_fwd with ring = 0 on the
+ *       (B, Hkv, cap_v, dh) cache gathered through the table - whatever the page size and whichever physical pages the table names;
+ *   (2) the bits of o for (b, h, t) depend on q, the keys / values at the positions it reads, n, W and scale ONLY: not on B, T,
+ *       max_pages, num_pages, the other samples, nor on what any other page, slot or table entry holds (NaN or 1e30, -1 or an id past
+ *       the pool are harmless);
+ *   (3) two samples whose rows name the same pages for a common prefix read the same memory: equal queries give equal bits.
+ *   Nothing leaves the pool: positions that do not count are redirected to position n - 1 before the lookup, so table entries past a
+ *   sequence's own pages, or below its window, are never read; the entry that is read is clamped into [0, num_pages) with one unsigned
+ *   min, which changes nothing for a valid entry.  A wrong table gives wrong numbers, never an access outside the two allocations.
+ *   No atomics; the chunk is the compile-time constant nk_attention_decode_chunk(dh); nothing depends on the CU count.
+ *   `workspace`: nk_attention_decode_paged_workspace(B, T, H, dh, max_pages, page, window) floats (needs no device): window == 0,
+ *   nk_attention_decode_workspace(B, T, H, dh, cap_v); otherwise nk_attention_decode_window_workspace(B, T, H, dh, window).  0 for a
+ *   geometry the entry point refuses.
+ *   NK_ERR_INVALID, nothing written: everything nk_attention_decode_gqa_fwd refuses with cap := cap_v, in its order and words; page
+ *   not a power of two or below 16; max_pages <= 0; num_pages <= 0; cap_v >= 2^31 - 1024; a null table; window < 0; a pool of more
+ *   than 2^32 16-byte units (dh 32 / 64 / 128). */
+int nk_kv_pages_append(nk_device* dev, float* Kp, float* Vp, const float* K, const float* V, int ld, const int* start, const int* table,
+                       int max_pages, int B, int T, int H, int dh, int page, int num_pages);
+int nk_kv_pages_copy(nk_device* dev, float* Kp, float* Vp, const int* src, const int* dst, int n, int H, int dh, int page, int num_pages);
+size_t nk_attention_decode_paged_workspace(int B, int T, int H, int dh, int max_pages, int page, int window);
+int nk_attention_decode_paged_fwd(nk_device* dev, const float* Q, int ldq, const float* Kp, const float* Vp, const int* start,
+                                  const int* table, int max_pages, float* O, float* workspace, int B, int T, int H, int Hkv, int dh, int page,
+                                  int num_pages, int window, float scale);
 /* ------------------------------------------------------------------ rotary position embedding --
  * Ours (the reference has no position encoding of any kind): RoPE, Su et al. 2021 (RoFormer), as LLaMA / Mistral / Qwen / GPT-NeoX /
  * Phi apply it to the query and key rows in front of the attention scores.

@@ -18,7 +18,7 @@ use std::{cell::{Cell, RefCell}, rc::Rc};
 
 use ndarray::{Array, Dimension, Ix0, Ix1, Ix2, Ix3, Ix4, Ix5, RemoveAxis};
 use neuronika_variable::{
-    hip::{Device, Gate, HipVar, HipVarDiff, KvBuffers, PaddingMode, RotaryTable, SamplerState},
+    hip::{Device, Gate, HipVar, HipVarDiff, KvBuffers, PaddingMode, PagedBuffers, RotaryTable, SamplerState},
     Reduction,
 };
 use rand::distributions::{Distribution, Uniform};
@@ -683,6 +683,226 @@ impl MultiheadAttention {
             cache.window.set(self.window);
         }
         cache.advance(rows / batch);
+        context.linear(self.o.weight.detached(), self.o.bias.detached(), false)
+    }
+}
+
+/// The page table of a paged key / value cache, on the host (ours; the tested mirror is `nn::PageTable` in `host/neuronika.hpp`):
+/// per sequence a length, a row of `max_pages` page ids (`-1`: none) and `behind`, the first position still held; per page a
+/// reference count.  Every operation that can fail panics before it changes any state.
+pub struct PageTable {
+    pub num_pages: usize,
+    pub page: usize,
+    pub max_seqs: usize,
+    pub max_pages: usize,
+    lens: Vec<usize>,
+    behind: Vec<usize>,
+    rows: Vec<i32>,
+    refs: Vec<usize>,
+    free: std::collections::BTreeSet<usize>,
+}
+
+impl PageTable {
+    pub fn new(num_pages: usize, page: usize, max_seqs: usize, max_pages: usize) -> Self {
+        assert!(num_pages > 0 && max_seqs > 0 && max_pages > 0, "PageTable: num_pages, max_seqs and max_pages must be positive");
+        assert!(page >= 16 && page.is_power_of_two(), "PageTable: page must be a power of two and at least 16");
+        assert!(max_pages * page < (1usize << 31) - 1024, "PageTable: max_pages * page must stay below 2^31 - 1024");
+        Self { num_pages, page, max_seqs, max_pages, lens: vec![0; max_seqs], behind: vec![0; max_seqs], rows: vec![-1; max_seqs * max_pages],
+               refs: vec![0; num_pages], free: (0..num_pages).collect() }
+    }
+
+    pub fn lens(&self) -> &[usize] {
+        &self.lens
+    }
+
+    /// `max_pages` ids, `-1` where the sequence owns nothing.
+    pub fn row(&self, seq: usize) -> &[i32] {
+        &self.rows[seq * self.max_pages..(seq + 1) * self.max_pages]
+    }
+
+    pub fn pages(&self, seq: usize) -> Vec<usize> {
+        self.row(seq).iter().filter(|&&p| p >= 0).map(|&p| p as usize).collect()
+    }
+
+    pub fn refcount(&self, page: usize) -> usize {
+        self.refs[page]
+    }
+
+    pub fn free_pages(&self) -> Vec<usize> {
+        self.free.iter().copied().collect()
+    }
+
+    pub fn behind(&self, seq: usize) -> usize {
+        self.behind[seq]
+    }
+
+    fn unref(&mut self, page: usize) {
+        self.refs[page] -= 1;
+        if self.refs[page] == 0 {
+            self.free.insert(page);
+        }
+    }
+
+    fn take(&mut self) -> usize {
+        let page = *self.free.iter().next().expect("PageTable: a free page");
+        self.free.remove(&page);
+        self.refs[page] = 1;
+        page
+    }
+
+    /// Grows every listed sequence by `rows` positions, in the order of `seqs`, lowest free page first.  A partial last page with
+    /// another owner is replaced by a page of the sequence's own; the `(old, new)` pairs are the copies to make before the append.
+    pub fn reserve(&mut self, seqs: &[usize], rows: usize) -> Vec<(usize, usize)> {
+        assert!(rows > 0, "PageTable::reserve: rows must be positive");
+        let mut left = std::collections::HashMap::<usize, usize>::new();
+        let mut need = 0;
+        for (i, &s) in seqs.iter().enumerate() {
+            assert!(s < self.max_seqs, "PageTable::reserve: sequence id {} is outside [0, {})", s, self.max_seqs);
+            assert!(!seqs[..i].contains(&s), "PageTable::reserve: sequence {} is listed twice", s);
+            let (have, want) = ((self.lens[s] + self.page - 1) / self.page, (self.lens[s] + rows + self.page - 1) / self.page);
+            assert!(want <= self.max_pages, "PageTable::reserve: sequence {} would exceed max_pages = {}", s, self.max_pages);
+            need += want - have;
+            if self.lens[s] % self.page != 0 {
+                let last = self.rows[s * self.max_pages + have - 1] as usize;
+                let gone = left.entry(last).or_insert(0);
+                if self.refs[last] - *gone > 1 {
+                    *gone += 1;
+                    need += 1;
+                }
+            }
+        }
+        assert!(need <= self.free.len(), "PageTable::reserve: {} pages needed, {} are free", need, self.free.len());
+        let mut copies = Vec::new();
+        for &s in seqs {
+            let (have, want) = ((self.lens[s] + self.page - 1) / self.page, (self.lens[s] + rows + self.page - 1) / self.page);
+            if self.lens[s] % self.page != 0 {
+                let old = self.rows[s * self.max_pages + have - 1] as usize;
+                if self.refs[old] > 1 {
+                    self.refs[old] -= 1;
+                    let new = self.take();
+                    self.rows[s * self.max_pages + have - 1] = new as i32;
+                    copies.push((old, new));
+                }
+            }
+            for i in have..want {
+                self.rows[s * self.max_pages + i] = self.take() as i32;
+            }
+            self.lens[s] += rows;
+        }
+        copies
+    }
+
+    /// Releases the pages wholly past `len`.
+    pub fn truncate(&mut self, seq: usize, len: usize) {
+        assert!(seq < self.max_seqs && len <= self.lens[seq] && len >= self.behind[seq], "PageTable::truncate: sequence {} to length {}", seq, len);
+        for i in (len + self.page - 1) / self.page..(self.lens[seq] + self.page - 1) / self.page {
+            let p = self.rows[seq * self.max_pages + i];
+            if p >= 0 {
+                self.unref(p as usize);
+                self.rows[seq * self.max_pages + i] = -1;
+            }
+        }
+        self.lens[seq] = len;
+    }
+
+    pub fn release(&mut self, seq: usize) {
+        assert!(seq < self.max_seqs, "PageTable::release: sequence id {}", seq);
+        for i in 0..self.max_pages {
+            let p = self.rows[seq * self.max_pages + i];
+            if p >= 0 {
+                self.unref(p as usize);
+                self.rows[seq * self.max_pages + i] = -1;
+            }
+        }
+        self.lens[seq] = 0;
+        self.behind[seq] = 0;
+    }
+
+    /// `dst` must be empty: it shares every page of `src` by reference count and takes its length.
+    pub fn fork(&mut self, src: usize, dst: usize) {
+        assert!(src < self.max_seqs && dst < self.max_seqs && src != dst, "PageTable::fork: sequence ids {} -> {}", src, dst);
+        assert!(self.lens[dst] == 0 && self.behind[dst] == 0, "PageTable::fork: sequence {} is not empty", dst);
+        for i in 0..self.max_pages {
+            let p = self.rows[src * self.max_pages + i];
+            self.rows[dst * self.max_pages + i] = p;
+            if p >= 0 {
+                self.refs[p as usize] += 1;
+            }
+        }
+        self.lens[dst] = self.lens[src];
+        self.behind[dst] = self.behind[src];
+    }
+
+    /// Releases the pages wholly below `pos`: how a windowed layer bounds its memory.
+    pub fn release_behind(&mut self, seq: usize, pos: usize) {
+        assert!(seq < self.max_seqs && pos <= self.lens[seq], "PageTable::release_behind: sequence {} below {}", seq, pos);
+        for i in 0..pos / self.page {
+            let p = self.rows[seq * self.max_pages + i];
+            if p >= 0 {
+                self.unref(p as usize);
+                self.rows[seq * self.max_pages + i] = -1;
+            }
+        }
+        self.behind[seq] = self.behind[seq].max(pos / self.page * self.page);
+    }
+
+    pub fn reset(&mut self) {
+        *self = Self::new(self.num_pages, self.page, self.max_seqs, self.max_pages);
+    }
+}
+
+/// A paged key / value cache (ours; the tested mirror is `nn::PagedKvCache` in `host/neuronika.hpp`): the pools, a `PageTable`
+/// and the decode scratch.
+pub struct PagedKvCache {
+    pub buffers: PagedBuffers,
+    pub table: RefCell<PageTable>,
+}
+
+impl PagedKvCache {
+    pub fn new(num_pages: usize, page: usize, kv_heads: usize, head_dim: usize, max_seqs: usize, max_pages: usize, device: &Device) -> Self {
+        Self { buffers: PagedBuffers::new(num_pages, page, kv_heads, head_dim, max_pages, device),
+               table: RefCell::new(PageTable::new(num_pages, page, max_seqs, max_pages)) }
+    }
+
+    pub fn lens(&self) -> Vec<usize> {
+        self.table.borrow().lens().to_vec()
+    }
+}
+
+impl MultiheadAttention {
+    /// `forward_step` over a paged cache: the batch is `seqs.len()`, any subset of the cache's sequences in any order.  The pages
+    /// of the step are reserved here, when the graph is built; the node's forward runs the page copies, the append and
+    /// `nk_attention_decode_paged_fwd` with the layer's `window`.  Like `forward_step`, always on the decode kernels.
+    pub fn forward_step_paged(&self, input: HipVar<Ix2>, seqs: &[usize], cache: &PagedKvCache) -> HipVar<Ix2> {
+        assert!(self.causal, "MultiheadAttention::forward_step is the incremental form of the causal forward");
+        assert!(!self.dropout.status.get() || self.dropout.p == 0., "MultiheadAttention::forward_step: dropout is active, call eval() first");
+        let (rows, batch) = (input.shape()[0], seqs.len());
+        assert!(batch > 0 && rows > 0 && rows % batch == 0, "MultiheadAttention: rows must be a multiple of the number of sequences");
+        let dh = self.d_model / self.heads;
+        let (_, ch, _, cd, max_pages) = cache.buffers.geometry();
+        assert!((ch, cd) == (self.kv_heads, dh), "MultiheadAttention::forward_step: the cache holds {} heads, the layer has {} kv heads", ch, self.kv_heads);
+        let mut table = cache.table.borrow_mut();
+        assert!(seqs.iter().all(|&s| s < table.max_seqs), "MultiheadAttention::forward_step: a sequence id is out of range");
+        let start: Vec<usize> = seqs.iter().map(|&s| table.lens()[s]).collect();
+        for (&s, &l) in seqs.iter().zip(start.iter()) {
+            let behind = table.behind(s);
+            assert!(behind == 0 || (self.window > 0 && (l + 1).saturating_sub(self.window) >= behind),
+                    "MultiheadAttention::forward_step: sequence {} released the pages below {}: the window must stay above them", s, behind);
+        }
+        if let Some(r) = &self.rope {
+            assert!(r.table.head_dim() == dh && start.iter().all(|&l| l + rows / batch <= r.table.max_pos()),
+                    "MultiheadAttention::forward_step: rope does not fit the head size or the positions");
+        }
+        let copies = table.reserve(seqs, rows / batch);
+        let image: Vec<i32> = seqs.iter().flat_map(|&s| table.row(s).to_vec()).collect();
+        debug_assert!(image.len() == batch * max_pages);
+        let scale = 1. / (dh as f32).sqrt();
+        let packed = input.linear(self.qkv.weight.detached(), self.qkv.bias.detached(), false);
+        let packed = match &self.rope {
+            Some(r) => packed.rope_in_place(&r.table, batch, self.heads + self.kv_heads, Some(&start)),
+            None => packed,
+        };
+        let context = packed.packed_paged_decode_attention(&cache.buffers, self.heads, &start, &image, &copies, scale, self.window);
         context.linear(self.o.weight.detached(), self.o.bias.detached(), false)
     }
 }

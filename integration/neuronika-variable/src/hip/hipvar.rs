@@ -23,7 +23,7 @@ use super::{
         AvgPool, AvgPoolBackward, MaxPool, MaxPoolBackward,
         DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, RmsNorm, RmsNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
-        decode_chunk, decode_window_workspace, decode_workspace, PackedDecodeAttention,
+        decode_chunk, decode_paged_workspace, decode_window_workspace, decode_workspace, PackedDecodeAttention, PagedDecodeAttention,
         RepeatKv, RepeatKvBackward, RepeatKvGeometry, rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
         sample_stage_limit, Sample, SampleParams,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
@@ -650,6 +650,75 @@ impl HipVar<Ix2> {
         let op = PackedDecodeAttention::new(geometry, query_heads as i32, capacity as i32, window.min(i32::MAX as usize) as i32, buffers.rolling(), self.data,
                                             buffers.keys.clone(), buffers.values.clone(), start,
                                             buffers.workspace_for(rows, query_heads, window, &device), data.clone(), scale);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+}
+
+/// Device storage of a PAGED key / value cache (layout at `nk_attention_decode_paged_fwd` in `include/neuronika_hip.h`): the two
+/// pools `(num_pages, heads, page, dh)`, never initialised, and the decode scratch, regrown when a larger step first arrives.  The
+/// table and the lengths are the caller's (`neuronika_nn::hip::PagedKvCache`).
+pub struct PagedBuffers {
+    pub(crate) keys: Shared<HipArray<Ix4>>,
+    pub(crate) values: Shared<HipArray<Ix4>>,
+    workspace: RefCell<Option<Shared<HipArray<Ix1>>>>,
+    workspace_floats: Cell<usize>,
+    geometry: (usize, usize, usize, usize, usize), // num_pages, heads (kv heads), page, dh, max_pages
+}
+
+impl PagedBuffers {
+    pub fn new(num_pages: usize, page: usize, heads: usize, dh: usize, max_pages: usize, device: &Device) -> Self {
+        assert!(num_pages > 0 && heads > 0 && dh > 0 && max_pages > 0, "PagedBuffers: num_pages, heads, dh and max_pages must be positive");
+        assert!(page >= 16 && page.is_power_of_two(), "PagedBuffers: page must be a power of two and at least 16");
+        assert!(num_pages * heads * page * dh <= i32::MAX as usize, "PagedBuffers: one pool must fit 31 bits of elements");
+        let dim = ndarray::Dim([num_pages, heads, page, dh]);
+        Self { keys: shared(dim, device), values: shared(dim, device), workspace: RefCell::new(None), workspace_floats: Cell::new(0),
+               geometry: (num_pages, heads, page, dh, max_pages) }
+    }
+
+    /// `(num_pages, heads, page, dh, max_pages)`
+    pub fn geometry(&self) -> (usize, usize, usize, usize, usize) {
+        self.geometry
+    }
+
+    fn workspace_for(&self, batch: usize, rows: usize, query_heads: usize, window: usize, device: &Device) -> Shared<HipArray<Ix1>> {
+        let (_, _, page, dh, max_pages) = self.geometry;
+        let floats = decode_paged_workspace(batch, rows, query_heads, dh, max_pages, page, window);
+        if floats > self.workspace_floats.get() || self.workspace.borrow().is_none() {
+            *self.workspace.borrow_mut() = Some(shared(ndarray::Dim([floats]), device));
+            self.workspace_floats.set(floats);
+        }
+        self.workspace.borrow().as_ref().unwrap().clone()
+    }
+}
+
+impl HipVar<Ix2> {
+    /// `packed_decode_attention` over a paged cache: `start[b]` is sequence b's length before the step, `table` its `max_pages` page
+    /// ids per sequence (`-1`: none) AFTER the step's pages were reserved, `copies` the (old, new) page pairs to copy first.  One
+    /// upload; `nk_kv_pages_copy`, `nk_kv_pages_append`, `nk_attention_decode_paged_fwd` in the node's forward.
+    #[allow(clippy::too_many_arguments)]
+    pub fn packed_paged_decode_attention(self, buffers: &PagedBuffers, query_heads: usize, start: &[usize], table: &[i32], copies: &[(usize, usize)],
+                                         scale: f32, window: usize) -> HipVar<Ix2> {
+        let device = self.device();
+        let (num_pages, heads, page, dh, max_pages) = buffers.geometry();
+        let batch = start.len();
+        let total = self.data.borrow().dimension()[0];
+        assert!(batch > 0 && total % batch == 0 && total > 0, "packed_paged_decode_attention: rows must be a positive multiple of the batch");
+        assert!(table.len() == batch * max_pages, "packed_paged_decode_attention: one table row of max_pages ids per sequence");
+        assert!(query_heads >= heads && query_heads % heads == 0, "packed_paged_decode_attention: query_heads must be a multiple of the cache's heads");
+        assert!(self.data.borrow().dimension()[1] == (query_heads + 2 * heads) * dh,
+                "packed_paged_decode_attention: the input must be (rows, (query_heads + 2 * heads) * dh)");
+        let rows = total / batch;
+        assert!(start.iter().all(|&s| s + rows <= max_pages * page), "packed_paged_decode_attention: the step exceeds max_pages * page");
+        let mut cells: Vec<f32> = start.iter().map(|&s| f32::from_bits(s as u32)).collect();
+        cells.extend(table.iter().map(|&p| f32::from_bits(p as u32)));
+        cells.extend(copies.iter().map(|&(old, _)| f32::from_bits(old as u32)));
+        cells.extend(copies.iter().map(|&(_, new)| f32::from_bits(new as u32)));
+        let image = HipArray::from_slice(&cells, ndarray::Dim([cells.len()]), device.clone());
+        let geometry = Heads { batch: batch as i32, seq: rows as i32, heads: heads as i32, dh: dh as i32 };
+        let data = shared(ndarray::Dim([total, query_heads * dh]), &device);
+        let op = PagedDecodeAttention::new(geometry, query_heads as i32, page as i32, max_pages as i32, num_pages as i32, copies.len() as i32,
+                                           window.min(i32::MAX as usize) as i32, self.data, buffers.keys.clone(), buffers.values.clone(), image,
+                                           buffers.workspace_for(batch, rows, query_heads, window, &device), data.clone(), scale);
         HipVar::node(data, Rc::new(op), self.history)
     }
 }

@@ -12,7 +12,7 @@ pub use {
     device::Device,
     dp::{Communicator, GradientSync, SyncEntry},
     hiparray::HipArray,
-    hipvar::{manual_seed, Gate, HipVar, HipVarDiff, KvBuffers, PaddingMode, RotaryTable, SamplerState},
+    hipvar::{manual_seed, Gate, HipVar, HipVarDiff, KvBuffers, PaddingMode, PagedBuffers, RotaryTable, SamplerState},
     optimizer::AdamW,
     optimizer::SGD,
 };

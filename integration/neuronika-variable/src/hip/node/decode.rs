@@ -100,3 +100,73 @@ impl Forward for PackedDecodeAttention {
         }
     }
 }
+
+/// Floats of scratch `nk_attention_decode_paged_fwd` needs (`nk_attention_decode_paged_workspace`): the contiguous forms' at the
+/// virtual capacity `max_pages * page`, or at the window.
+pub(crate) fn decode_paged_workspace(batch: usize, rows: usize, heads: usize, dh: usize, max_pages: usize, page: usize, window: usize) -> usize {
+    unsafe {
+        ffi::nk_attention_decode_paged_workspace(batch as i32, rows as i32, heads as i32, dh as i32, max_pages as i32, page as i32,
+                                                 window.min(i32::MAX as usize) as i32)
+    }
+}
+
+/// `PackedDecodeAttention` over a PAGED cache (semantics at `nk_attention_decode_paged_fwd` in `include/neuronika_hip.h`): `keys` /
+/// `values` are the pools `(num_pages, heads, page, dh)`; `image` holds, in one upload of int32 in f32 cells, the `batch` start
+/// positions, the `(batch, max_pages)` table rows and the `copies` (src | dst) page ids.  The forward runs the page copies
+/// (`nk_kv_pages_copy`), then the append (`nk_kv_pages_append`), then the attention; running it again repeats the same writes.
+pub(crate) struct PagedDecodeAttention {
+    geometry: Heads, // `seq` = new rows per sequence, `heads` = kv heads
+    query_heads: i32,
+    page: i32,
+    max_pages: i32,
+    num_pages: i32,
+    copies: i32,
+    window: i32, // 0: off
+    packed: Shared<HipArray<Ix2>>,
+    keys: Shared<HipArray<Ix4>>,
+    values: Shared<HipArray<Ix4>>,
+    image: HipArray<Ix1>,
+    workspace: Shared<HipArray<Ix1>>,
+    data: Shared<HipArray<Ix2>>,
+    scale: f32,
+}
+
+impl PagedDecodeAttention {
+    #[allow(clippy::too_many_arguments)]
+    pub(crate) fn new(geometry: Heads, query_heads: i32, page: i32, max_pages: i32, num_pages: i32, copies: i32, window: i32,
+                      packed: Shared<HipArray<Ix2>>, keys: Shared<HipArray<Ix4>>, values: Shared<HipArray<Ix4>>, image: HipArray<Ix1>,
+                      workspace: Shared<HipArray<Ix1>>, data: Shared<HipArray<Ix2>>, scale: f32) -> Self {
+        Self { geometry, query_heads, page, max_pages, num_pages, copies, window, packed, keys, values, image, workspace, data, scale }
+    }
+}
+
+impl Forward for PagedDecodeAttention {
+    fn forward(&self) {
+        let qkv = self.packed.borrow();
+        let (mut kp, mut vp) = (self.keys.borrow_mut(), self.values.borrow_mut());
+        let mut ws = self.workspace.borrow_mut();
+        let mut out = self.data.borrow_mut();
+        let h = self.geometry;
+        let (d, dkv) = ((self.query_heads * h.dh) as usize, (h.heads * h.dh) as usize);
+        let ld = (d + 2 * dkv) as i32;
+        let start = self.image.as_ptr() as *const i32;
+        let table = unsafe { start.add(h.batch as usize) };
+        let pairs = unsafe { table.add((h.batch * self.max_pages) as usize) };
+        let dev = qkv.device().as_raw();
+        if self.copies > 0 {
+            ffi::check(unsafe {
+                ffi::nk_kv_pages_copy(dev, kp.as_mut_ptr(), vp.as_mut_ptr(), pairs, pairs.add(self.copies as usize), self.copies, h.heads, h.dh,
+                                      self.page, self.num_pages)
+            });
+        }
+        ffi::check(unsafe {
+            ffi::nk_kv_pages_append(dev, kp.as_mut_ptr(), vp.as_mut_ptr(), qkv.as_ptr().add(d), qkv.as_ptr().add(d + dkv), ld, start, table,
+                                    self.max_pages, h.batch, h.seq, h.heads, h.dh, self.page, self.num_pages)
+        });
+        ffi::check(unsafe {
+            ffi::nk_attention_decode_paged_fwd(dev, qkv.as_ptr(), ld, kp.as_ptr(), vp.as_ptr(), start, table, self.max_pages, out.as_mut_ptr(),
+                                               ws.as_mut_ptr(), h.batch, h.seq, self.query_heads, h.heads, h.dh, self.page, self.num_pages,
+                                               self.window, self.scale)
+        });
+    }
+}

@@ -240,6 +240,11 @@ _SIGS = {
                                        C.c_float],
     "nk_attention_decode_window_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_kv_cache_append_ring": [VP, VP, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_kv_pages_append": [VP, VP, VP, VP, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_kv_pages_copy": [VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_attention_decode_paged_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_attention_decode_paged_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_float],
     "nk_rope_table": [VP, VP, C.c_int, C.c_int, C.c_double],
     "nk_rope_fwd": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_rope_bwd": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
@@ -286,6 +291,7 @@ _SIGS = {
 }
 _RESTYPES = {"nk_last_error": C.c_char_p, "nk_version": C.c_char_p, "nk_stream_compute": VP, "nk_stream_comm": VP,
              "nk_attention_decode_workspace": C.c_size_t, "nk_attention_decode_window_workspace": C.c_size_t,
+             "nk_attention_decode_paged_workspace": C.c_size_t,
              "nk_gemm_buffer_records": C.c_longlong, "nk_attention_band_scratch": C.c_size_t, "nk_attention_band_mask_words": C.c_size_t}
 EXPORTED = tuple(_SIGS)
 
@@ -1072,6 +1078,30 @@ def attention_decode_window_fwd(dev, Q, ldq, Kc, Vc, start, out, workspace, B, T
     to cap.  workspace: `attention_decode_window_workspace(B, T, H, dh, window)` floats."""
     check(lib.nk_attention_decode_window_fwd(dev.h, _p(Q), ldq, _p(Kc), _p(Vc), _p(start), _p(out), _p(workspace), B, T, H, Hkv, dh, cap,
                                              window, int(ring), scale))
+
+
+def kv_pages_append(dev, Kp, Vp, K, V, ld, start, table, max_pages, B, T, H, dh, page, num_pages):
+    """Row b*T + t of K / V goes to position start[b] + t of the (num_pages, H, page, dh) pools, through the device int32
+    (B, max_pages) table: page table[b, p // page], slot p % page.  Rows past max_pages * page, or behind an entry outside the pool,
+    are dropped."""
+    check(lib.nk_kv_pages_append(dev.h, _p(Kp), _p(Vp), _p(K), _p(V), ld, _p(start), _p(table), max_pages, B, T, H, dh, page, num_pages))
+
+
+def kv_pages_copy(dev, Kp, Vp, src, dst, n, H, dh, page, num_pages):
+    """Whole pages src[i] -> dst[i] (device int32 arrays of n ids), every head, K and V, in one launch."""
+    check(lib.nk_kv_pages_copy(dev.h, _p(Kp), _p(Vp), _p(src), _p(dst), n, H, dh, page, num_pages))
+
+
+def attention_decode_paged_workspace(B, T, H, dh, max_pages, page, window) -> int:
+    """Floats of caller-owned scratch nk_attention_decode_paged_fwd needs: the contiguous forms' at cap = max_pages * page."""
+    return int(lib.nk_attention_decode_paged_workspace(B, T, H, dh, max_pages, page, window))
+
+
+def attention_decode_paged_fwd(dev, Q, ldq, Kp, Vp, start, table, max_pages, out, workspace, B, T, H, Hkv, dh, page, num_pages, window, scale):
+    """Decode over a paged cache: the bits of `attention_decode_gqa_fwd` (window == 0) or `attention_decode_window_fwd` with
+    ring = 0 on the cache gathered through the table.  workspace: `attention_decode_paged_workspace(...)` floats."""
+    check(lib.nk_attention_decode_paged_fwd(dev.h, _p(Q), ldq, _p(Kp), _p(Vp), _p(start), _p(table), max_pages, _p(out), _p(workspace), B, T, H,
+                                            Hkv, dh, page, num_pages, window, scale))
 
 
 def repeat_kv_fwd(dev, x, ldx, y, ldy, rows, Hkv, G, dh):

@@ -5,7 +5,8 @@
 // Memory-bound, no MFMA: a query row reads its cached keys and values once, straight into registers with 16-byte loads (no LDS
 // staging: nothing is shared between waves, cdna_hip_programming.md "GEMV / M <= 16" and "Attention decode").
 // The three forms are three kernel SIGNATURES per family - the kernel-argument layout is part of the machine code - around ONE body
-// each, included textually and switched by compile-time constants (grouped indexing, window and slots, heads per block):
+// each, included textually and switched by compile-time constants (grouped indexing, window and slots, heads per block, and
+// ADEC_PAGED, 0 in this header: the paged signatures around the same bodies are in nk_attention_decode_paged.h):
 // nk_attention_decode_body.h for the vector partial kernels, nk_attention_decode_generic_body.h for the generic ones,
 // nk_attention_decode_combine_body.h for the combine; the append is one function template with a ring flag, below.  So the bit
 // contracts are structural: the grouped result is the plain result, the windowed result at n <= W is both, and the bits of a
@@ -124,7 +125,9 @@ __global__ void __launch_bounds__(ADEC_THREADS) adec_partial_kernel(const float*
 #define ADEC_GROUPED 0
 #define ADEC_NH 1
 #define ADEC_WINDOW 0
+#define ADEC_PAGED 0
 #include "nk_attention_decode_body.h"
+#undef ADEC_PAGED
 #undef ADEC_GROUPED
 #undef ADEC_NH
 #undef ADEC_WINDOW
@@ -138,7 +141,9 @@ __global__ void __launch_bounds__(ADEC_THREADS) adec_gqa_partial_kernel(const fl
 #define ADEC_GROUPED 1
 #define ADEC_NH ADEC_GQA_HEADS
 #define ADEC_WINDOW 0
+#define ADEC_PAGED 0
 #include "nk_attention_decode_body.h"
+#undef ADEC_PAGED
 #undef ADEC_GROUPED
 #undef ADEC_NH
 #undef ADEC_WINDOW
@@ -153,7 +158,9 @@ __global__ void __launch_bounds__(ADEC_THREADS) adw_partial_kernel(const float* 
 #define ADEC_GROUPED 1
 #define ADEC_NH NH
 #define ADEC_WINDOW 1
+#define ADEC_PAGED 0
 #include "nk_attention_decode_body.h"
+#undef ADEC_PAGED
 #undef ADEC_GROUPED
 #undef ADEC_NH
 #undef ADEC_WINDOW
@@ -166,7 +173,9 @@ __global__ void __launch_bounds__(ADEC_THREADS) adec_generic_kernel(const float*
                                                                     int cap, int nchunks, float c1, int lpk) {
 #define ADEC_GROUPED 0
 #define ADEC_WINDOW 0
+#define ADEC_PAGED 0
 #include "nk_attention_decode_generic_body.h"
+#undef ADEC_PAGED
 #undef ADEC_GROUPED
 #undef ADEC_WINDOW
 }
@@ -177,7 +186,9 @@ __global__ void __launch_bounds__(ADEC_THREADS) adec_gqa_generic_kernel(const fl
                                                                         int dh, int cap, int nchunks, float c1, int lpk) {
 #define ADEC_GROUPED 1
 #define ADEC_WINDOW 0
+#define ADEC_PAGED 0
 #include "nk_attention_decode_generic_body.h"
+#undef ADEC_PAGED
 #undef ADEC_GROUPED
 #undef ADEC_WINDOW
 }
@@ -188,7 +199,9 @@ __global__ void __launch_bounds__(ADEC_THREADS) adw_generic_kernel(const float* 
                                                                    int cap, int W, int ring, int nchunks, float c1, int lpk) {
 #define ADEC_GROUPED 1
 #define ADEC_WINDOW 1
+#define ADEC_PAGED 0
 #include "nk_attention_decode_generic_body.h"
+#undef ADEC_PAGED
 #undef ADEC_GROUPED
 #undef ADEC_WINDOW
 }

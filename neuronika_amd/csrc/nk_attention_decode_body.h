@@ -1,6 +1,6 @@
 // The body of the vector partial kernels of single-query attention (nk_attention_decode.h says what they compute).  No kernel of its
 // own and no include guard: it is included INSIDE the signatures of adec_partial_kernel<DH>, adec_gqa_partial_kernel<DH> and
-// adw_partial_kernel<DH, NH>, so the three are one body by construction - the bits of a head's result are the same in all three
+// adw_partial_kernel<DH, NH> (and of the paged adp_partial_kernel / adpw_partial_kernel<DH, NH>), so they are one body by construction - the bits of a head's result are the same in all three
 // whenever its keys are, and a change to the arithmetic is made once.  (A force-inlined function called from the three moved their
 // register allocation; a textual body does not - profiles/attention_decode_isa_identity.md.)  The includer defines, and undefines
 // after the include:
@@ -10,7 +10,11 @@
 //   ADEC_WINDOW   0: positions j < n count, position j lives at slot j, blockIdx.y is the chunk; argument nchunks.
 //                 1: positions lo <= j < n count, position j lives at slot s0 + (j - lo) wrapped at cap, blockIdx.y counts the chunks
 //                    from lo / C; arguments W and ring, and nchunks is the number of chunks a window can touch.
-// The forms differ in four places, marked (1) - (4); everything else - the loads, dot, xor-shuffles, chunk maximum, exp2, the groups
+//   ADEC_PAGED    0: the cache is one (B, Hkv, cap, dh) slab, slot s of the block's kv head at base + s * LPK.
+//                 1: (nk_attention_decode_paged.h) pools of pages (num_pages, Hkv, page, dh) and a table: position p is in page
+//                    table[b*max_pages + (p >> psh)], clamped to np1 = num_pages - 1, at slot p & (page - 1); arguments table,
+//                    max_pages, psh, np1, and cap is the virtual capacity max_pages << psh.
+// The forms differ in five places, marked (1) - (5); everything else - the loads, dot, xor-shuffles, chunk maximum, exp2, the groups
 // in order, the write of o / ls or of the partial - is stated once.
     constexpr int LPK = DH / 4, G = ADEC_THREADS / LPK, C = G * ADEC_KPG;
     static_assert(C == adec_chunk_of(DH), "chunk");
@@ -71,12 +75,31 @@
 #if !ADEC_GROUPED
     ADEC_Q(h0);
 #endif
+    // (5) where a position's row is in memory: at base + slot * LPK of one slab, or in the page the sample's table row names
+#if !ADEC_PAGED
     const size_t base = ((size_t)b * Hkv + kvh) * cap * LPK + sub;
+#endif
     float4 kk[ADEC_KPG], vv[ADEC_KPG];
+#if ADEC_PAGED
+    // the 16 table entries first, then the 16 + 16 loads they address: one dependent-load latency per chunk.  Only positions that
+    // count (or n - 1) are looked up; the entry is clamped into the pool
+    const int* __restrict__ trow = table + (size_t)b * max_pages;
+    unsigned at[ADEC_KPG];
+#pragma unroll
+    for (int i = 0; i < ADEC_KPG; ++i) at[i] = (unsigned)trow[ADEC_AT(i) >> psh];
+#pragma unroll
+    for (int i = 0; i < ADEC_KPG; ++i)
+        at[i] = ((((at[i] < np1 ? at[i] : np1) * Hkv + kvh) << psh) + (ADEC_AT(i) & ((1 << psh) - 1))) * LPK + sub;
+#pragma unroll
+    for (int i = 0; i < ADEC_KPG; ++i) kk[i] = Kc[at[i]];
+#pragma unroll
+    for (int i = 0; i < ADEC_KPG; ++i) vv[i] = Vc[at[i]];
+#else
 #pragma unroll
     for (int i = 0; i < ADEC_KPG; ++i) kk[i] = Kc[base + (size_t)ADEC_AT(i) * LPK];
 #pragma unroll
     for (int i = 0; i < ADEC_KPG; ++i) vv[i] = Vc[base + (size_t)ADEC_AT(i) * LPK];
+#endif
 #if ADEC_GROUPED
 #pragma unroll 1
     for (int hq = 0; hq < nh; ++hq)  // head by head over the registers above

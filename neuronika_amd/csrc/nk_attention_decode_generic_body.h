@@ -1,9 +1,10 @@
 // The body of the generic kernels of single-query attention (any dh but 32 / 64 / 128; nk_attention_decode.h says what they compute).
 // No kernel of its own and no include guard: it is included INSIDE the signatures of adec_generic_kernel, adec_gqa_generic_kernel and
-// adw_generic_kernel, as nk_attention_decode_body.h is inside the vector kernels'.  One block per (b, t, h) in all three; nothing is
+// adw_generic_kernel (and of the paged adp_generic_kernel / adpw_generic_kernel), as nk_attention_decode_body.h is inside the vector kernels'.  One block per (b, t, h) in all three; nothing is
 // shared between the heads of a group.  The includer defines, and undefines after the include:
 //   ADEC_GROUPED  1: the cache has Hkv heads and query head h reads head h / (H / Hkv); argument Hkv.  0: head h.
 //   ADEC_WINDOW   as in nk_attention_decode_body.h: arguments W and ring, and nchunks counts the chunks a window can touch.
+//   ADEC_PAGED    as in nk_attention_decode_body.h: 0 one slab, 1 pages behind a table (arguments table, max_pages, psh, np1).
     constexpr int C = ADEC_CHUNK_GENERIC;
     static_assert(C == ADEC_THREADS, "one key per thread");
     __shared__ float sc[C];
@@ -47,14 +48,24 @@
     const int s0 = ring ? lo % cap : lo;  // the slot of position lo
 #endif
     const float* __restrict__ qp = Q + (size_t)row * ldq + (size_t)h * dh;
+    // where slot s of the block's kv head starts: in one slab, or in the page the sample's table row names (the entry clamped into
+    // the pool; only slots of positions that count, or of n - 1, are looked up)
+#if ADEC_PAGED
+    const int* __restrict__ trow = table + (size_t)b * max_pages;
+    const unsigned kvh = h / (H / Hkv);
+#define ADEC_ROW(s) \
+    (((((size_t)((unsigned)trow[(s) >> psh] < np1 ? (unsigned)trow[(s) >> psh] : np1) * Hkv + kvh) << psh) + ((s) & ((1 << psh) - 1))) * dh)
+#else
+#define ADEC_ROW(s) base + (size_t)(s) * dh  // unparenthesised: Kc + base + ..., the association the three kernels were compiled with
 #if ADEC_GROUPED
     const size_t base = ((size_t)b * Hkv + h / (H / Hkv)) * cap * dh;
 #else
     const size_t base = ((size_t)b * H + h) * cap * dh;
 #endif
+#endif
     for (int i = 0; i < lpk; ++i) {
         const int j = c0 + i * G + g, r = ADEC_REL(j);
-        const float* __restrict__ kr = Kc + base + (size_t)ADEC_AT(r) * dh;
+        const float* __restrict__ kr = Kc + ADEC_ROW(ADEC_AT(r));
         float d = 0.f;
         for (int e = sub; e < dh; e += lpk) d = __builtin_fmaf(qp[e], kr[e], d);
         for (int off = lpk >> 1; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
@@ -75,7 +86,7 @@
         if (e < dh)
             for (int i = 0; i < lpk; ++i) {
                 const int jl = i * G + g, j = c0 + jl, r = ADEC_REL(j);
-                acc = __builtin_fmaf(sc[jl], Vc[base + (size_t)ADEC_AT(r) * dh + e], acc);
+                acc = __builtin_fmaf(sc[jl], Vc[ADEC_ROW(ADEC_AT(r)) + e], acc);
             }
         ro[tid] = acc;  // ro[g * lpk + sub]
         __syncthreads();
@@ -96,4 +107,5 @@
 #undef ADEC_IN
 #undef ADEC_REL
 #undef ADEC_AT
+#undef ADEC_ROW
 #undef ADEC_SINGLE

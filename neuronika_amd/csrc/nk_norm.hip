@@ -13,6 +13,7 @@
 #include "nk_activation.h"
 #include "nk_optim_multi.h"
 #include "nk_attention_decode.h"
+#include "nk_attention_decode_paged.h"
 #include "nk_attention_band.h"
 #include "nk_repeat_kv.h"
 #include "nk_rope.h"
