@@ -45,7 +45,7 @@ def _device_run(dev, c, x, g, gamma, beta, assign, init, eps=EPS):
 
 
 ROWS = (1, 3, 64, 1000, 4097)
-DS = (1, 2, 3, 4, 5, 31, 64, 100, 256, 768, 1024, 1027, 2048, 4096, 8192, 16384, 20000)
+DS = (1, 2, 3, 4, 5, 31, 64, 100, 256, 260, 512, 768, 1024, 1027, 2048, 2052, 4096, 8192, 16384, 20000)
 # the product, thinned: every D at 3 and 64 rows, the other row counts at the D that change the kernel or the row split
 EXTRA = {1: (1, 4, 1027, 16384), 1000: (5, 64, 768, 1024, 2048, 4096, 20000), 4097: (3, 256, 1024, 1027, 4096)}
 GRID = [(r, D) for D in DS for r in ROWS if r in (3, 64) or D in EXTRA[r]]

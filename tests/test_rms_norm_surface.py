@@ -85,16 +85,49 @@ def test_kernels_sit_beside_the_layernorm_family():
     mine = {k for k in luk.source_kernels("nk_norm.hip") if k.startswith("rms_norm_")}
     assert mine == {"rms_norm_fwd_kernel", "rms_norm_bwd_kernel", "rms_norm_fwd_general_kernel", "rms_norm_bwd_general_kernel",
                     "rms_norm_gamma_partial_kernel", "rms_norm_gamma_final_kernel"}
-    src = re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", "nk_norm.hip"))
-    rms = src[src.index("void rms_norm_fwd_kernel"):src.index("\n}  \n\nextern")]
-    assert "atomic" not in rms.lower() and "hipMemset" not in rms and "hipMalloc" not in rms and "Synchronize" not in rms
-    assert "nk_workspace(" in rms and "nk_streams_past_cache(" in rms
+    def text(f):
+        return re.sub(r"//[^\n]*", "", _read("neuronika_amd", "csrc", f))
+
+    # each family's statements stand once, in a body header that defines no kernel and that both norms' kernels include
+    bodies = sorted(f for f in os.listdir(luk.CSRC) if re.fullmatch(r"nk_norm_\w+_body\.h", f))
+    assert len(bodies) == 6 and set(bodies) <= set(luk.unit_sources("nk_norm.hip"))
+    assert not any(luk.file_kernels(os.path.join(luk.CSRC, f)) for f in bodies)
+    src = text("nk_norm.hip")
+    norm = src + "".join(text(f) for f in bodies)                  # the norm unit's own code: kernels, bodies and host paths
+    assert "atomic" not in norm.lower() and "hipMemset" not in norm and "hipMalloc" not in norm and "Synchronize" not in norm
+    assert "nk_workspace(" in norm and "nk_streams_past_cache(" in norm
+
+    def expanded(name):
+        """what the compiler sees of one kernel: the body header in place of its #include, `#if NORM_CENTRED` evaluated with the
+        value the kernel defines"""
+        k = src[src.index("void %s(" % name):]
+        k = k[:k.index("\n}\n")]
+        (centred,) = re.findall(r"^#define NORM_CENTRED ([01])$", k, re.M)
+        (header,) = re.findall(r'^\s*#include "(nk_norm_\w+_body\.h)"$', k, re.M)
+        k = k.replace('#include "%s"' % header, text(header))
+        out, on = [], [True]
+        for line in k.split("\n"):
+            word = line.strip()
+            if word.startswith("#if"):
+                assert word == "#if NORM_CENTRED", word               # the one switch, so that nothing is evaluated wrongly here
+                on.append(on[-1] and centred == "1")
+            elif word == "#else":
+                on[-1] = on[-2] and not on[-1]
+            elif word == "#endif":
+                on.pop()
+            elif on[-1]:
+                out.append(line)
+        assert on == [True], name
+        return "\n".join(out)
+
     # one reduction forward, one backward, no mean: the row-in-registers kernels and the general ones each call owner_sum once
     for name in ("rms_norm_fwd_kernel", "rms_norm_bwd_kernel", "rms_norm_fwd_general_kernel", "rms_norm_bwd_general_kernel"):
-        body = rms[rms.index("void %s(" % name):]
-        body = body[:body.index("\n}\n")]
+        body = expanded(name)
         assert body.count("owner_sum<") == 1, name
         assert "mean" not in body and "sub4" not in body, name
+    # and the switch at 1 selects the centred branch: LayerNorm's dx has the second reduction
+    for name in ("layer_norm_bwd_kernel", "layer_norm_bwd_general_kernel"):
+        assert expanded(name).count("owner_sum<") == 2, name
     assert not [f for f in os.listdir(luk.CSRC) if f.endswith(".hip") and "rms" in f]   # no new translation unit
 
 
