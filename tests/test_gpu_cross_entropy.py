@@ -7,18 +7,10 @@ import numpy as np
 import pytest
 
 import cross_entropy_oracle as X
+from cross_entropy_rows import family, ownership
 from test_gpu_embedding import Guarded, same_bits
 
 pytestmark = pytest.mark.gpu
-
-
-def family(C, inner, together=True):
-    """the dispatch rule of include/neuronika_hip.h, restated"""
-    if inner > 1 or not together:
-        return "generic"
-    if C <= 2048:
-        return "row%d" % (1 if C <= 256 else 2 if C <= 512 else 4 if C <= 1024 else 8)
-    return "block%d" % (256 if C <= 16384 else 512 if C <= 65536 else 1024)
 
 
 def run_all(dev, x, t, red, ignore=-1, eps=0.0, g=1.0, dx0=None, lead=4, lead_dx=None):
@@ -45,7 +37,8 @@ def check_case(dev, x, t, red, ignore=-1, eps=0.0, g=0.75, lead=4, lead_dx=None,
     _, on = X.active_mask(t, C, ignore)
     count = int(on.sum())
     w = (1.0 / count if count else 0.0) if red == "mean" else 1.0
-    b = X.bounds(C, float(np.abs(x).max()) if x.size else 0.0, t.size, eps, g, w)
+    finite = np.abs(x[np.isfinite(x)])
+    b = X.bounds(C, float(finite.max()) if finite.size else 0.0, t.size, eps, g, w)
     assert np.abs(lse - want_lse).max() <= b["lse"], ("lse", np.abs(lse - want_lse).max(), b["lse"])
     assert abs(out - want_loss) <= b["loss"] * (max(count, 1) if red == "sum" else 1), ("loss", out, want_loss)
     want = X.backward(x, t, want_lse, g, red, ignore, eps)
@@ -176,22 +169,34 @@ def composed(dev, x, t, red, g):
     return OUT.item(), DX.numpy()
 
 
-@pytest.mark.parametrize("shape", [(6, 10), (5, 3000)])
+@pytest.mark.parametrize("shape", [(6, 10), (5, 3000), (5, 4099), (3, 16385)])
 def test_non_finite_logits_follow_the_composed_device_path(dev, shape):
-    """-inf is ordinary; a NaN or +inf logit gives the NaN pattern of log_softmax + nll on this library"""
+    """-inf is ordinary; a NaN or +inf logit gives the NaN pattern of log_softmax + nll on this library.  At C = 4099 and 16385 the
+    block kernels run their four-quad trip (C = 3000: nb = 750 < 3 * 256, the partial trip alone): there each row's first non-finite
+    value sits in slot u = 3 of a full trip (cross_entropy_rows.ownership)."""
     x, t = make(6, shape)
-    x[0, 2] = -np.inf; x[1, 3] = np.nan; x[2, 0] = np.inf; x[3, 1] = -np.inf; x[3, 7] = -np.inf
-    t[:4] = [1.0, 0.0, 2.0, 5.0]
+    N, C = shape
+
+    def at(r, c):
+        own = ownership(family(C, 1), C, (r * C) % 4)
+        slot3 = np.flatnonzero(own.full & (own.u == 3))
+        return int(slot3[slot3.size // 2 + c]) if slot3.size else c
+
+    c0 = at(0, 2)
+    x[0, c0] = -np.inf; x[1, at(1, 3)] = np.nan; x[2, at(2, 0)] = np.inf
+    if N > 3:
+        x[3, 1] = -np.inf; x[3, 7] = -np.inf
+    t[:min(N, 4)] = [1.0, 0.0, 2.0, 5.0][:min(N, 4)]
     out, lse, _, da = run_all(dev, x, t, "sum", g=1.0)
     cout, cdx = composed(dev, x, t, "sum", 1.0)
     assert np.isnan(out) and np.isnan(cout)
     assert np.isnan(lse[1]) and np.isnan(lse[2]) and np.isfinite(np.delete(lse, [1, 2])).all()
     assert np.array_equal(np.isnan(da), np.isnan(cdx)) and np.array_equal(np.isinf(da), np.isinf(cdx))
-    assert np.isnan(da[1]).all() and np.isnan(da[2]).all() and da[0, 2] == 0.0
+    assert np.isnan(da[1]).all() and np.isnan(da[2]).all() and da[0, c0] == 0.0
     rest = np.delete(np.arange(shape[0]), [1, 2])
     b = X.bounds(shape[1], 20.0, shape[0])
     assert np.abs(da[rest] - cdx[rest]).max() <= 2 * b["dx"]
-    x[1, 3] = 0.0; x[2, 0] = 0.0                                   # with only -inf left everything is finite
+    x[1, at(1, 3)] = 0.0; x[2, at(2, 0)] = 0.0                     # with only -inf left everything is finite
     out, lse, _, da = run_all(dev, x, t, "sum", g=0.75)
     want_loss, want_lse = X.forward(x, t, "sum")
     b = X.bounds(shape[1], float(np.abs(x[np.isfinite(x)]).max()), shape[0], 0.0, 0.75)

@@ -490,6 +490,44 @@ def test_attn_probs(dev, L):
             assert same_bits(z, zr)
 
 
+@pytest.mark.parametrize("L", (4, 260, 1028, 2048), ids=lambda L: f"L{L}")               # V = 1, 2, 8, 8
+def test_attn_probs_extremes(dev, L):
+    """the max subtraction of the fused kernel and of the backward that recomputes from the scores, held against `_softmax_ref` as
+    test_softmax_extremes holds the plain kernels: test_attn_probs draws scaled scores in [-1, 1), where any shift - or none - gives
+    the same probabilities"""
+    c = capi()
+    rows, scale, seed, offset = 5, 0.125, 77, 5
+    s = np.empty((rows, L), np.float32)
+    s[0] = np.linspace(-1e4, 1e4, L, dtype=np.float32) / np.float32(scale)   # exp(x) alone would overflow / underflow
+    s[1] = 1e4 / scale                                                        # all equal, large
+    s[2] = -np.inf; s[2, L // 2] = 2.0 / scale                                # one live entry among -inf
+    s[3] = pattern(62, (L,), -3, 3) / np.float32(scale); s[3, 4:] -= np.float32(1e3 / scale)     # the maximum in the first lane only
+    s[4] = -1e4 / scale
+    y64 = _softmax_ref(False, s.astype(np.float64) * scale, 1)
+    assert np.isfinite(y64).all() and (L == 4 or y64[3, 4:].max() == 0.0)
+    S = put(dev, s)
+    lab = f"dispatch/attn_probs_extremes/L{L}"
+    P, Ow = Window(dev, (rows, L), np.nan), Window(dev, (rows, L), np.nan)
+    c.scale_softmax_dropout_fwd(dev, S, P.v, Ow.v, None, scale, 0.0, True, seed, offset)
+    probs, out = P.read(), Ow.read()
+    assert np.isfinite(probs).all(), lab
+    tolerance.assert_contraction(lab + "/probs", probs, y64, L, 1.0, float(y64.max()), epilogue=True)
+    assert same_bits(out, probs)
+    for r in (1, 4):
+        assert np.array_equal(probs[r], np.full(L, np.float32(1) / np.float32(L)))
+    assert probs[2, L // 2] == 1.0 and probs[2].sum() == 1.0
+    g = pattern(72, (rows, L), -1, 1)
+    G = put(dev, g)
+    inc = y64 * (g - (g * y64).sum(axis=1, keepdims=True)) * scale
+    zr = accumulate_forms(dev, (rows, L), lambda d, a: c.scale_softmax_dropout_bwd_from_scores(dev, d, G, S, None, scale, 0.0, True, seed, offset, assign=a),
+                          inc, lab + "/bwd_recompute", L, float(np.abs(g).max()), float(y64.max()))
+    Pk = put(dev, probs)
+    z = accumulate_forms(dev, (rows, L), lambda d, a: c.scale_softmax_dropout_bwd(dev, d, G, Pk, None, scale, 0.0, True, seed, offset, assign=a),
+                         probs.astype(np.float64) * (g - (g * probs.astype(np.float64)).sum(axis=1, keepdims=True)) * scale,
+                         lab + "/bwd", L, float(np.abs(g).max()), float(y64.max()))
+    assert same_bits(z, zr)
+
+
 # ======================================================================================================================
 # full reductions and their backward
 # ======================================================================================================================

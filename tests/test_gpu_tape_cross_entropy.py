@@ -181,3 +181,61 @@ def test_captured_step_equals_eager_step(nk, tdev):
     assert mg["loss"].item() == me["loss"].item() and np.isfinite(me["loss"].item())
     assert all((a != b).any() for a, b in zip(want, w0))
     del graph
+
+
+ROWS_C = 4099
+ROWS_KINDS = ("climbing", "falling", "lifted", "masked_inf", "peaked:slot3", "peaked:last_wave")
+
+
+def _shift_rows(masked="masked_inf"):
+    """(6, 4099) logits of tests/cross_entropy_rows.py - rows that move the running maximum of the block kernel, each at the offset
+    from a 16-byte boundary it has in an aligned leaf - and targets alternating between the row's maximum and its lowest live class"""
+    import cross_entropy_rows as R
+    kinds = tuple(masked if k == "masked_inf" else k for k in ROWS_KINDS)
+    made = [R.make_row(k, R.family(ROWS_C, 1), ROWS_C, (r * ROWS_C) % 4, 900 + r) for r, k in enumerate(kinds)]
+    x = np.stack([m[0] for m in made])
+    live = np.stack([m[1] for m in made])
+    hi, lo = np.where(live, x, -np.inf).argmax(1), np.where(live, x, np.inf).argmin(1)
+    return x, live, np.where(np.arange(len(kinds)) % 2 == 0, hi, lo).astype(np.float32)
+
+
+@pytest.mark.parametrize("red", ["Mean", "Sum"])
+def test_rows_that_move_the_running_maximum_through_the_tape(nk, tdev, red):
+    """nn::CrossEntropyLoss over a leaf of climbing, falling, lifted, masked and peaked rows: loss and leaf gradient against the f64
+    oracle within its bounds, finite throughout (the N(0, 2^2) logits of the tests above leave any shift, or none, unnoticed)"""
+    x, _, tgt = _shift_rows()
+    leaf = nk.from_ndarray(tdev, x).requires_grad()
+    loss = nk.nn.CrossEntropyLoss(getattr(nk.Reduction, red)).forward(leaf, nk.from_ndarray(tdev, tgt))
+    loss.forward(); loss.backward(1.0)
+    want_loss, lse = X.forward(x, tgt, red.lower())
+    want = X.backward(x, tgt, lse, 1.0, red.lower())
+    n = x.shape[0]
+    b = X.bounds(ROWS_C, float(np.abs(x[np.isfinite(x)]).max()), n, 0.0, 1.0, 1.0 / n if red == "Mean" else 1.0)
+    assert np.isfinite(want_loss) and want_loss > 100.0                    # the targets on low classes: a large finite loss
+    assert np.isfinite(loss.item()) and abs(loss.item() - want_loss) <= b["loss"] * (n if red == "Sum" else 1), (loss.item(), want_loss)
+    grad = leaf.grad()
+    assert np.isfinite(grad).all() and np.abs(grad - want).max() <= b["dx"], np.abs(grad - want).max()
+
+
+@pytest.mark.parametrize("ce_first", [True, False])
+def test_rows_that_move_the_running_maximum_with_a_second_consumer(nk, tdev, ce_first):
+    """as test_logits_with_a_second_consumer_accumulate, on the same rows (the mask value -1e9 in place of -inf, which a squared
+    error cannot take): whichever writer runs first assigns, the other adds"""
+    x, live, tgt = _shift_rows("masked_1e9")
+    noise = np.round(np.random.default_rng(5).standard_normal(x.shape) * 8.0) / 8.0
+    other = np.where(live, x.astype(np.float64) + noise, x).astype(np.float32)
+    diff = x.astype(np.float64) - other
+    assert np.array_equal(diff, np.where(live, -noise, 0.0))               # exact on the 1/8 grid
+    leaf = nk.from_ndarray(tdev, x).requires_grad()
+    ce = lambda: leaf.cross_entropy(nk.from_ndarray(tdev, tgt), nk.Reduction.Mean)
+    mse = lambda: leaf.mse(nk.from_ndarray(tdev, other), nk.Reduction.Sum)
+    total = ce() + mse() if ce_first else mse() + ce()
+    total.forward(); total.backward(1.0)
+    want_loss, lse = X.forward(x, tgt, "mean")
+    want = X.backward(x, tgt, lse, 1.0, "mean") + 2.0 * diff
+    n = x.shape[0]
+    b = X.bounds(ROWS_C, float(np.abs(x[live]).max()), n, 0.0, 1.0, 1.0 / n)
+    sq = (diff ** 2).sum()
+    assert abs(total.item() - (want_loss + sq)) <= b["loss"] + 1e-5 * sq
+    grad = leaf.grad()
+    assert np.isfinite(grad).all() and (np.abs(grad - want) <= b["dx"] + 2 * X.U * np.abs(want)).all()
