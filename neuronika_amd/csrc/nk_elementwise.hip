@@ -39,14 +39,15 @@ int check_bcast(const int* out_shape, int out_nd, const int* s, int nd, const ch
     return NK_OK;
 }
 
-// Collapse adjacent dims that are mergeable for every stride vector in `sts` (nvec vectors).
+// Collapse adjacent dims that are mergeable for every stride vector in `sts` (nvec vectors).  A merged extent stays an int: two dims
+// whose product is beyond 2^31 - 1 are left apart (the kernels walk them with 64-bit offsets either way).
 int collapse(const int* shape, int nd, long long** sts, int nvec, int* oshape) {
     int m = 0;
     for (int i = 0; i < nd; ++i) {
         if (shape[i] == 1) continue;  // drop unit dims
         bool merged = false;
         if (m > 0) {
-            bool ok = true;
+            bool ok = (long long)oshape[m - 1] * shape[i] <= 0x7fffffffLL;
             for (int v = 0; v < nvec; ++v) {
                 const long long prev = sts[v][m - 1], cur = sts[v][i];
                 if (!((prev == 0 && cur == 0) || (cur != 0 && prev == cur * shape[i]))) ok = false;
@@ -418,12 +419,17 @@ int bwd_dispatch(nk_device* dev, float* d, const int* t_shape, int t_nd, const f
         int ki = -1;
         for (int i = 0; i < nd; ++i) if (pat[i] == 1) ki = i;
         if (ki < 0) {  // everything reduced (scalar target): view the flat range as [R0][1][R1]
-            if (nd != 1) goto generic;  // o/q strides prevented merging into one flat range
+            // dims that collapse() left apart only to keep an extent inside an int are still one flat range; any other reason
+            // (o / q strides that do not merge) goes to the generic kernel
+            for (int i = 1; i < nd; ++i)
+                for (const long long* v : {os, qs})
+                    if (!((v[i - 1] == 0 && v[i] == 0) || (v[i] != 0 && v[i - 1] == v[i] * cshape[i]))) goto generic;
+            const long long eo = os[nd - 1], eq = qs[nd - 1];  // the element strides of the flat range
             long long r1 = 8192;
             while (r1 > 1 && total % r1 != 0) r1 >>= 1;
             if (total / r1 > 0x7fffffffLL) goto generic;
             p.R1 = (int)r1; p.R0 = (int)(total / r1);
-            p.os1 = os[0]; p.qs1 = qs[0]; p.os0 = os[0] * r1; p.qs0 = qs[0] * r1;
+            p.os1 = eo; p.qs1 = eq; p.os0 = eo * r1; p.qs0 = eq * r1;
         } else {
             if (ki > 1 || nd - 1 - ki > 1) goto generic;
             p.K = cshape[ki]; p.osk = os[ki]; p.qsk = qs[ki];

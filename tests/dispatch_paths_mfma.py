@@ -26,7 +26,9 @@ TRACE_SUMMARY = "profiles/r11_mfma_dispatch_paths_kernels.md"
 NOT_INVENTORIED = (
     ("nk_batchnorm.hip", "32 instantiations; tests/test_gpu_batchnorm.py is written from shapes, its dispatch branches are not listed yet"),
     ("nk_pool.hip", "38 instantiations (window / index-width / kernel-size templates); tests/test_gpu_pooling.py is written from shapes"),
-    ("nk_norm.hip", "19 instantiations of the LayerNorm row kernels; tests/test_gpu_layernorm.py is written from shapes"),
+    ("nk_norm.hip", "230 instantiations: the LayerNorm and RMSNorm row kernels, embedding, cross entropy, activations and GLU, the "
+                    "multi-tensor optimizer, rope, sampling, band attention and every decode and paged-cache kernel; their test files "
+                    "(tests/test_gpu_layernorm.py, test_gpu_rms_norm.py, test_gpu_rope.py, ...) are written from shapes"),
     ("nk_comm.hip", "2 replica-sum kernels; they run under a communicator only (tests/test_gpu_multi.py needs two GPUs)"),
     ("nk_runtime.hip", "1 copy kernel (nk_copy from 1 Mi floats on); entered by tests/test_gpu_parity.py, no dispatch grid to list"),
 )
