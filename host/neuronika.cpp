@@ -766,76 +766,150 @@ struct HeadsContextBwd : Backward {
     void targets(std::vector<const Gradient*>& out) const override { out.push_back(dp.get()); out.push_back(dv.get()); }
 };
 
-// heads_scores -> attention_probs -> heads_context as one node (nk_attention_fwd / nk_attention_bwd)
-struct HeadsAttentionFwd : Forward {
-    HeadsGeom hg;
-    Shared<HipArray> q, k, v, scores, stats, mask, o;  // mask: the dropout draws, 1 bit per score (u32 words in an f32 array)
-    float scale;
-    double p;
-    Shared<bool> status;
-    uint64_t seed;
-    Shared<uint64_t> calls;  // each forward draws a fresh mask (the Philox offset advances), as AttnProbsFwd
-    bool causal = false;     // nk_attention_causal_*: query r attends to keys <= r (same draws, same offset advance)
-    int window = 0;          // > 0: nk_attention_band_*, query r attends to keys r - window < k <= r; scores / mask are the banded scratch
-    Shared<HipArray> seg;    // (B, S) int32 left edges: nk_attention_seg_* with span = `window`, which sizes the same scratch
-    void forward() const override {
-        const uint64_t sp = ((uint64_t)hg.S + 31) / 32 * 32;  // the draws are indexed in the padded (B*H, SP, SP) tensor (SP = S unless S is ragged)
-        const uint64_t offset = (*calls) * (((uint64_t)hg.B * hg.H * sp * sp + 7) / 8);  // draws per forward, 8 per Philox call
-        if (seg) {
-            check(nk_attention_seg_fwd(D(q), q->ptr(), k->ptr(), v->ptr(), reinterpret_cast<const int*>(seg->ptr()), scores->ptr(), stats->ptr(),
-                                       reinterpret_cast<uint32_t*>(mask->ptr()), o->ptr(), hg.B, hg.S, hg.H, hg.dh, window, scale, p, *status ? 1 : 0,
-                                       seed, offset));
-            ++(*calls);
-            return;
-        }
-        if (window > 0) {  // (the band keeps its state in every graph: scores and stats are never null here)
-            check(nk_attention_band_fwd(D(q), q->ptr(), k->ptr(), v->ptr(), scores->ptr(), stats->ptr(), reinterpret_cast<uint32_t*>(mask->ptr()),
-                                        o->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p, *status ? 1 : 0, seed, offset, window));
-            ++(*calls);
-            return;
-        }
-        // scores / stats / mask are null in a graph without gradients: nothing is kept, no (B*H, S, S) tensor exists
-        check((causal ? nk_attention_causal_fwd : nk_attention_fwd)(D(q), q->ptr(), k->ptr(), v->ptr(), scores ? scores->ptr() : nullptr, stats ? stats->ptr() : nullptr,
-                               mask ? reinterpret_cast<uint32_t*>(mask->ptr()) : nullptr, o->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
-                               *status ? 1 : 0, seed, offset));
-        ++(*calls);  // only a forward that was issued consumes its Philox range (a refused capture throws above)
+// S <= window: the band is the whole triangle, every path as without a window (the causal kernels as they are)
+int band_of(int window, int S) { return window > 0 && S > window ? window : 0; }
+// The banded scratch of the sliding-window core, sized by the library's three geometry functions and allocated WITHOUT a fill: the
+// kernels define every element they read, and an O(S * ld) memset per graph would be pure loss.
+struct BandScratch { Shape scores, mask; };
+BandScratch band_scratch(int B, int S, int H, int window) {
+    const size_t ext = nk_attention_band_scratch(S, window), words = nk_attention_band_mask_words(S, window);
+    if (ext > 0x7fffffffu || words > 0x7fffffffu) panic("heads_attention: the banded scratch of one head exceeds 2^31 elements");
+    return {Shape{B * H, (int)ext}, Shape{B * H, (int)words}};
+}
+Shared<HipArray> uninit_like(const Shared<HipArray>& a, Shape s) { return std::make_shared<HipArray>(a->device(), std::move(s), HipArray::Uninit{}); }
+
+// What a causal form refuses, worded once for the two callers that refuse it under their own name.
+struct FormRefusals {
+    const char* who;
+    bool causal;
+    void window(int w) const {
+        if (w < 0) panic(std::string(who) + ": window must not be negative, got " + std::to_string(w));
+        if (w > 0 && !causal) panic(std::string(who) + ": a sliding window is a band of the CAUSAL triangle: set causal = true");
+    }
+    void segments(const nn::Segments* s, int B, int S, const Device* dev) const {
+        if (s && !causal) panic(std::string(who) + ": segments are blocks of the CAUSAL triangle: set causal = true");
+        if (s && (s->batch != B || s->S != S))
+            panic(std::string(who) + ": the segments were built for (batch " + std::to_string(s->batch) + ", S " + std::to_string(s->S) + "), the call has (" +
+                  std::to_string(B) + ", " + std::to_string(S) + ")");
+        if (s && s->lo->device().get() != dev) panic(std::string(who) + ": the segments live on another device");
     }
 };
-struct HeadsAttentionBwd : Backward {
+
+// One call of the fused attention core, heads_scores -> attention_probs -> heads_context as one launch sequence (nk_attention_* on
+// three operands, nk_attention_qkv_* on the packed buffer): the form, the dropout stream and the scratch.  The forward and the
+// backward node of a graph hold copies of ONE description, so the arrays and `calls` are shared between them.
+struct AttnCore {
     HeadsGeom hg;
-    Shared<HipArray> q, k, v, scores, stats, mask, o;
-    Shared<HipArray> ds, dropped;  // (B*H, S, S) scratch written by the first kernel, read by the dK / dV products
-    Shared<Gradient> dq, dk, dv, g;
-    float scale;
-    double p;
+    float scale = 0.f;
+    double p = 0.0;
     Shared<bool> status;
-    bool causal = false;
-    int window = 0;  // as the forward node
-    Shared<HipArray> seg;
+    uint64_t seed = 0;
+    Shared<uint64_t> calls;  // each forward draws a fresh mask (the Philox offset advances), as AttnProbsFwd
+    bool causal = false;     // nk_attention_causal_*: query r attends to keys <= r (same draws, same offset advance)
+    int span = 0;            // > 0: nk_attention_band_*, query r attends to keys r - span < k <= r; scores / mask are the banded scratch
+    Shared<HipArray> lo;     // (B, S) int32 left edges: nk_attention_seg_* with `span`, which sizes the same scratch
+    // mask: the dropout draws, 1 bit per score (u32 words in an f32 array).  All three are null in the dense form of a graph without
+    // gradients: nothing is kept, no (B*H, S, S) tensor exists.  The band keeps its state in every graph.
+    Shared<HipArray> scores, stats, mask;
+    Shared<HipArray> ds, dropped;  // backward only: scratch of the extent of `scores`, written by the first kernel, read by the dK / dV products
+
+    // Every decision about the form and its scratch.  `like` gives the device; keep: a backward node will read the state.
+    static AttnCore build(const Shared<HipArray>& like, int B, int S, int H, int dh, float scale, double p, Shared<bool> status, bool causal,
+                          int window, const nn::Segments* segments, bool keep) {
+        AttnCore c;
+        c.hg = {B, S, H, dh}; c.scale = scale; c.p = p; c.status = std::move(status); c.causal = causal;
+        c.span = band_of(window, S);
+        // one document per sample is the call without segments; otherwise the seg kernels on the band's scratch for span = min(max_len, window)
+        if (segments && segments->max_len < S) {
+            c.span = c.span ? std::min(c.span, segments->max_len) : segments->max_len;
+            c.lo = segments->lo;
+        }
+        const int SP = (S + 31) / 32 * 32;  // the scratch tensors are padded to whole 32 x 32 tiles (include/neuronika_hip.h)
+        if (c.span) {
+            const BandScratch bs = band_scratch(B, S, H, c.span);
+            c.scores = uninit_like(like, bs.scores);
+            c.stats = uninit_like(like, Shape{B * H, SP, 2});
+            c.mask = uninit_like(like, bs.mask);
+        } else if (keep) {
+            c.scores = zeros_like(like, Shape{B * H, SP, SP});
+            c.stats = zeros_like(like, Shape{B * H, SP, 2});
+            c.mask = zeros_like(like, Shape{B * H, SP, SP / 32});
+        }
+        c.seed = next_node_seed();
+        c.calls = std::make_shared<uint64_t>(0);
+        return c;
+    }
+    // the second step of a differentiable graph: the banded kernels define what they read, the dense ones want zeros
+    void add_backward_scratch() {
+        ds = (span ? uninit_like : zeros_like)(scores, scores->shape());
+        dropped = (span ? uninit_like : zeros_like)(scores, scores->shape());
+    }
+
+    // q, k, v: the (B*S, H*dh) operands; k == null: q is the packed (B*S, 3 H*dh) buffer
+    void forward(nk_device* dev, const float* q, const float* k, const float* v, float* o) const {
+        const uint64_t sp = ((uint64_t)hg.S + 31) / 32 * 32;  // the draws are indexed in the padded (B*H, SP, SP) tensor (SP = S unless S is ragged)
+        const uint64_t offset = (*calls) * (((uint64_t)hg.B * hg.H * sp * sp + 7) / 8);  // draws per forward, 8 per Philox call
+        const int* edges = lo ? reinterpret_cast<const int*>(lo->ptr()) : nullptr;
+        float *sc = scores ? scores->ptr() : nullptr, *st = stats ? stats->ptr() : nullptr;
+        uint32_t* mk = mask ? reinterpret_cast<uint32_t*>(mask->ptr()) : nullptr;
+        const int B = hg.B, S = hg.S, H = hg.H, dh = hg.dh, train = *status ? 1 : 0;
+        if (lo)
+            check(k ? nk_attention_seg_fwd(dev, q, k, v, edges, sc, st, mk, o, B, S, H, dh, span, scale, p, train, seed, offset)
+                    : nk_attention_qkv_seg_fwd(dev, q, edges, sc, st, mk, o, B, S, H, dh, span, scale, p, train, seed, offset));
+        else if (span > 0)
+            check(k ? nk_attention_band_fwd(dev, q, k, v, sc, st, mk, o, B, S, H, dh, scale, p, train, seed, offset, span)
+                    : nk_attention_qkv_band_fwd(dev, q, sc, st, mk, o, B, S, H, dh, scale, p, train, seed, offset, span));
+        else if (k)
+            check((causal ? nk_attention_causal_fwd : nk_attention_fwd)(dev, q, k, v, sc, st, mk, o, B, S, H, dh, scale, p, train, seed, offset));
+        else
+            check((causal ? nk_attention_qkv_causal_fwd : nk_attention_qkv_fwd)(dev, q, sc, st, mk, o, B, S, H, dh, scale, p, train, seed, offset));
+        ++(*calls);  // only a forward that was issued consumes its Philox range (a refused capture throws above)
+    }
+    void forward(nk_device* dev, const float* qkv, float* o) const { forward(dev, qkv, nullptr, nullptr, o); }
+
+    // dS and Pd are written by the fused kernel, dQ comes out of it; dK / dV are the two batched products on dS / Pd.
+    // k == null: dq is the packed (B*S, 3 H*dh) gradient, q the packed buffer and aq the one assign flag.
+    void backward(nk_device* dev, float* dq, float* dk, float* dv, const float* dO, const float* o, const float* q, const float* k, const float* v,
+                  int aq, int ak, int av) const {
+        const int* edges = lo ? reinterpret_cast<const int*>(lo->ptr()) : nullptr;
+        float *s = ds->ptr(), *pd = dropped->ptr();
+        const float *sc = scores->ptr(), *st = stats->ptr();
+        const uint32_t* mk = reinterpret_cast<const uint32_t*>(mask->ptr());
+        const int B = hg.B, S = hg.S, H = hg.H, dh = hg.dh, train = *status ? 1 : 0;
+        if (lo)
+            check(k ? nk_attention_seg_bwd(dev, dq, dk, dv, s, pd, dO, o, sc, st, mk, q, k, v, edges, B, S, H, dh, span, scale, p, train, aq, ak, av)
+                    : nk_attention_qkv_seg_bwd(dev, dq, s, pd, dO, o, sc, st, mk, q, edges, B, S, H, dh, span, scale, p, train, aq));
+        else if (span > 0)
+            check(k ? nk_attention_band_bwd(dev, dq, dk, dv, s, pd, dO, o, sc, st, mk, q, k, v, B, S, H, dh, scale, p, train, aq, ak, av, span)
+                    : nk_attention_qkv_band_bwd(dev, dq, s, pd, dO, o, sc, st, mk, q, B, S, H, dh, scale, p, train, aq, span));
+        else if (k)
+            check((causal ? nk_attention_causal_bwd : nk_attention_bwd)(dev, dq, dk, dv, s, pd, dO, o, sc, st, mk, q, k, v, B, S, H, dh, scale, p, train,
+                                                                        aq, ak, av));
+        else
+            check((causal ? nk_attention_qkv_causal_bwd : nk_attention_qkv_bwd)(dev, dq, s, pd, dO, o, sc, st, mk, q, B, S, H, dh, scale, p, train, aq));
+    }
+    void backward(nk_device* dev, float* dqkv, const float* dO, const float* o, const float* qkv) const {
+        backward(dev, dqkv, nullptr, nullptr, dO, o, qkv, nullptr, nullptr, 1, 0, 0);
+    }
+};
+
+// the core on three projections in the flat layout
+struct HeadsAttentionFwd : Forward {
+    AttnCore core;
+    Shared<HipArray> q, k, v, o;
+    void forward() const override { core.forward(D(q), q->ptr(), k->ptr(), v->ptr(), o->ptr()); }
+};
+struct HeadsAttentionBwd : Backward {
+    AttnCore core;
+    Shared<HipArray> q, k, v, o;
+    Shared<Gradient> dq, dk, dv, g;
     void backward() const override {
         const HipArray& G = g->borrow();  // dO, flat layout
-        nk_device* dev = D(q);
         float bq, bk, bv;
         float* gq = first_write(dq, bq);
         float* gk = first_write(dk, bk);
         float* gv = first_write(dv, bv);
-        if (seg) {
-            check(nk_attention_seg_bwd(dev, gq, gk, gv, ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
-                                       reinterpret_cast<const uint32_t*>(mask->ptr()), q->ptr(), k->ptr(), v->ptr(),
-                                       reinterpret_cast<const int*>(seg->ptr()), hg.B, hg.S, hg.H, hg.dh, window, scale, p, *status ? 1 : 0,
-                                       bq == 0.f ? 1 : 0, bk == 0.f ? 1 : 0, bv == 0.f ? 1 : 0));
-            return;
-        }
-        if (window > 0) {
-            check(nk_attention_band_bwd(dev, gq, gk, gv, ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
-                                        reinterpret_cast<const uint32_t*>(mask->ptr()), q->ptr(), k->ptr(), v->ptr(), hg.B, hg.S, hg.H, hg.dh, scale,
-                                        p, *status ? 1 : 0, bq == 0.f ? 1 : 0, bk == 0.f ? 1 : 0, bv == 0.f ? 1 : 0, window));
-            return;
-        }
-        // dS and Pd are written by the fused kernel, dQ comes out of it; dK / dV are the two batched products on dS / Pd
-        check((causal ? nk_attention_causal_bwd : nk_attention_bwd)(dev, gq, gk, gv, ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
-                               reinterpret_cast<const uint32_t*>(mask->ptr()), q->ptr(), k->ptr(), v->ptr(), hg.B, hg.S, hg.H, hg.dh, scale,
-                               p, *status ? 1 : 0, bq == 0.f ? 1 : 0, bk == 0.f ? 1 : 0, bv == 0.f ? 1 : 0));
+        core.backward(D(q), gq, gk, gv, G.ptr(), o->ptr(), q->ptr(), k->ptr(), v->ptr(), bq == 0.f ? 1 : 0, bk == 0.f ? 1 : 0, bv == 0.f ? 1 : 0);
     }
     void targets(std::vector<const Gradient*>& out) const override {
         out.push_back(dq.get()); out.push_back(dk.get()); out.push_back(dv.get());
@@ -862,56 +936,24 @@ static void rope_inplace(nk_device* dev, float* x, int ld, const Shared<HipArray
 // the unpacked module runs as three Linear nodes + the attention node (same values bit for bit in the forward; the backward's
 // input gradient is one K = 3d chain instead of three K = d chains added up).
 struct QkvAttentionFwd : Forward {
-    HeadsGeom hg;
-    Shared<HipArray> x, w, b, qkv, scores, stats, mask, o;  // w (3d, d), b (3d): the packed storage; qkv (B*S, 3d)
-    float scale;
-    double p;
-    Shared<bool> status;
-    uint64_t seed;
-    Shared<uint64_t> calls;
-    bool causal = false;
-    int window = 0;         // > 0: nk_attention_qkv_band_* on the banded scratch
-    Shared<HipArray> seg;   // (B, S) int32 left edges: nk_attention_qkv_seg_* with span = `window`
+    AttnCore core;
+    Shared<HipArray> x, w, b, qkv, o;  // w (3d, d), b (3d): the packed storage; qkv (B*S, 3d)
     Shared<HipArray> rope;  // the rotary table or null; rg: 2 H heads over the Q|K blocks
     RopeGeom rg;
     Shared<HipArray> rope_start;  // packed sequences: one position per row (rg.B = B*S, rg.T = 1)
     void forward() const override {
-        const int n = hg.B * hg.S, d = hg.d();
+        const int n = core.hg.B * core.hg.S, d = core.hg.d();
         check(nk_linear_fwd(D(x), x->ptr(), w->ptr(), b->ptr(), qkv->ptr(), n, d, 3 * d));
         if (rope) rope_inplace(D(x), qkv->ptr(), 3 * d, rope, rope_start ? reinterpret_cast<const int*>(rope_start->ptr()) : nullptr, rg, false);
-        const uint64_t sp = ((uint64_t)hg.S + 31) / 32 * 32;
-        const uint64_t offset = (*calls) * (((uint64_t)hg.B * hg.H * sp * sp + 7) / 8);
-        if (seg) {
-            check(nk_attention_qkv_seg_fwd(D(x), qkv->ptr(), reinterpret_cast<const int*>(seg->ptr()), scores->ptr(), stats->ptr(),
-                                           reinterpret_cast<uint32_t*>(mask->ptr()), o->ptr(), hg.B, hg.S, hg.H, hg.dh, window, scale, p,
-                                           *status ? 1 : 0, seed, offset));
-            ++(*calls);
-            return;
-        }
-        if (window > 0) {
-            check(nk_attention_qkv_band_fwd(D(x), qkv->ptr(), scores->ptr(), stats->ptr(), reinterpret_cast<uint32_t*>(mask->ptr()), o->ptr(), hg.B,
-                                            hg.S, hg.H, hg.dh, scale, p, *status ? 1 : 0, seed, offset, window));
-            ++(*calls);
-            return;
-        }
-        check((causal ? nk_attention_qkv_causal_fwd : nk_attention_qkv_fwd)(D(x), qkv->ptr(), scores ? scores->ptr() : nullptr, stats ? stats->ptr() : nullptr,
-                                   mask ? reinterpret_cast<uint32_t*>(mask->ptr()) : nullptr, o->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
-                                   *status ? 1 : 0, seed, offset));
-        ++(*calls);
+        core.forward(D(x), qkv->ptr(), o->ptr());
     }
 };
 struct QkvAttentionBwd : Backward {
-    HeadsGeom hg;
-    Shared<HipArray> x, w, qkv, scores, stats, mask, o;
-    Shared<HipArray> dqkv, ds, dropped;  // scratch owned by the node: (B*S, 3d) and two (B*H, SP, SP)
+    AttnCore core;
+    Shared<HipArray> x, w, qkv, o;
+    Shared<HipArray> dqkv;               // scratch owned by the node: (B*S, 3d)
     Shared<HipArray> gw_all, gb_all;     // packed gradient storage: (3d, d), (3d)
     Shared<Gradient> dx, gw[3], gb[3], g;  // dx null for a non-differentiable input; gw / gb: views of gw_all / gb_all
-    float scale;
-    double p;
-    Shared<bool> status;
-    bool causal = false;
-    int window = 0;
-    Shared<HipArray> seg;
     Shared<HipArray> rope;  // as in the forward node: [dQ | dK] of the rotated rows go back through R^T in place
     RopeGeom rg;
     Shared<HipArray> rope_start;
@@ -929,20 +971,8 @@ struct QkvAttentionBwd : Backward {
     void backward() const override {
         const HipArray& G = g->borrow();  // dO (B*S, d)
         nk_device* dev = D(x);
-        const int n = hg.B * hg.S, d = hg.d();
-        if (seg) {
-            check(nk_attention_qkv_seg_bwd(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
-                                           reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), reinterpret_cast<const int*>(seg->ptr()), hg.B,
-                                           hg.S, hg.H, hg.dh, window, scale, p, *status ? 1 : 0, 1));
-        } else if (window > 0) {
-            check(nk_attention_qkv_band_bwd(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
-                                            reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
-                                            *status ? 1 : 0, 1, window));
-        } else {
-            check((causal ? nk_attention_qkv_causal_bwd : nk_attention_qkv_bwd)(dev, dqkv->ptr(), ds->ptr(), dropped->ptr(), G.ptr(), o->ptr(), scores->ptr(), stats->ptr(),
-                                       reinterpret_cast<const uint32_t*>(mask->ptr()), qkv->ptr(), hg.B, hg.S, hg.H, hg.dh, scale, p,
-                                       *status ? 1 : 0, 1));
-        }
+        const int n = core.hg.B * core.hg.S, d = core.hg.d();
+        core.backward(dev, dqkv->ptr(), G.ptr(), o->ptr(), qkv->ptr());
         if (rope) rope_inplace(dev, dqkv->ptr(), 3 * d, rope, rope_start ? reinterpret_cast<const int*>(rope_start->ptr()) : nullptr, rg, true);
         float beta;
         if (dx) {  // dX (+)= [dQ | dK | dV] . [Wq; Wk; Wv]: one NN product, K = 3d
@@ -2187,75 +2217,48 @@ VarDiff VarDiff::heads_context(const VarDiff& values, int B, int S, int H, int d
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(h));
 }
 bool Var::attention_core_supported(int S, int dh, double p) { return nk_attention_supported(S, dh, p, 1) != 0; }
-// The banded scratch of the sliding-window core, sized by the library's three geometry functions and allocated WITHOUT a fill: the
-// kernels define every element they read, and an O(S * ld) memset per graph would be pure loss.
-struct BandScratch { Shape scores, mask; };
-static BandScratch band_scratch(int B, int S, int H, int window) {
-    const size_t ext = nk_attention_band_scratch(S, window), words = nk_attention_band_mask_words(S, window);
-    if (ext > 0x7fffffffu || words > 0x7fffffffu) panic("heads_attention: the banded scratch of one head exceeds 2^31 elements");
-    return {Shape{B * H, (int)ext}, Shape{B * H, (int)words}};
-}
-static Shared<HipArray> uninit_like(const Shared<HipArray>& a, Shape s) { return std::make_shared<HipArray>(a->device(), std::move(s), HipArray::Uninit{}); }
-static Var heads_attention_node(const Var& q, const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
-                                Shared<bool> status, bool keep, bool causal, int window, const nn::Segments* segments) {
-    if (window < 0) panic("heads_attention: window must not be negative, got " + std::to_string(window));
-    if (window > 0 && !causal) panic("heads_attention: a sliding window is a band of the CAUSAL triangle: set causal = true");
-    if (segments && !causal) panic("heads_attention: segments are blocks of the CAUSAL triangle: set causal = true");
-    if (segments && (segments->batch != B || segments->S != S))
-        panic("heads_attention: the segments were built for (batch " + std::to_string(segments->batch) + ", S " + std::to_string(segments->S) +
-              "), the call has (" + std::to_string(B) + ", " + std::to_string(S) + ")");
-    if (segments && segments->lo->device().get() != q.device().get()) panic("heads_attention: the segments live on another device");
-    int band = window > 0 && S > window ? window : 0;  // S <= window: the band is the whole triangle, the causal kernels as they are
-    // one document per sample is the call without segments; otherwise the seg kernels on the band's scratch for span = min(max_len, window)
-    const bool seg = segments && segments->max_len < S;
-    if (seg) band = band ? std::min(band, segments->max_len) : segments->max_len;
+static Shared<HeadsAttentionFwd> heads_attention_node(const Var& q, const Var& keys, const Var& values, int B, int S, int H, int dh, float scale,
+                                                      double p, Shared<bool> status, bool keep, bool causal, int window,
+                                                      const nn::Segments* segments) {
+    const FormRefusals refuse{"heads_attention", causal};
+    refuse.window(window);
+    refuse.segments(segments, B, S, q.device().get());
     if (!(p >= 0.0 && p <= 1.0)) panic("Wrong probability received: " + std::to_string(p) + ".");
     check_heads(q.shape(), {}, B, S, H, dh, false);
     check_heads(keys.shape(), {}, B, S, H, dh, false);
     check_heads(values.shape(), {}, B, S, H, dh, false);
     if (!Var::attention_core_supported(S, dh, p)) panic("heads_attention: the fused kernels take dh in {32, 64, 128} and p < 1");
+    auto op = std::make_shared<HeadsAttentionFwd>();
+    op->q = q.data; op->k = keys.data; op->v = values.data;
+    op->core = AttnCore::build(q.data, B, S, H, dh, scale, p, std::move(status), causal, window, segments, keep);
+    op->o = zeros_like(q.data, Shape{B * S, H * dh});
+    return op;
+}
+static Var heads_attention_var(const Var& q, const Var& keys, const Var& values, const Shared<HeadsAttentionFwd>& op) {
     History<ForwardEntry> h = q.history;
     h.merge(keys.history);
     h.merge(values.history);
-    auto op = std::make_shared<HeadsAttentionFwd>();
-    op->hg = {B, S, H, dh}; op->q = q.data; op->k = keys.data; op->v = values.data;
-    if (band) {  // the band kernels keep their state in every graph
-        const BandScratch bs = band_scratch(B, S, H, band);
-        op->scores = uninit_like(q.data, bs.scores);
-        op->stats = uninit_like(q.data, Shape{B * H, (S + 31) / 32 * 32, 2});
-        op->mask = uninit_like(q.data, bs.mask);
-    } else if (keep) {  // what the backward node reads; a graph without gradients keeps nothing
-        const int SP = (S + 31) / 32 * 32;  // the scratch tensors are padded to whole 32 x 32 tiles (include/neuronika_hip.h)
-        op->scores = zeros_like(q.data, Shape{B * H, SP, SP});
-        op->stats = zeros_like(q.data, Shape{B * H, SP, 2});
-        op->mask = zeros_like(q.data, Shape{B * H, SP, SP / 32});
-    }
-    op->o = zeros_like(q.data, Shape{B * S, H * dh});
-    op->scale = scale; op->p = p; op->status = std::move(status); op->causal = causal; op->window = band;
-    if (seg) op->seg = segments->lo;
-    op->seed = next_node_seed();
-    op->calls = std::make_shared<uint64_t>(0);
     auto y = op->o;
     return Var::node(y, op, std::move(h));
 }
 Var Var::heads_attention(const Var& keys, const Var& values, int B, int S, int H, int dh, float scale, double p,
                          Shared<bool> status, bool causal, int window, const nn::Segments* segments) const {
-    return heads_attention_node(*this, keys, values, B, S, H, dh, scale, p, std::move(status), false, causal, window, segments);
+    return heads_attention_var(*this, keys, values,
+                               heads_attention_node(*this, keys, values, B, S, H, dh, scale, p, std::move(status), false, causal, window, segments));
 }
 VarDiff VarDiff::heads_attention(const VarDiff& keys, const VarDiff& values, int B, int S, int H, int dh, float scale, double p,
                                  Shared<bool> status, bool causal, int window, const nn::Segments* segments) const {
-    Var out = heads_attention_node(var, keys.var, values.var, B, S, H, dh, scale, p, status, true, causal, window, segments);
-    auto fwd = std::dynamic_pointer_cast<HeadsAttentionFwd>(out.history.to_vec().back().op);
+    auto fwd = heads_attention_node(var, keys.var, values.var, B, S, H, dh, scale, p, std::move(status), true, causal, window, segments);
+    Var out = heads_attention_var(var, keys.var, values.var, fwd);
     History<BackwardEntry> h = history;
     h.merge(keys.history);
     h.merge(values.history);
     auto g = std::make_shared<Gradient>(out.device(), out.shape());
     auto bw = std::make_shared<HeadsAttentionBwd>();
-    bw->hg = fwd->hg; bw->q = fwd->q; bw->k = fwd->k; bw->v = fwd->v; bw->scores = fwd->scores; bw->stats = fwd->stats; bw->mask = fwd->mask; bw->o = fwd->o;
-    bw->ds = fwd->window ? uninit_like(fwd->scores, fwd->scores->shape()) : zeros_like(fwd->scores, fwd->scores->shape());
-    bw->dropped = fwd->window ? uninit_like(fwd->scores, fwd->scores->shape()) : zeros_like(fwd->scores, fwd->scores->shape());
+    bw->core = fwd->core;
+    bw->core.add_backward_scratch();
+    bw->q = fwd->q; bw->k = fwd->k; bw->v = fwd->v; bw->o = fwd->o;
     bw->dq = grad; bw->dk = keys.grad; bw->dv = values.grad; bw->g = g;
-    bw->scale = scale; bw->p = p; bw->status = status; bw->causal = causal; bw->window = fwd->window; bw->seg = fwd->seg;
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(h));
 }
 Var Var::bmm(const Var& rhs) const { return matmul_var(2, *this, rhs); }
@@ -3189,26 +3192,11 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     History<ForwardEntry> hf = x.var.history;
     for (const Linear* l : {&m.q, &m.k, &m.v}) { hf.merge(l->weight.var.history); hf.merge(l->bias.var.history); }
     auto fw = std::make_shared<QkvAttentionFwd>();
-    fw->hg = {B, S, H, dh}; fw->x = x.var.data; fw->w = w; fw->b = b;
+    fw->x = x.var.data; fw->w = w; fw->b = b;
     fw->qkv = zeros_like(x.var.data, Shape{B * S, 3 * d});
-    const int SP = (S + 31) / 32 * 32;
-    int band = m.window > 0 && S > m.window ? m.window : 0;  // (forward() checked window >= 0 and causal)
-    if (seg) band = band ? std::min(band, seg->max_len) : seg->max_len;  // packed sequences (max_len < S): the band's scratch at the span
-    if (band) {
-        const BandScratch bs = band_scratch(B, S, H, band);
-        fw->scores = uninit_like(x.var.data, bs.scores);
-        fw->stats = uninit_like(x.var.data, Shape{B * H, SP, 2});
-        fw->mask = uninit_like(x.var.data, bs.mask);
-    } else {
-        fw->scores = zeros_like(x.var.data, Shape{B * H, SP, SP});
-        fw->stats = zeros_like(x.var.data, Shape{B * H, SP, 2});
-        fw->mask = zeros_like(x.var.data, Shape{B * H, SP, SP / 32});
-    }
+    // (forward() checked window >= 0 and causal; seg: packed sequences with max_len < S)
+    fw->core = AttnCore::build(x.var.data, B, S, H, dh, scale, m.drop.p, m.drop.status, m.causal, m.window, seg, true);
     fw->o = zeros_like(x.var.data, Shape{B * S, d});
-    fw->scale = scale; fw->p = m.drop.p; fw->status = m.drop.status; fw->causal = m.causal; fw->window = band;
-    if (seg) fw->seg = seg->lo;
-    fw->seed = next_node_seed();
-    fw->calls = std::make_shared<uint64_t>(0);
     if (m.rope) {
         fw->rope = m.rope->table;
         fw->rg = seg ? rope_geom(*m.rope, B * S, 1, 2 * H) : rope_geom(*m.rope, B, S, 2 * H);  // packed sequences: every row at its own position
@@ -3219,16 +3207,16 @@ static VarDiff qkv_attention_node(const MultiheadAttention& m, const Shared<HipA
     for (const Linear* l : {&m.q, &m.k, &m.v}) { hb.merge(l->weight.history); hb.merge(l->bias.history); }
     auto g = std::make_shared<Gradient>(out.device(), out.shape());
     auto bw = std::make_shared<QkvAttentionBwd>();
-    bw->hg = fw->hg; bw->x = fw->x; bw->w = w; bw->qkv = fw->qkv; bw->scores = fw->scores; bw->stats = fw->stats; bw->mask = fw->mask; bw->o = fw->o;
+    bw->core = fw->core;
+    bw->x = fw->x; bw->w = w; bw->qkv = fw->qkv; bw->o = fw->o;
     bw->dqkv = zeros_like(fw->qkv, fw->qkv->shape());
-    bw->ds = band ? uninit_like(fw->scores, fw->scores->shape()) : zeros_like(fw->scores, fw->scores->shape());
-    bw->dropped = band ? uninit_like(fw->scores, fw->scores->shape()) : zeros_like(fw->scores, fw->scores->shape());
+    bw->core.add_backward_scratch();
     bw->gw_all = gw; bw->gb_all = gb;
     bw->dx = x.grad;
     const Linear* ls[3] = {&m.q, &m.k, &m.v};
     for (int i = 0; i < 3; ++i) { bw->gw[i] = ls[i]->weight.grad; bw->gb[i] = ls[i]->bias.grad; }
-    bw->g = g; bw->scale = scale; bw->p = m.drop.p; bw->status = m.drop.status; bw->causal = m.causal; bw->window = band;
-    bw->rope = fw->rope; bw->rg = fw->rg; bw->rope_start = fw->rope_start; bw->seg = fw->seg;
+    bw->g = g;
+    bw->rope = fw->rope; bw->rg = fw->rg; bw->rope_start = fw->rope_start;
     return VarDiff::node(std::move(out), g, entry(bw, g), std::move(hb));
 }
 // q / k / v are public members: the packed path is only valid while they still ARE the views of the packed storage
@@ -3251,20 +3239,16 @@ VarDiff MultiheadAttention::forward(const VarDiff& x, int batch, const Segments&
 VarDiff MultiheadAttention::forward_impl(const VarDiff& x, int batch, const Segments* seg) const {
     const int rows = x.shape()[0], S = rows / batch, dh = d_model / heads;
     if (rows % batch != 0 || x.shape()[1] != d_model) panic("MultiheadAttention: bad input shape");
+    const FormRefusals refuse{"MultiheadAttention", causal};
+    refuse.segments(seg, batch, S, x.var.device().get());
     if (seg) {
-        if (!causal) panic("MultiheadAttention: segments are blocks of the CAUSAL triangle: set causal = true");
-        if (seg->batch != batch || seg->S != S)
-            panic("MultiheadAttention: the segments were built for (batch " + std::to_string(seg->batch) + ", S " + std::to_string(seg->S) +
-                  "), the call has (" + std::to_string(batch) + ", " + std::to_string(S) + ")");
-        if (seg->lo->device().get() != x.var.device().get()) panic("MultiheadAttention: the segments live on another device");
         if (rope && seg->max_len > rope->max_pos)
             panic("MultiheadAttention: a document of " + std::to_string(seg->max_len) + " positions exceeds rope's table of " + std::to_string(rope->max_pos));
         if (seg->max_len >= S) seg = nullptr;  // one document per sample: lo = 0 and pos = t - the call without segments, node for node
     }
     const float scale = 1.f / std::sqrt((float)dh);
-    if (window < 0) panic("MultiheadAttention: window must not be negative, got " + std::to_string(window));
-    if (window > 0 && !causal) panic("MultiheadAttention: a sliding window is a band of the CAUSAL triangle: set causal = true");
-    const bool banded = window > 0 && S > window;  // S <= window: the band is the whole triangle, every path as without a window
+    refuse.window(window);
+    const bool banded = band_of(window, S) != 0;  // what the mask leaves below draw
     if (rope) {
         if (rope->head_dim != dh)
             panic("MultiheadAttention: rope was built for heads of " + std::to_string(rope->head_dim) + ", the module has heads of " + std::to_string(dh));
@@ -3438,26 +3422,35 @@ void KvCache::truncate(const std::vector<int>& lens) {
 static std::shared_ptr<DecodeStepFwd> decode_step_node(const MultiheadAttention& m, const Var& x, int batch, int T, bool fresh, bool packed,
                                                        const Shared<HipArray>& wqkv, const Shared<HipArray>& bqkv, History<ForwardEntry>& hf);
 
-Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) const {
-    if (!causal) panic("MultiheadAttention::forward_step is the incremental form of the CAUSAL forward: set causal = true");
-    if (*drop.status && drop.p > 0.0) panic("MultiheadAttention::forward_step runs in inference: dropout is active (p > 0 in train mode), call drop.eval() first");
-    if (x.shape().size() != 2 || batch <= 0 || x.shape()[0] % batch != 0 || x.shape()[0] == 0 || x.shape()[1] != d_model)
+// What both forward_step overloads refuse before they look at their cache's contents, in the order they fire: the layer's mode,
+// the input's shape, the cache's own geometry and device (`cache_fits(dh)`, worded by each overload), rope's head size, the
+// window.  Returns T.
+template <class CacheFits>
+static int step_preamble(const MultiheadAttention& m, const Var& x, int batch, const CacheFits& cache_fits) {
+    if (!m.causal) panic("MultiheadAttention::forward_step is the incremental form of the CAUSAL forward: set causal = true");
+    if (*m.drop.status && m.drop.p > 0.0) panic("MultiheadAttention::forward_step runs in inference: dropout is active (p > 0 in train mode), call drop.eval() first");
+    if (x.shape().size() != 2 || batch <= 0 || x.shape()[0] % batch != 0 || x.shape()[0] == 0 || x.shape()[1] != m.d_model)
         panic("MultiheadAttention::forward_step: bad input shape");
-    const int T = x.shape()[0] / batch, dh = d_model / heads;
-    if (cache.batch != batch || cache.heads != kv_heads || cache.head_dim != dh)
-        panic("MultiheadAttention::forward_step: the cache was built for batch " + std::to_string(cache.batch) + ", " + std::to_string(cache.heads) +
-              " heads of " + std::to_string(cache.head_dim) + ", the step has batch " + std::to_string(batch) + ", " + std::to_string(kv_heads) +
-              " kv heads (of " + std::to_string(heads) + " query heads) of " + std::to_string(dh));
-    if (cache.k->device().get() != x.device().get()) panic("MultiheadAttention::forward_step: the cache lives on another device");
-    if (rope) {
-        if (rope->head_dim != dh)
-            panic("MultiheadAttention::forward_step: rope was built for heads of " + std::to_string(rope->head_dim) + ", the module has heads of " +
-                  std::to_string(dh));
-        if (!cache.rolling && cache.capacity > rope->max_pos)
-            panic("MultiheadAttention::forward_step: the cache's capacity of " + std::to_string(cache.capacity) + " exceeds rope's table of " +
-                  std::to_string(rope->max_pos));
-    }
-    if (window < 0) panic("MultiheadAttention::forward_step: window must not be negative, got " + std::to_string(window));
+    const int T = x.shape()[0] / batch, dh = m.d_model / m.heads;
+    cache_fits(dh);
+    if (m.rope && m.rope->head_dim != dh)
+        panic("MultiheadAttention::forward_step: rope was built for heads of " + std::to_string(m.rope->head_dim) + ", the module has heads of " +
+              std::to_string(dh));
+    if (m.window < 0) panic("MultiheadAttention::forward_step: window must not be negative, got " + std::to_string(m.window));
+    return T;
+}
+
+Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) const {
+    const int T = step_preamble(*this, x, batch, [&](int dh) {
+        if (cache.batch != batch || cache.heads != kv_heads || cache.head_dim != dh)
+            panic("MultiheadAttention::forward_step: the cache was built for batch " + std::to_string(cache.batch) + ", " + std::to_string(cache.heads) +
+                  " heads of " + std::to_string(cache.head_dim) + ", the step has batch " + std::to_string(batch) + ", " + std::to_string(kv_heads) +
+                  " kv heads (of " + std::to_string(heads) + " query heads) of " + std::to_string(dh));
+        if (cache.k->device().get() != x.device().get()) panic("MultiheadAttention::forward_step: the cache lives on another device");
+    });
+    if (rope && !cache.rolling && cache.capacity > rope->max_pos)
+        panic("MultiheadAttention::forward_step: the cache's capacity of " + std::to_string(cache.capacity) + " exceeds rope's table of " +
+              std::to_string(rope->max_pos));
     if (cache.rolling && window == 0)
         panic("MultiheadAttention::forward_step: a rolling cache keeps the last positions only: it needs a layer with window > 0");
     if (cache.rolling && T > cache.capacity)
@@ -3546,21 +3539,14 @@ static std::shared_ptr<DecodeStepFwd> decode_step_node(const MultiheadAttention&
 }
 
 Var MultiheadAttention::forward_step(const Var& x, const std::vector<int>& seqs, PagedKvCache& cache) const {
-    if (!causal) panic("MultiheadAttention::forward_step is the incremental form of the CAUSAL forward: set causal = true");
-    if (*drop.status && drop.p > 0.0) panic("MultiheadAttention::forward_step runs in inference: dropout is active (p > 0 in train mode), call drop.eval() first");
     const int batch = (int)seqs.size();
-    if (x.shape().size() != 2 || batch <= 0 || x.shape()[0] % batch != 0 || x.shape()[0] == 0 || x.shape()[1] != d_model)
-        panic("MultiheadAttention::forward_step: bad input shape");
-    const int T = x.shape()[0] / batch, dh = d_model / heads;
-    if (cache.heads != kv_heads || cache.head_dim != dh)
-        panic("MultiheadAttention::forward_step: the paged cache was built for " + std::to_string(cache.heads) + " heads of " +
-              std::to_string(cache.head_dim) + ", the step has " + std::to_string(kv_heads) + " kv heads (of " + std::to_string(heads) +
-              " query heads) of " + std::to_string(dh));
-    if (cache.k->device().get() != x.device().get()) panic("MultiheadAttention::forward_step: the cache lives on another device");
-    if (rope && rope->head_dim != dh)
-        panic("MultiheadAttention::forward_step: rope was built for heads of " + std::to_string(rope->head_dim) + ", the module has heads of " +
-              std::to_string(dh));
-    if (window < 0) panic("MultiheadAttention::forward_step: window must not be negative, got " + std::to_string(window));
+    const int T = step_preamble(*this, x, batch, [&](int dh) {
+        if (cache.heads != kv_heads || cache.head_dim != dh)
+            panic("MultiheadAttention::forward_step: the paged cache was built for " + std::to_string(cache.heads) + " heads of " +
+                  std::to_string(cache.head_dim) + ", the step has " + std::to_string(kv_heads) + " kv heads (of " + std::to_string(heads) +
+                  " query heads) of " + std::to_string(dh));
+        if (cache.k->device().get() != x.device().get()) panic("MultiheadAttention::forward_step: the cache lives on another device");
+    });
     bool fresh = true;
     for (int b = 0; b < batch; ++b) {
         const int s = seqs[b];
