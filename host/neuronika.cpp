@@ -1476,6 +1476,105 @@ VarDiff rms_norm_diff(const Var& x, const Shared<Gradient>& dx, const History<Ba
     return VarDiff::node(std::move(var), grad, entry(bw, grad), std::move(h));
 }
 
+// Group normalisation (ours; the reference has no such node): x of shape (N, C, spatial...) read as (N, C, L), `groups` channel
+// groups; groups == C is instance normalisation.  gamma / beta of shape (C), both or neither.  The forward node owns `stats` =
+// {mean, rstd} per (sample, group), which the backward node reads; the no-gradient form keeps none.
+struct GroupNormFwd : Forward {
+    Shared<HipArray> x, gamma, beta, y, stats;  // gamma / beta null: no affine part; stats null: nothing kept for a backward pass
+    long long N, L;
+    int C, groups;
+    double eps;
+    void forward() const override {
+        check(nk_group_norm_fwd(D(x), x->ptr(), gamma ? gamma->ptr() : nullptr, beta ? beta->ptr() : nullptr, y->ptr(),
+                                stats ? stats->ptr() : nullptr, N, C, L, groups, eps));
+    }
+};
+// ONE backward entry for up to three gradients, each written only if that operand is differentiable, each through its own
+// first-writer-assigns state.
+struct GroupNormBwd : Backward {
+    Shared<Gradient> dx, dgamma, dbeta, g;  // any of the three targets may be null
+    Shared<HipArray> x, gamma, stats;
+    long long N, L;
+    int C, groups;
+    void backward() const override {
+        const HipArray& G = g->borrow();
+        nk_device* dev = D(x);
+        auto params = [&](float* a, float* b, bool assign) {
+            check((assign ? nk_group_norm_bwd_params_assign : nk_group_norm_bwd_params)(dev, a, b, G.ptr(), x->ptr(), stats->ptr(), N, C, L, groups));
+        };
+        bool ag = false, ab = false;
+        float* pg = dgamma ? dgamma->borrow_first_write(ag).ptr() : nullptr;
+        float* pb = dbeta ? dbeta->borrow_first_write(ab).ptr() : nullptr;
+        if (pg && pb && ag != ab) {  // one gradient already written in this pass (a shared parameter), the other not
+            params(pg, nullptr, ag);
+            params(nullptr, pb, ab);
+        } else if (pg || pb) {  // one pass over (g, x, stats) for both
+            params(pg, pb, pg ? ag : ab);
+        }
+        if (dx) {
+            bool assign = false;
+            HipArray& d = dx->borrow_first_write(assign);
+            check((assign ? nk_group_norm_bwd_assign : nk_group_norm_bwd)(dev, d.ptr(), G.ptr(), x->ptr(), gamma ? gamma->ptr() : nullptr,
+                                                                          stats->ptr(), N, C, L, groups));
+        }
+    }
+    void targets(std::vector<const Gradient*>& out) const override {
+        if (dgamma) out.push_back(dgamma.get());
+        if (dbeta) out.push_back(dbeta.get());
+        if (dx) out.push_back(dx.get());
+    }
+};
+
+Shared<GroupNormFwd> group_norm_fwd_node(const Var& x, int groups, const Var* gamma, const Var* beta, double eps, bool keep_stats) {
+    const Shape& xs = x.shape();
+    if (xs.size() < 2) panic("group_norm: expected an input of at least 2 dimensions (N, C, ...), got " + std::to_string(xs.size()));
+    const int C = xs[1];
+    if (groups <= 0 || C <= 0 || C % groups != 0)
+        panic("group_norm: " + std::to_string(C) + " channels cannot be cut into " + std::to_string(groups) + " groups");
+    if ((gamma == nullptr) != (beta == nullptr)) panic("group_norm: gamma and beta go together");
+    if (gamma && gamma->shape() != Shape{C}) panic("group_norm: gamma must have shape (C)");
+    if (beta && beta->shape() != Shape{C}) panic("group_norm: beta must have shape (C)");
+    if (!(eps >= 0.0) || !std::isfinite(eps)) panic("group_norm: eps must be finite and not negative");
+    auto n = std::make_shared<GroupNormFwd>();
+    n->N = xs[0]; n->C = C; n->groups = groups;
+    n->L = 1;
+    for (size_t i = 2; i < xs.size(); ++i) n->L *= xs[i];
+    if (n->L * (C / groups) > 0x7fffffffll || n->N * groups > 0x7fffffffll) panic("group_norm: a group row and the row count must each fit in 31 bits");
+    n->x = x.data; n->gamma = gamma ? gamma->data : nullptr; n->beta = beta ? beta->data : nullptr;
+    n->y = zeros_like(x.data, xs);
+    if (keep_stats) n->stats = zeros_like(x.data, Shape{(int)(n->N * groups), 2});
+    n->eps = eps;
+    return n;
+}
+Var group_norm_var(const Var& x, int groups, const Var* gamma, const Var* beta, double eps) {
+    History<ForwardEntry> h = x.history;
+    if (gamma) h.merge(gamma->history);
+    if (beta) h.merge(beta->history);
+    auto n = group_norm_fwd_node(x, groups, gamma, beta, eps, false);
+    auto y = n->y;
+    return Var::node(y, n, std::move(h));
+}
+// x, gamma, beta with their gradients and tapes where differentiable (null otherwise); at least one gradient is not null
+VarDiff group_norm_diff(const Var& x, const Shared<Gradient>& dx, const History<BackwardEntry>* hx, int groups, const Var* gamma,
+                        const Shared<Gradient>& dgamma, const History<BackwardEntry>* hg, const Var* beta,
+                        const Shared<Gradient>& dbeta, const History<BackwardEntry>* hb, double eps) {
+    History<ForwardEntry> fh = x.history;
+    if (gamma) fh.merge(gamma->history);
+    if (beta) fh.merge(beta->history);
+    auto n = group_norm_fwd_node(x, groups, gamma, beta, eps, true);
+    auto y = n->y;
+    Var var = Var::node(y, n, std::move(fh));
+    History<BackwardEntry> h;
+    if (hx) h = *hx;
+    if (hg) h.merge(*hg);
+    if (hb) h.merge(*hb);
+    auto grad = std::make_shared<Gradient>(var.device(), var.shape());
+    auto bw = std::make_shared<GroupNormBwd>();
+    bw->dx = dx; bw->dgamma = dgamma; bw->dbeta = dbeta; bw->g = grad;
+    bw->x = x.data; bw->gamma = n->gamma; bw->stats = n->stats; bw->N = n->N; bw->C = n->C; bw->L = n->L; bw->groups = groups;
+    return VarDiff::node(std::move(var), grad, entry(bw, grad), std::move(h));
+}
+
 // Batch normalisation (ours; the reference has no such node): x read as (N, C, L), L the product of the extents behind the channel
 // axis.  The forward node reads `status` each time it runs on the host (as Dropout's does): training normalises with the batch
 // statistics and updates the running ones in place, inference normalises with the running ones.  Without running statistics the
@@ -2005,6 +2104,11 @@ Var Var::rms_norm(const Shape& normalized_shape, double eps) const { return rms_
 VarDiff Var::rms_norm(const VarDiff& gamma, double eps) const {
     return rms_norm_diff(*this, nullptr, nullptr, &gamma.var, gamma.grad, &gamma.history, gamma.shape(), eps);
 }
+Var Var::group_norm(int num_groups, const Var& gamma, const Var& beta, double eps) const { return group_norm_var(*this, num_groups, &gamma, &beta, eps); }
+Var Var::group_norm(int num_groups, double eps) const { return group_norm_var(*this, num_groups, nullptr, nullptr, eps); }
+VarDiff Var::group_norm(int num_groups, const VarDiff& gamma, const VarDiff& beta, double eps) const {
+    return group_norm_diff(*this, nullptr, nullptr, num_groups, &gamma.var, gamma.grad, &gamma.history, &beta.var, beta.grad, &beta.history, eps);
+}
 Var Var::batch_norm(const Var* gamma, const Var* beta, const Var* running_mean, const Var* running_var, double momentum, double eps,
                     Shared<bool> status) const {
     return batch_norm_var(*this, gamma, beta, running_mean, running_var, momentum, eps, std::move(status));
@@ -2519,6 +2623,15 @@ VarDiff VarDiff::rms_norm(const Var& gamma, double eps) const {
 VarDiff VarDiff::rms_norm(const Shape& normalized_shape, double eps) const {
     return rms_norm_diff(var, grad, &history, nullptr, nullptr, nullptr, normalized_shape, eps);
 }
+VarDiff VarDiff::group_norm(int num_groups, const VarDiff& gamma, const VarDiff& beta, double eps) const {
+    return group_norm_diff(var, grad, &history, num_groups, &gamma.var, gamma.grad, &gamma.history, &beta.var, beta.grad, &beta.history, eps);
+}
+VarDiff VarDiff::group_norm(int num_groups, const Var& gamma, const Var& beta, double eps) const {
+    return group_norm_diff(var, grad, &history, num_groups, &gamma, nullptr, nullptr, &beta, nullptr, nullptr, eps);
+}
+VarDiff VarDiff::group_norm(int num_groups, double eps) const {
+    return group_norm_diff(var, grad, &history, num_groups, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, eps);
+}
 VarDiff VarDiff::embedding(const Var& indices, long padding_idx) const {
     auto n = embedding_fwd_node(var, indices, padding_idx);
     auto y = n->y;
@@ -2891,6 +3004,56 @@ VarDiff RMSNorm::forward(const Var& input) const {
 }
 VarDiff RMSNorm::forward(const VarDiff& input) const {
     return elementwise_affine ? input.rms_norm(weight, eps) : input.rms_norm(normalized_shape, eps);
+}
+GroupNorm::GroupNorm(DevicePtr dev, int num_groups, int num_channels, double eps, bool affine)
+    : num_groups(num_groups), num_channels(num_channels), eps(eps), affine(affine) {
+    if (num_groups <= 0 || num_channels <= 0 || num_channels % num_groups != 0)
+        panic("GroupNorm: num_channels must be a positive multiple of num_groups");
+    if (affine) {
+        weight = ones(dev, {num_channels}).requires_grad();
+        bias = zeros(dev, {num_channels}).requires_grad();
+    }
+}
+GroupNorm::GroupNorm(int num_groups, VarDiff w, VarDiff b, double eps)
+    : weight(std::move(w)), bias(std::move(b)), num_groups(num_groups), num_channels(0), eps(eps) {
+    if (weight.shape().size() != 1 || bias.shape() != weight.shape()) panic("GroupNorm: weight and bias must share one shape (C)");
+    num_channels = weight.shape()[0];
+    if (num_groups <= 0 || num_channels % num_groups != 0) panic("GroupNorm: num_channels must be a positive multiple of num_groups");
+}
+void GroupNorm::check_input(const Shape& s) const {
+    if (s.size() < 2) panic("GroupNorm: expected an input of at least 2 dimensions, got " + std::to_string(s.size()));
+    if (s[1] != num_channels) panic("GroupNorm: expected " + std::to_string(num_channels) + " channels, got " + std::to_string(s[1]));
+}
+VarDiff GroupNorm::forward(const Var& input) const {
+    check_input(input.shape());
+    if (!affine) panic("GroupNorm without affine parameters on a Var input has nothing to differentiate: use Var::group_norm(num_groups, eps)");
+    return input.group_norm(num_groups, weight, bias, eps);
+}
+VarDiff GroupNorm::forward(const VarDiff& input) const {
+    check_input(input.shape());
+    return affine ? input.group_norm(num_groups, weight, bias, eps) : input.group_norm(num_groups, eps);
+}
+InstanceNormNd::InstanceNormNd(int nd, DevicePtr dev, int num_features, double eps, bool affine)
+    : num_features(num_features), eps(eps), affine(affine), nd(nd) {
+    if (num_features <= 0) panic("InstanceNorm: num_features must be positive");
+    if (affine) {
+        weight = ones(dev, {num_features}).requires_grad();
+        bias = zeros(dev, {num_features}).requires_grad();
+    }
+}
+void InstanceNormNd::check_input(const Shape& s) const {
+    const std::string name = "InstanceNorm" + std::to_string(nd) + "d";
+    if (s.size() != (size_t)nd + 2) panic(name + ": expected " + std::to_string(nd + 2) + "-dimensional input, got " + std::to_string(s.size()) + " dimensions");
+    if (s[1] != num_features) panic(name + ": expected " + std::to_string(num_features) + " channels, got " + std::to_string(s[1]));
+}
+VarDiff InstanceNormNd::forward(const Var& input) const {
+    check_input(input.shape());
+    if (!affine) panic("InstanceNorm without affine parameters on a Var input has nothing to differentiate: use Var::group_norm(C, eps)");
+    return input.group_norm(num_features, weight, bias, eps);
+}
+VarDiff InstanceNormNd::forward(const VarDiff& input) const {
+    check_input(input.shape());
+    return affine ? input.group_norm(num_features, weight, bias, eps) : input.group_norm(num_features, eps);
 }
 Var GELU::forward(const Var& input) const { return input.gelu(approximate_tanh); }
 VarDiff GELU::forward(const VarDiff& input) const { return input.gelu(approximate_tanh); }
@@ -3921,6 +4084,16 @@ nn::LayerNorm layer_norm_from_json(DevicePtr dev, const Json& j, double eps) {
     return nn::LayerNorm(vardiff_from_json(dev, j.at("weight")), vardiff_from_json(dev, j.at("bias")), eps);
 }
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const std::string& text, double eps) { return layer_norm_from_json(std::move(dev), parse(text), eps); }
+std::string to_json(const nn::GroupNorm& l) {
+    if (!l.affine) panic("serde: a GroupNorm without affine parameters has nothing to serialise");
+    return "{\"weight\":" + to_json(l.weight) + ",\"bias\":" + to_json(l.bias) + "}";
+}
+nn::GroupNorm group_norm_from_json(DevicePtr dev, const Json& j, int num_groups, double eps) {
+    return nn::GroupNorm(num_groups, vardiff_from_json(dev, j.at("weight")), vardiff_from_json(dev, j.at("bias")), eps);
+}
+nn::GroupNorm group_norm_from_json(DevicePtr dev, const std::string& text, int num_groups, double eps) {
+    return group_norm_from_json(std::move(dev), parse(text), num_groups, eps);
+}
 std::string to_json(const nn::RMSNorm& l) {
     if (!l.elementwise_affine) panic("serde: an RMSNorm without a weight has nothing to serialise");
     return "{\"weight\":" + to_json(l.weight) + "}";

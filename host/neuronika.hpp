@@ -346,6 +346,12 @@ class Var {
     Var rms_norm(const Var& gamma, double eps = 1e-6) const;
     Var rms_norm(const Shape& normalized_shape, double eps = 1e-6) const;
     VarDiff rms_norm(const VarDiff& gamma, double eps = 1e-6) const;
+    // Group normalisation of an (N, C, spatial...) input over `num_groups` channel groups (ours: the reference has none; semantics
+    // in neuronika_hip.h); num_groups == C is instance normalisation.  gamma / beta of shape (C), or neither.  The Var forms keep
+    // no statistics.  The input needs at least 2 dimensions; C % num_groups != 0 throws before any launch.
+    Var group_norm(int num_groups, const Var& gamma, const Var& beta, double eps = 1e-5) const;
+    Var group_norm(int num_groups, double eps = 1e-5) const;
+    VarDiff group_norm(int num_groups, const VarDiff& gamma, const VarDiff& beta, double eps = 1e-5) const;
     // Batch normalisation over (N, spatial...) for each channel of an (N, C, spatial...) input (ours: the reference has none;
     // semantics in neuronika_hip.h).  gamma / beta of shape (C), both or neither (null: no affine part); running_mean /
     // running_var of shape (C), both or neither, updated IN PLACE by a training forward.  `status` is read each time the forward
@@ -496,6 +502,10 @@ class VarDiff {
     VarDiff rms_norm(const VarDiff& gamma, double eps = 1e-6) const;
     VarDiff rms_norm(const Var& gamma, double eps = 1e-6) const;
     VarDiff rms_norm(const Shape& normalized_shape, double eps = 1e-6) const;
+    // one forward and ONE backward entry; gradients flow to self and, independently, to gamma and beta where differentiable
+    VarDiff group_norm(int num_groups, const VarDiff& gamma, const VarDiff& beta, double eps = 1e-5) const;
+    VarDiff group_norm(int num_groups, const Var& gamma, const Var& beta, double eps = 1e-5) const;
+    VarDiff group_norm(int num_groups, double eps = 1e-5) const;
     // Embedding (ours: the reference has none; semantics in neuronika_hip.h): self is the (V, D) table, `indices` holds ids as f32
     // (read as the NLL targets are) in any shape; the result has shape indices.shape + (D,).  Differentiable in the table only:
     // its gradient is the ordered sum per row, no atomics; rows selected through `padding_idx` (< 0: none) receive no gradient.
@@ -657,6 +667,48 @@ struct RMSNorm {
     RMSNorm(VarDiff weight, double eps = 1e-6);  // a parameter built elsewhere (e.g. deserialised)
     VarDiff forward(const Var& input) const;  // differentiable in the weight: needs elementwise_affine
     VarDiff forward(const VarDiff& input) const;
+};
+
+// Group normalisation (ours: the reference has no normalisation layer), torch's GroupNorm: the channels of an (N, C, spatial...)
+// input are cut into `num_groups` groups and each (sample, group) is normalised over its channels and positions, then scaled and
+// shifted per channel.  weight = ones, bias = zeros of shape (C): ordinary leaves for the optimizers; without `affine` there are no
+// parameters.  It does not depend on the batch size, which is why it replaces BatchNorm at small per-device batches.
+struct GroupNorm {
+    VarDiff weight, bias;
+    int num_groups, num_channels;
+    double eps = 1e-5;
+    bool affine = true;
+    GroupNorm(DevicePtr dev, int num_groups, int num_channels, double eps = 1e-5, bool affine = true);
+    GroupNorm(int num_groups, VarDiff weight, VarDiff bias, double eps = 1e-5);  // parameters built elsewhere (e.g. deserialised)
+    VarDiff forward(const Var& input) const;  // differentiable in the parameters: needs affine
+    VarDiff forward(const VarDiff& input) const;
+   private:
+    void check_input(const Shape& s) const;
+};
+
+// Instance normalisation, torch's InstanceNorm1d/2d/3d: group normalisation with one channel per group, each (sample, channel)
+// plane normalised on its own.  No parameters by default (torch's default).  torch's track_running_stats is NOT built: the
+// statistics are always the input's own, in training and in inference.
+struct InstanceNormNd {
+    VarDiff weight, bias;
+    int num_features;
+    double eps;
+    bool affine;
+    int nd;  // 1: (N, C, L); 2: (N, C, H, W); 3: (N, C, D, H, W)
+    InstanceNormNd(int nd, DevicePtr dev, int num_features, double eps, bool affine);
+    VarDiff forward(const Var& input) const;  // differentiable in the parameters: needs affine
+    VarDiff forward(const VarDiff& input) const;
+   private:
+    void check_input(const Shape& s) const;
+};
+struct InstanceNorm1d : InstanceNormNd {
+    InstanceNorm1d(DevicePtr dev, int num_features, double eps = 1e-5, bool affine = false) : InstanceNormNd(1, std::move(dev), num_features, eps, affine) {}
+};
+struct InstanceNorm2d : InstanceNormNd {
+    InstanceNorm2d(DevicePtr dev, int num_features, double eps = 1e-5, bool affine = false) : InstanceNormNd(2, std::move(dev), num_features, eps, affine) {}
+};
+struct InstanceNorm3d : InstanceNormNd {
+    InstanceNorm3d(DevicePtr dev, int num_features, double eps = 1e-5, bool affine = false) : InstanceNormNd(3, std::move(dev), num_features, eps, affine) {}
 };
 
 // Batch normalisation over (N, spatial...) per channel (ours: the reference has no normalisation layer), torch's BatchNorm1d/2d/3d:
@@ -1154,6 +1206,9 @@ nn::Linear linear_from_json(DevicePtr dev, const std::string& text);
 std::string to_json(const nn::LayerNorm& l);  // {"weight":..., "bias":...}; eps is not part of the wire format
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const Json& j, double eps = 1e-5);
 nn::LayerNorm layer_norm_from_json(DevicePtr dev, const std::string& text, double eps = 1e-5);
+std::string to_json(const nn::GroupNorm& l);  // {"weight":..., "bias":...}; num_groups and eps are not part of the wire format
+nn::GroupNorm group_norm_from_json(DevicePtr dev, const Json& j, int num_groups, double eps = 1e-5);
+nn::GroupNorm group_norm_from_json(DevicePtr dev, const std::string& text, int num_groups, double eps = 1e-5);
 std::string to_json(const nn::RMSNorm& l);  // {"weight":...}; eps is not part of the wire format
 nn::RMSNorm rms_norm_from_json(DevicePtr dev, const Json& j, double eps = 1e-6);
 nn::RMSNorm rms_norm_from_json(DevicePtr dev, const std::string& text, double eps = 1e-6);

@@ -78,6 +78,9 @@ PYBIND11_MODULE(_tape, m) {
         .def("rms_norm", py::overload_cast<const Var&, double>(&Var::rms_norm, py::const_), py::arg("gamma"), py::arg("eps") = 1e-6)
         .def("rms_norm", py::overload_cast<const VarDiff&, double>(&Var::rms_norm, py::const_), py::arg("gamma"), py::arg("eps") = 1e-6)
         .def("rms_norm", py::overload_cast<const Shape&, double>(&Var::rms_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-6)
+        .def("group_norm", py::overload_cast<int, const Var&, const Var&, double>(&Var::group_norm, py::const_), py::arg("num_groups"), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
+        .def("group_norm", py::overload_cast<int, const VarDiff&, const VarDiff&, double>(&Var::group_norm, py::const_), py::arg("num_groups"), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
+        .def("group_norm", py::overload_cast<int, double>(&Var::group_norm, py::const_), py::arg("num_groups"), py::arg("eps") = 1e-5)
         // gamma / beta: VarDiff (differentiable result), Var, or None; running_mean / running_var: Var or None
         .def("batch_norm", [](const Var& x, const VarDiff& gamma, const VarDiff& beta, const Var* rm, const Var* rv, double momentum, double eps,
                               const Status& s) { return x.batch_norm(gamma, beta, rm, rv, momentum, eps, s.flag); },
@@ -161,6 +164,9 @@ PYBIND11_MODULE(_tape, m) {
         .def("rms_norm", py::overload_cast<const VarDiff&, double>(&VarDiff::rms_norm, py::const_), py::arg("gamma"), py::arg("eps") = 1e-6)
         .def("rms_norm", py::overload_cast<const Var&, double>(&VarDiff::rms_norm, py::const_), py::arg("gamma"), py::arg("eps") = 1e-6)
         .def("rms_norm", py::overload_cast<const Shape&, double>(&VarDiff::rms_norm, py::const_), py::arg("normalized_shape"), py::arg("eps") = 1e-6)
+        .def("group_norm", py::overload_cast<int, const VarDiff&, const VarDiff&, double>(&VarDiff::group_norm, py::const_), py::arg("num_groups"), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
+        .def("group_norm", py::overload_cast<int, const Var&, const Var&, double>(&VarDiff::group_norm, py::const_), py::arg("num_groups"), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
+        .def("group_norm", py::overload_cast<int, double>(&VarDiff::group_norm, py::const_), py::arg("num_groups"), py::arg("eps") = 1e-5)
         .def("embedding", &VarDiff::embedding, py::arg("indices"), py::arg("padding_idx") = -1)
         .def("batch_norm", [](const VarDiff& x, const VarDiff& gamma, const VarDiff& beta, const Var* rm, const Var* rv, double momentum, double eps,
                               const Status& s) { return x.batch_norm(gamma, beta, rm, rv, momentum, eps, s.flag); },
@@ -293,6 +299,9 @@ PYBIND11_MODULE(_tape, m) {
     sd.def("to_json", py::overload_cast<const nn::LayerNorm&>(&serde::to_json));
     sd.def("layer_norm_from_json", py::overload_cast<DevicePtr, const std::string&, double>(&serde::layer_norm_from_json), py::arg("dev"), py::arg("text"),
            py::arg("eps") = 1e-5);
+    sd.def("to_json", py::overload_cast<const nn::GroupNorm&>(&serde::to_json));
+    sd.def("group_norm_from_json", py::overload_cast<DevicePtr, const std::string&, int, double>(&serde::group_norm_from_json), py::arg("dev"), py::arg("text"),
+           py::arg("num_groups"), py::arg("eps") = 1e-5);
     sd.def("to_json", py::overload_cast<const nn::RMSNorm&>(&serde::to_json));
     sd.def("rms_norm_from_json", py::overload_cast<DevicePtr, const std::string&, double>(&serde::rms_norm_from_json), py::arg("dev"), py::arg("text"),
            py::arg("eps") = 1e-6);
@@ -338,6 +347,33 @@ PYBIND11_MODULE(_tape, m) {
         .def_readonly("elementwise_affine", &nn::RMSNorm::elementwise_affine)
         .def("forward", py::overload_cast<const Var&>(&nn::RMSNorm::forward, py::const_))
         .def("forward", py::overload_cast<const VarDiff&>(&nn::RMSNorm::forward, py::const_));
+    py::class_<nn::GroupNorm>(nn, "GroupNorm")
+        .def(py::init<DevicePtr, int, int, double, bool>(), py::arg("dev"), py::arg("num_groups"), py::arg("num_channels"), py::arg("eps") = 1e-5,
+             py::arg("affine") = true)
+        .def(py::init<int, VarDiff, VarDiff, double>(), py::arg("num_groups"), py::arg("weight"), py::arg("bias"), py::arg("eps") = 1e-5)
+        // without affine parameters there is no weight and no bias: None
+        .def_property_readonly("weight", [](const nn::GroupNorm& l) { return l.affine ? py::cast(l.weight) : py::object(py::none()); })
+        .def_property_readonly("bias", [](const nn::GroupNorm& l) { return l.affine ? py::cast(l.bias) : py::object(py::none()); })
+        .def_readonly("num_groups", &nn::GroupNorm::num_groups)
+        .def_readonly("num_channels", &nn::GroupNorm::num_channels)
+        .def_readwrite("eps", &nn::GroupNorm::eps)
+        .def_readonly("affine", &nn::GroupNorm::affine)
+        .def("forward", py::overload_cast<const Var&>(&nn::GroupNorm::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::GroupNorm::forward, py::const_));
+    py::class_<nn::InstanceNormNd>(nn, "InstanceNormNd")
+        .def_property_readonly("weight", [](const nn::InstanceNormNd& l) { return l.affine ? py::cast(l.weight) : py::object(py::none()); })
+        .def_property_readonly("bias", [](const nn::InstanceNormNd& l) { return l.affine ? py::cast(l.bias) : py::object(py::none()); })
+        .def_readonly("num_features", &nn::InstanceNormNd::num_features)
+        .def_readwrite("eps", &nn::InstanceNormNd::eps)
+        .def_readonly("affine", &nn::InstanceNormNd::affine)
+        .def("forward", py::overload_cast<const Var&>(&nn::InstanceNormNd::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::InstanceNormNd::forward, py::const_));
+    py::class_<nn::InstanceNorm1d, nn::InstanceNormNd>(nn, "InstanceNorm1d")
+        .def(py::init<DevicePtr, int, double, bool>(), py::arg("dev"), py::arg("num_features"), py::arg("eps") = 1e-5, py::arg("affine") = false);
+    py::class_<nn::InstanceNorm2d, nn::InstanceNormNd>(nn, "InstanceNorm2d")
+        .def(py::init<DevicePtr, int, double, bool>(), py::arg("dev"), py::arg("num_features"), py::arg("eps") = 1e-5, py::arg("affine") = false);
+    py::class_<nn::InstanceNorm3d, nn::InstanceNormNd>(nn, "InstanceNorm3d")
+        .def(py::init<DevicePtr, int, double, bool>(), py::arg("dev"), py::arg("num_features"), py::arg("eps") = 1e-5, py::arg("affine") = false);
     py::class_<nn::GELU>(nn, "GELU")
         .def(py::init<bool>(), py::arg("approximate_tanh") = false)
         .def_readonly("approximate_tanh", &nn::GELU::approximate_tanh)

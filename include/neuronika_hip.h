@@ -736,6 +736,47 @@ int nk_batch_norm_bwd_assign(nk_device* dev, float* dx, const float* g, const fl
 int nk_batch_norm_bwd_params(nk_device* dev, float* dgamma, float* dbeta, const float* sums, int C);
 int nk_batch_norm_bwd_params_assign(nk_device* dev, float* dgamma, float* dbeta, const float* sums, int C);
 
+/* ------------------------------------------------------------------ group / instance normalisation */
+/* Normalisation over channel groups of a contiguous row-major tensor read as (N, C, L), L the product of the extents behind the
+ * channel axis (L = 1 for an (N, C) input).  The reference has no such layer; the semantics are fixed here.  G groups with
+ * C % G == 0, Cg = C / G.  Group row r = n * G + j is the D = Cg * L contiguous floats at x + r * D.  Per row, all in f32:
+ *   mean = sum(x) / D ;  var = sum((x - mean)^2) / D   (biased; centred, never E[x^2] - mean^2)
+ *   rstd = 1 / sqrt(var + eps) ;  xhat = (x - mean) * rstd
+ *   y    = xhat * gamma[c] + beta[c] ,  c = j * Cg + (offset in the row) / L              (gamma, beta of C elements)
+ * G == C is instance normalisation; G == 1 is layer normalisation over (C, L) with a per-channel affine.  torch's
+ * track_running_stats of instance norm is not built.  fwd overwrites y and, when `stats` is not NULL, writes
+ * stats[N * G][2] = {mean, rstd}.  `gamma`, `beta` and `stats` may each be NULL.
+ * bwd, with gh = g * gamma[c] (or g when gamma is NULL) and xhat recomputed from x and stats:
+ *   dx        += rstd * (gh - mean_D(gh) - xhat * mean_D(gh * xhat))
+ *   dgamma[c] += sum over n and l of g * xhat ;  dbeta[c] += sum over n and l of g        (either output may be NULL, not both)
+ * N * G and D must each fit in 31 bits; element offsets are 64-bit.  N == 0 or L == 0 returns NK_OK and writes nothing (the
+ * _assign twins included).  NK_ERR_INVALID before any launch: G <= 0, C <= 0, C % G != 0, an eps that is negative or not finite.
+ * D = 1 gives y = beta[c]; a constant row has var = 0 and stays finite through eps; a non-finite input stays inside its own group
+ * row.  Three kernel classes, chosen from (Cg, L) and the pointers' 16-byte alignment alone:
+ *   D % 4 == 0, aligned, D <= 16384: the row in registers, the statistics formed exactly as nk_layer_norm_fwd forms them - at
+ *     G == 1 `stats` equals what nk_layer_norm_fwd(rows = N, D = C * L) writes, bit for bit (y may differ by an FMA contraction);
+ *   D % 4 == 0, aligned, D > 16384: the row is cut into chunks of 8192 floats (a constant of the library), each chunk's
+ *     (count, mean, M2) is formed in registers relative to an anchor, the row's first value (see batch normalisation), and every
+ *     block merges its row's triples in chunk order with Chan's formula; two launches per direction, x (and g) read twice;
+ *   anything else: a block per row, scalar accesses, the same construction with chunks of 2048 floats.
+ * No atomics, and no block waits on another.  The order of every sum is a function of (Cg, L) and the alignment alone - not of N,
+ * G, the device or its CU count - so every output repeats bit for bit, and the bits of a group row's y, stats and dx depend on that
+ * row's own x / g and its Cg channels' gamma / beta and on nothing else: a sample run alone gets the bits it gets inside a batch.
+ * For dgamma / dbeta (per-(n, c) sums in the workspace, then a fixed-order sum over n) the order also depends on N.  Nothing
+ * here synchronises or allocates beyond the workspace: the calls can be captured into a graph after one eager call of the same
+ * sizes.  The `_assign` twins write what their `+=` twin would leave in an all-zero destination, without reading it (see
+ * "first-write variants"). */
+int nk_group_norm_fwd(nk_device* dev, const float* x, const float* gamma, const float* beta, float* y, float* stats,
+                      long long N, int C, long long L, int G, double eps);
+int nk_group_norm_bwd(nk_device* dev, float* dx, const float* g, const float* x, const float* gamma, const float* stats,
+                      long long N, int C, long long L, int G);
+int nk_group_norm_bwd_assign(nk_device* dev, float* dx, const float* g, const float* x, const float* gamma,
+                             const float* stats, long long N, int C, long long L, int G);
+int nk_group_norm_bwd_params(nk_device* dev, float* dgamma, float* dbeta, const float* g, const float* x,
+                             const float* stats, long long N, int C, long long L, int G);
+int nk_group_norm_bwd_params_assign(nk_device* dev, float* dgamma, float* dbeta, const float* g, const float* x,
+                                    const float* stats, long long N, int C, long long L, int G);
+
 /* ------------------------------------------------------------------ pooling */
 /* Max and average pooling of a contiguous f32 tensor x of shape (N, C, in_1 .. in_nd), nd = 1, 2, 3.  The reference has no pooling;
  * the semantics are fixed here and they are torch's (max_pool / avg_pool 1d, 2d, 3d).  Per spatial axis i: window k_i >= 1, stride

@@ -201,6 +201,67 @@ impl<E: Dimension + 'static> LayerNorm<E> {
     }
 }
 
+/// Group normalisation (the reference has no normalisation layer; semantics in `include/neuronika_hip.h`), torch's `GroupNorm`:
+/// the channels of an `(N, C, spatial...)` input are cut into `num_groups` groups, each `(sample, group)` is normalised over its
+/// channels and positions and then scaled and shifted per channel.  `weight` starts as ones, `bias` as zeros, both of shape `(C)`.
+pub struct GroupNorm {
+    pub weight: HipVarDiff<Ix1>,
+    pub bias: HipVarDiff<Ix1>,
+    pub num_groups: usize,
+    pub eps: f64,
+}
+
+impl GroupNorm {
+    pub fn new(num_groups: usize, num_channels: usize, eps: f64, device: &Device) -> Self {
+        assert!(num_groups > 0 && num_channels % num_groups == 0, "GroupNorm: num_channels must be a multiple of num_groups");
+        Self {
+            weight: HipVarDiff::parameter(&Array::ones(num_channels), device.clone()),
+            bias: HipVarDiff::parameter(&Array::zeros(num_channels), device.clone()),
+            num_groups,
+            eps,
+        }
+    }
+
+    /// ONE forward node (`nk_group_norm_fwd`) and ONE backward entry (`nk_group_norm_bwd`, `nk_group_norm_bwd_params`).
+    pub fn forward<D: Dimension + 'static>(&self, input: HipVarDiff<D>) -> HipVarDiff<D> {
+        input.group_norm(self.num_groups, self.weight.clone(), self.bias.clone(), self.eps)
+    }
+}
+
+/// Instance normalisation, torch's `InstanceNorm1d / 2d / 3d` with `affine = true`: group normalisation with one channel per group.
+/// Running statistics (`track_running_stats`) are not built: the statistics are always the input's own.
+macro_rules! instance_norm_layer {
+    ($name:ident, $rank:expr, $doc:expr) => {
+        #[doc = $doc]
+        pub struct $name {
+            pub weight: HipVarDiff<Ix1>,
+            pub bias: HipVarDiff<Ix1>,
+            pub num_features: usize,
+            pub eps: f64,
+        }
+
+        impl $name {
+            pub fn new(num_features: usize, eps: f64, device: &Device) -> Self {
+                Self {
+                    weight: HipVarDiff::parameter(&Array::ones(num_features), device.clone()),
+                    bias: HipVarDiff::parameter(&Array::zeros(num_features), device.clone()),
+                    num_features,
+                    eps,
+                }
+            }
+
+            pub fn forward<D: Dimension + 'static>(&self, input: HipVarDiff<D>) -> HipVarDiff<D> {
+                assert!(input.shape().len() == $rank, "{}: an input of {} dimensions", stringify!($name), input.shape().len());
+                input.group_norm(self.num_features, self.weight.clone(), self.bias.clone(), self.eps)
+            }
+        }
+    };
+}
+
+instance_norm_layer!(InstanceNorm1d, 3usize, "Instance normalisation of `(N, C, L)` inputs.");
+instance_norm_layer!(InstanceNorm2d, 4usize, "Instance normalisation of `(N, C, H, W)` inputs.");
+instance_norm_layer!(InstanceNorm3d, 5usize, "Instance normalisation of `(N, C, D, H, W)` inputs.");
+
 /// RMS normalisation over the trailing dimensions `normalized_shape` of the input (the reference has no normalisation layer;
 /// semantics in `include/neuronika_hip.h`): `y = x / sqrt(mean(x^2) + eps) * weight` per row, no centring and no bias, the
 /// normalisation of LLaMA-style decoders (`eps` = 1e-6 there).  `weight` starts as ones of `normalized_shape` (dimension `E`).

@@ -21,7 +21,7 @@ use super::{
         Convolution, ConvolutionBackwardInput, ConvolutionBackwardKernel, ConvolutionBackwardKernelBias, ConvolutionBackwardPadded, ConvolutionBias,
         ConvolutionBiasPadded, CrossEntropy, CrossEntropyBackward, Dropout, Embedding, EmbeddingBackward,
         AvgPool, AvgPoolBackward, MaxPool, MaxPoolBackward,
-        DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, RmsNorm, RmsNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
+        DropoutBackward, Heads, HeadsAttention, HeadsAttentionBackward, BatchNorm, BatchNormBackward, LayerNorm, LayerNormBackward, GroupNorm, GroupNormBackward, RmsNorm, RmsNormBackward, Linear, LinearBackward, LogSoftmax, LogSoftmaxBackward, MatrixMatrixMul, MatrixMatrixMulBackwardLeft,
         MatrixMatrixMulBackwardRight, MatrixMatrixMulT, MatrixMatrixMulTBackwardLeft, MatrixMatrixMulTBackwardRight, Mean, MeanBackward,
         decode_chunk, decode_paged_workspace, decode_window_workspace, decode_workspace, PackedDecodeAttention, PagedDecodeAttention,
         RepeatKv, RepeatKvBackward, RepeatKvGeometry, rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
@@ -291,6 +291,28 @@ where
 
     pub fn rms_norm<E: 'static + Dimension>(self, gamma: HipVar<E>, eps: f64) -> HipVar<D> {
         self.rms_norm_with_stats(gamma, eps, None)
+    }
+
+    /// Group normalisation of an `(N, C, spatial...)` input over `groups` channel groups, `gamma` / `beta` of shape `(C)`: ours,
+    /// the reference has no normalisation node.  `groups == C` is instance normalisation.  `stats` = the `{mean, rstd}` buffer per
+    /// `(sample, group)` a backward node will read, `None` for the no-gradient form (`group_norm`).
+    pub(crate) fn group_norm_with_stats(mut self, groups: usize, gamma: HipVar<Ix1>, beta: HipVar<Ix1>, eps: f64,
+                                        stats: Option<Shared<HipArray<Ix2>>>) -> HipVar<D> {
+        let xs = self.data.borrow().shape_c();
+        assert!(xs.len() >= 2, "group_norm: the input must have at least two dimensions (N, C, ...)");
+        let channels = xs[1] as usize;
+        assert!(groups > 0 && channels % groups == 0, "group_norm: the channel count must be a multiple of the group count");
+        assert!(gamma.data.borrow().len() == channels && beta.data.borrow().len() == channels, "group_norm: gamma and beta must have shape (C)");
+        assert!(eps >= 0.0 && eps.is_finite(), "group_norm: eps must be finite and not negative");
+        self.history.merge(gamma.history);
+        self.history.merge(beta.history);
+        let data = shared(self.data.borrow().dimension(), &self.device());
+        let op = GroupNorm::new(self.data, gamma.data, beta.data, data.clone(), stats, groups, eps);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    pub fn group_norm(self, groups: usize, gamma: HipVar<Ix1>, beta: HipVar<Ix1>, eps: f64) -> HipVar<D> {
+        self.group_norm_with_stats(groups, gamma, beta, eps, None)
     }
 
     /// Batch normalisation over `(N, spatial...)` for each channel of an `(N, C, spatial...)` input: ours, the reference has no
@@ -1168,6 +1190,21 @@ where
         let grad = self.new_grad(self.grad.shape());
         let var = self.var.rms_norm_with_stats(gamma.var, eps, Some(stats.clone()));
         let op: Rc<dyn Backward> = Rc::new(RmsNormBackward::new(input_data, gamma_data, stats, Some(self.grad.clone()), gamma.grad.clone(), grad.clone()));
+        HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
+    }
+
+    /// Group normalisation with differentiable parameters: ONE forward node and ONE backward entry writing the gradients of
+    /// `self`, `gamma` and `beta` (`GroupNormBackward`).
+    pub fn group_norm(mut self, groups: usize, gamma: HipVarDiff<Ix1>, beta: HipVarDiff<Ix1>, eps: f64) -> HipVarDiff<D> {
+        self.history.merge(gamma.history);
+        self.history.merge(beta.history);
+        let (input_data, gamma_data) = (self.var.data.clone(), gamma.var.data.clone());
+        let samples = input_data.borrow().shape_c().first().map_or(0, |&n| n as usize);
+        let stats = shared(Ix2(samples * groups, 2), &self.var.device());
+        let grad = self.new_grad(self.grad.shape());
+        let var = self.var.group_norm_with_stats(groups, gamma.var, beta.var, eps, Some(stats.clone()));
+        let op: Rc<dyn Backward> = Rc::new(GroupNormBackward::new(input_data, gamma_data, stats, groups, Some(self.grad.clone()), gamma.grad.clone(),
+                                                                   beta.grad.clone(), grad.clone()));
         HipVarDiff::node(var, grad.clone(), (op, grad), self.history)
     }
 

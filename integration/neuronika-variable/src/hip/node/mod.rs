@@ -3,7 +3,7 @@
 //! reference's ndarray nodes (`node/*/mod.rs`), so graph construction code is unchanged.  Written here: the nodes of
 //! the BASELINE configurations (MatMul / MatMulT, Convolution, broadcast binaries, ReLU, Softmax, Dropout, Sum,
 //! SquaredError, the fused attention core of the composed MHA) and their glue (LogSoftmax, Mean, Pad in all four modes, Chunk,
-//! MultiConcatenate, Transpose, the SGD / Adam steps) and the layer and batch normalisation and the max / average pooling the reference lacks.  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
+//! MultiConcatenate, Transpose, the SGD / Adam steps) and the layer, batch and group normalisation and the max / average pooling the reference lacks.  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
 mod activation;
 mod attention;
 mod binary_op;
@@ -11,6 +11,7 @@ mod convolution;
 mod cross_entropy;
 mod decode;
 mod embedding;
+mod group_norm;
 mod layout;
 mod linear;
 mod matrix_matrix_mul;
@@ -32,6 +33,7 @@ pub(crate) use convolution::*;
 pub(crate) use cross_entropy::*;
 pub(crate) use decode::*;
 pub(crate) use embedding::*;
+pub(crate) use group_norm::*;
 pub(crate) use layout::*;
 pub(crate) use linear::*;
 pub(crate) use matrix_matrix_mul::*;

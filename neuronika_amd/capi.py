@@ -191,6 +191,11 @@ _SIGS = {
     "nk_batch_norm_bwd_assign": [VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int],
     "nk_batch_norm_bwd_params": [VP, VP, VP, VP, C.c_int],
     "nk_batch_norm_bwd_params_assign": [VP, VP, VP, VP, C.c_int],
+    "nk_group_norm_fwd": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_double],
+    "nk_group_norm_bwd": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_longlong, C.c_int],
+    "nk_group_norm_bwd_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_longlong, C.c_int],
+    "nk_group_norm_bwd_params": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_longlong, C.c_int],
+    "nk_group_norm_bwd_params_assign": [VP, VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_longlong, C.c_int],
     "nk_pool_out_shape": [C.c_int, c_intp, c_intp, c_intp, c_intp, c_intp],
     "nk_max_pool_fwd": [VP, C.c_int, VP, c_intp, VP, VP, c_intp, c_intp, c_intp],
     "nk_max_pool_bwd": [VP, C.c_int, VP, c_intp, VP, VP, c_intp, c_intp, c_intp],
@@ -948,6 +953,22 @@ def batch_norm_bwd(dev, dx, g, x, gamma, stats, sums, N, C, L, assign=False):
 def batch_norm_bwd_params(dev, dgamma, dbeta, sums, C, assign=False):
     """either of `dgamma`, `dbeta` may be None"""
     check((lib.nk_batch_norm_bwd_params_assign if assign else lib.nk_batch_norm_bwd_params)(dev.h, _p(dgamma), _p(dbeta), _p(sums), int(C)))
+
+
+def group_norm_fwd(dev, x, gamma, beta, y, stats, N, C, L, G, eps=1e-5):
+    """x read as (N, C, L), G groups; `gamma`, `beta` (C,) and `stats` (N * G, 2) may be None"""
+    check(lib.nk_group_norm_fwd(dev.h, _p(x), _p(gamma), _p(beta), _p(y), _p(stats), int(N), int(C), int(L), int(G), float(eps)))
+
+
+def group_norm_bwd(dev, dx, g, x, gamma, stats, N, C, L, G, assign=False):
+    check((lib.nk_group_norm_bwd_assign if assign else lib.nk_group_norm_bwd)(dev.h, _p(dx), _p(g), _p(x), _p(gamma), _p(stats), int(N), int(C),
+                                                                              int(L), int(G)))
+
+
+def group_norm_bwd_params(dev, dgamma, dbeta, g, x, stats, N, C, L, G, assign=False):
+    """either of `dgamma`, `dbeta` may be None"""
+    check((lib.nk_group_norm_bwd_params_assign if assign else lib.nk_group_norm_bwd_params)(dev.h, _p(dgamma), _p(dbeta), _p(g), _p(x), _p(stats),
+                                                                                            int(N), int(C), int(L), int(G)))
 
 
 def pool_out_shape(x_shape, kernel, stride, padding):

@@ -309,6 +309,8 @@ int rms_norm_bwd_gamma(nk_device* dev, float* dgamma, const float* g, const floa
 
 }  // namespace
 
+#include "nk_group_norm.h"  // GroupNorm / InstanceNorm: its kernels and entry points, built on the helpers above
+
 extern "C" {
 
 int nk_layer_norm_fwd(nk_device* dev, const float* x, const float* gamma, const float* beta, float* y, float* stats, long long rows,
