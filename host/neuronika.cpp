@@ -1775,6 +1775,63 @@ VarDiff pool_diff(const char* what, const VarDiff& x, const std::vector<int>& ke
     bw->average = average; bw->count_include_pad = count_include_pad;
     return VarDiff::node(std::move(v), g, entry(bw, g), x.history);
 }
+// Upsampling (ours; the reference has no such node; semantics in neuronika_hip.h).  The mode's name is checked against the rank
+// when the graph is built; the extents are checked by the library at the first forward, as every geometry it owns.
+int upsample_mode(const std::string& mode, size_t nd) {
+    if (mode == "nearest") return NK_UPSAMPLE_NEAREST;
+    const char* linear[] = {"linear", "bilinear", "trilinear"};
+    for (size_t i = 0; i < 3; ++i)
+        if (mode == linear[i]) {
+            if (nd != i + 1) panic("upsample: mode \"" + mode + "\" is for " + std::to_string(i + 1) + " spatial axes, the input has " + std::to_string(nd));
+            return NK_UPSAMPLE_LINEAR;
+        }
+    panic("upsample: unknown mode \"" + mode + "\" (nearest, linear, bilinear, trilinear)");
+    return -1;
+}
+struct UpsampleFwd : Forward {
+    Shared<HipArray> x, y;
+    std::vector<int> out_size;
+    int mode = 0, align_corners = 0;
+    void forward() const override {
+        check(nk_upsample_fwd(D(x), (int)out_size.size(), mode, align_corners, x->ptr(), x->shape().data(), y->ptr(), out_size.data()));
+    }
+};
+struct UpsampleBwd : Backward {
+    Shared<Gradient> dx, g;
+    Shape x_shape;
+    std::vector<int> out_size;
+    int mode = 0, align_corners = 0;
+    void backward() const override {
+        const HipArray& G = g->borrow();
+        bool assign = false;
+        HipArray& d = dx->borrow_first_write(assign);
+        check((assign ? nk_upsample_bwd_assign : nk_upsample_bwd)(d.device()->raw(), (int)out_size.size(), mode, align_corners, d.ptr(), x_shape.data(),
+                                                                  G.ptr(), out_size.data()));
+    }
+    void targets(std::vector<const Gradient*>& out) const override { out.push_back(dx.get()); }
+};
+Shared<UpsampleFwd> upsample_fwd_node(const Var& x, const std::vector<int>& out_size, const std::string& mode, bool align_corners) {
+    const Shape& xs = x.shape();
+    if (xs.size() < 3 || xs.size() > 5) panic("upsample: the input must be (N, C, spatial...) with 1 to 3 spatial axes, got " + std::to_string(xs.size()) + " dimensions");
+    const size_t nd = xs.size() - 2;
+    if (out_size.size() != nd) panic("upsample: out_size has " + std::to_string(out_size.size()) + " entries for " + std::to_string(nd) + " spatial axes");
+    const int m = upsample_mode(mode, nd);
+    if (m == NK_UPSAMPLE_NEAREST && align_corners) panic("upsample: align_corners has no meaning for the nearest mode");
+    Shape ys(xs.begin(), xs.begin() + 2);
+    size_t plane = 1;
+    for (size_t i = 0; i < nd; ++i) {
+        if (xs[2 + i] < 1) panic("upsample: spatial extent " + std::to_string(xs[2 + i]) + " of spatial axis " + std::to_string(i));
+        if (out_size[i] < 1) panic("upsample: output extent " + std::to_string(out_size[i]) + " of spatial axis " + std::to_string(i) + " (must be >= 1)");
+        plane *= (size_t)out_size[i];
+        if (plane > (size_t)INT_MAX) panic("upsample: an output plane of more than 2^31 - 1 elements");
+        ys.push_back(out_size[i]);
+    }
+    auto n = std::make_shared<UpsampleFwd>();
+    n->x = x.data; n->y = zeros_like(x.data, ys);
+    n->out_size = out_size; n->mode = m; n->align_corners = align_corners;
+    return n;
+}
+
 std::vector<int> spatial_extents(const char* what, const Shape& s) {
     if (s.size() < 3 || s.size() > 5)
         panic(std::string(what) + ": the input must be (N, C, spatial...) with 1 to 3 spatial axes, got " + std::to_string(s.size()) + " dimensions");
@@ -2080,6 +2137,11 @@ Var Var::max_pool(const std::vector<int>& kernel, const std::vector<int>& stride
 }
 Var Var::avg_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding, bool count_include_pad) const {
     return pool_var("avg_pool", *this, kernel, stride, padding, true, count_include_pad);
+}
+Var Var::upsample(const std::vector<int>& out_size, const std::string& mode, bool align_corners) const {
+    auto n = upsample_fwd_node(*this, out_size, mode, align_corners);
+    auto y = n->y;
+    return Var::node(y, n, history);
 }
 Var Var::global_avg_pool() const {
     const std::vector<int> k = spatial_extents("global_avg_pool", shape());
@@ -2590,6 +2652,15 @@ VarDiff VarDiff::max_pool(const std::vector<int>& kernel, const std::vector<int>
 }
 VarDiff VarDiff::avg_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding, bool count_include_pad) const {
     return pool_diff("avg_pool", *this, kernel, stride, padding, true, count_include_pad);
+}
+VarDiff VarDiff::upsample(const std::vector<int>& out_size, const std::string& mode, bool align_corners) const {
+    auto n = upsample_fwd_node(var, out_size, mode, align_corners);
+    auto y = n->y;
+    Var v = Var::node(y, n, var.history);
+    auto g = std::make_shared<Gradient>(v.device(), v.shape());
+    auto bw = std::make_shared<UpsampleBwd>();
+    bw->dx = grad; bw->g = g; bw->x_shape = shape(); bw->out_size = n->out_size; bw->mode = n->mode; bw->align_corners = n->align_corners;
+    return VarDiff::node(std::move(v), g, entry(bw, g), history);
 }
 VarDiff VarDiff::global_avg_pool() const {
     const std::vector<int> k = spatial_extents("global_avg_pool", shape());
@@ -3156,6 +3227,35 @@ VarDiff PoolNd::forward(const VarDiff& input) const {
     check_input(input.shape());
     return average ? input.avg_pool(kernel_size, stride, padding, count_include_pad) : input.max_pool(kernel_size, stride, padding);
 }
+
+Upsample::Upsample(std::vector<int> size, std::vector<double> scale_factor, std::string mode, bool align_corners)
+    : size(std::move(size)), scale_factor(std::move(scale_factor)), mode(std::move(mode)), align_corners(align_corners) {
+    if (this->size.empty() == this->scale_factor.empty()) panic("Upsample: give either size or scale_factor, not both and not neither");
+    if (this->mode != "nearest" && this->mode != "linear" && this->mode != "bilinear" && this->mode != "trilinear")
+        panic("Upsample: unknown mode \"" + this->mode + "\" (nearest, linear, bilinear, trilinear)");
+    if (this->mode == "nearest" && align_corners) panic("Upsample: align_corners has no meaning for the nearest mode");
+    for (int s : this->size)
+        if (s < 1) panic("Upsample: size entries must be >= 1");
+    for (double s : this->scale_factor)
+        if (!std::isfinite(s) || s <= 0.0) panic("Upsample: scale_factor entries must be finite and positive");
+}
+std::vector<int> Upsample::output_size(const Shape& s) const {
+    if (s.size() < 3 || s.size() > 5) panic("Upsample: the input must be (N, C, spatial...) with 1 to 3 spatial axes, got " + std::to_string(s.size()) + " dimensions");
+    const size_t nd = s.size() - 2;
+    if (!size.empty()) {
+        if (size.size() != nd) panic("Upsample: size has " + std::to_string(size.size()) + " entries for " + std::to_string(nd) + " spatial axes");
+        return size;
+    }
+    if (scale_factor.size() != 1 && scale_factor.size() != nd)
+        panic("Upsample: scale_factor has " + std::to_string(scale_factor.size()) + " entries for " + std::to_string(nd) + " spatial axes (one, or one per axis)");
+    std::vector<double> sc(nd, scale_factor[0]);
+    if (scale_factor.size() == nd) sc = scale_factor;
+    std::vector<int> out(nd);
+    if (nk_upsample_out_size((int)nd, s.data(), sc.data(), out.data()) != NK_OK) panic(std::string("Upsample: ") + nk_last_error());
+    return out;
+}
+Var Upsample::forward(const Var& input) const { return input.upsample(output_size(input.shape()), mode, align_corners); }
+VarDiff Upsample::forward(const VarDiff& input) const { return input.upsample(output_size(input.shape()), mode, align_corners); }
 
 static VarDiff linear_node(const Linear& l, const Var& x, const Shared<Gradient>& dx, const History<BackwardEntry>* hx, bool relu = false) {
     const Shape& xs = x.shape();

@@ -331,6 +331,9 @@ class Var {
     Var avg_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding,
                  bool count_include_pad = true) const;
     Var global_avg_pool() const;
+    // Resampling of the spatial axes of an (N, C, spatial...) input to `out_size` (one entry per axis; ours: the reference has none;
+    // semantics in neuronika_hip.h): mode "nearest", or "linear" / "bilinear" / "trilinear" for 1 / 2 / 3 spatial axes.
+    Var upsample(const std::vector<int>& out_size, const std::string& mode = "nearest", bool align_corners = false) const;
     Var flatten() const;
     Var softmax(int axis) const;                      // var.rs:318
     Var log_softmax(int axis) const;                  // var.rs:338
@@ -490,6 +493,7 @@ class VarDiff {
     VarDiff avg_pool(const std::vector<int>& kernel, const std::vector<int>& stride, const std::vector<int>& padding,
                      bool count_include_pad = true) const;
     VarDiff global_avg_pool() const;
+    VarDiff upsample(const std::vector<int>& out_size, const std::string& mode = "nearest", bool align_corners = false) const;
     VarDiff flatten() const;
     VarDiff softmax(int axis) const;
     VarDiff log_softmax(int axis) const;
@@ -757,6 +761,20 @@ struct PoolNd {
     VarDiff forward(const VarDiff& input) const;
    private:
     void check_input(const Shape& s) const;
+};
+// torch's nn.Upsample (ours: the reference has none): either `size` (one entry per spatial axis) or `scale_factor` (one value, or one
+// per axis; out_i = floor(in_i * scale_i), then the index arithmetic sees in_i and out_i alone - torch's recompute_scale_factor=True),
+// never both.  `mode` is checked against the input's rank at forward: "nearest" for any, "linear" / "bilinear" / "trilinear" for
+// 1 / 2 / 3 spatial axes.  No parameters and no serde state.
+struct Upsample {
+    std::vector<int> size;
+    std::vector<double> scale_factor;
+    std::string mode;
+    bool align_corners;
+    Upsample(std::vector<int> size, std::vector<double> scale_factor, std::string mode = "nearest", bool align_corners = false);
+    std::vector<int> output_size(const Shape& input) const;
+    Var forward(const Var& input) const;
+    VarDiff forward(const VarDiff& input) const;
 };
 struct MaxPool1d : PoolNd {
     MaxPool1d(int kernel_size, int stride = 0, int padding = 0)

@@ -70,6 +70,7 @@ PYBIND11_MODULE(_tape, m) {
         .def("exp", &Var::exp).def("unsqueeze", &Var::unsqueeze)
         .def("max_pool", &Var::max_pool, py::arg("kernel"), py::arg("stride") = std::vector<int>{}, py::arg("padding") = std::vector<int>{})
         .def("avg_pool", &Var::avg_pool, py::arg("kernel"), py::arg("stride") = std::vector<int>{}, py::arg("padding") = std::vector<int>{}, py::arg("count_include_pad") = true)
+        .def("upsample", &Var::upsample, py::arg("out_size"), py::arg("mode") = "nearest", py::arg("align_corners") = false)
         .def("global_avg_pool", &Var::global_avg_pool).def("flatten", &Var::flatten)
         .def("softmax", &Var::softmax).def("log_softmax", &Var::log_softmax).def("t", &Var::t)
         .def("layer_norm", py::overload_cast<const Var&, const Var&, double>(&Var::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
@@ -156,6 +157,7 @@ PYBIND11_MODULE(_tape, m) {
         .def("exp", &VarDiff::exp).def("unsqueeze", &VarDiff::unsqueeze)
         .def("max_pool", &VarDiff::max_pool, py::arg("kernel"), py::arg("stride") = std::vector<int>{}, py::arg("padding") = std::vector<int>{})
         .def("avg_pool", &VarDiff::avg_pool, py::arg("kernel"), py::arg("stride") = std::vector<int>{}, py::arg("padding") = std::vector<int>{}, py::arg("count_include_pad") = true)
+        .def("upsample", &VarDiff::upsample, py::arg("out_size"), py::arg("mode") = "nearest", py::arg("align_corners") = false)
         .def("global_avg_pool", &VarDiff::global_avg_pool).def("flatten", &VarDiff::flatten)
         .def("softmax", &VarDiff::softmax).def("log_softmax", &VarDiff::log_softmax).def("t", &VarDiff::t)
         .def("layer_norm", py::overload_cast<const VarDiff&, const VarDiff&, double>(&VarDiff::layer_norm, py::const_), py::arg("gamma"), py::arg("beta"), py::arg("eps") = 1e-5)
@@ -513,6 +515,25 @@ PYBIND11_MODULE(_tape, m) {
     py::class_<nn::AvgPool3d, nn::PoolNd>(nn, "AvgPool3d")
         .def(py::init<std::vector<int>, std::vector<int>, std::vector<int>, bool>(), py::arg("kernel_size"), py::arg("stride") = std::vector<int>{},
              py::arg("padding") = std::vector<int>{}, py::arg("count_include_pad") = true);
+    py::class_<nn::Upsample>(nn, "Upsample")
+        .def(py::init([](py::object size, py::object scale_factor, std::string mode, bool align_corners) {
+                 // an int / a float stands for one entry, as in torch; None for "not given"
+                 std::vector<int> sz;
+                 std::vector<double> sc;
+                 if (!size.is_none()) sz = py::isinstance<py::int_>(size) ? std::vector<int>{size.cast<int>()} : size.cast<std::vector<int>>();
+                 if (!scale_factor.is_none())
+                     sc = (py::isinstance<py::float_>(scale_factor) || py::isinstance<py::int_>(scale_factor)) ? std::vector<double>{scale_factor.cast<double>()}
+                                                                                                              : scale_factor.cast<std::vector<double>>();
+                 return nn::Upsample(std::move(sz), std::move(sc), std::move(mode), align_corners);
+             }),
+             py::arg("size") = py::none(), py::arg("scale_factor") = py::none(), py::arg("mode") = "nearest", py::arg("align_corners") = false)
+        .def_readonly("size", &nn::Upsample::size)
+        .def_readonly("scale_factor", &nn::Upsample::scale_factor)
+        .def_readonly("mode", &nn::Upsample::mode)
+        .def_readonly("align_corners", &nn::Upsample::align_corners)
+        .def("output_size", [](const nn::Upsample& u, const std::vector<int>& shape) { return u.output_size(shape); }, py::arg("input_shape"))
+        .def("forward", py::overload_cast<const Var&>(&nn::Upsample::forward, py::const_))
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::Upsample::forward, py::const_));
     py::class_<nn::Dropout>(nn, "Dropout")
         .def(py::init<double>())
         .def("train", &nn::Dropout::train)

@@ -828,6 +828,53 @@ int nk_avg_pool_bwd(nk_device* dev, int nd, float* dx, const int* x_shape, const
 int nk_avg_pool_bwd_assign(nk_device* dev, int nd, float* dx, const int* x_shape, const float* g, const int* kernel,
                            const int* stride, const int* padding, int count_include_pad);
 
+/* ------------------------------------------------------------------ upsampling */
+/* Resampling of a contiguous f32 tensor x of shape (N, C, in_1 .. in_nd), nd = 1, 2, 3, to y of shape (N, C, out_1 .. out_nd).  The
+ * reference has no such layer; the semantics are fixed here and they are torch's nn.Upsample / F.interpolate called with `size=`
+ * (or with recompute_scale_factor=True): per axis, in_i and out_i are all the index arithmetic sees.  x_shape has 2 + nd entries,
+ * out_size nd entries.  nk_upsample_out_size is the host arithmetic from a scale: out_i = floor(in_i * scale_i) in f64 (scale: nd
+ * entries; no device is needed).  NK_ERR_INVALID, with nothing launched and nothing written: nd outside 1..3, an unknown mode,
+ * align_corners != 0 with the nearest mode, a negative N or C, in_i < 1, out_i < 1, a scale that is not finite or not positive, or a
+ * plane (prod in_i or prod out_i) that does not fit in 31 bits.  Element offsets are 64-bit.  N * C == 0 returns NK_OK and writes
+ * nothing, the _assign twin included.
+ * Nearest, in integers:  src(o) = min((o * in) / out, in - 1)  (64-bit integer division) per axis; y is a copy of the selected
+ *   element's bits (a NaN, an infinity and -0.0 included).  torch forms the index through a rounded f32 scale and gives another
+ *   index for some pairs: 83 of the (in, out) with in <= 64 and out <= 129, (2, 82) and (14, 46) among them, none of them an integer
+ *   factor below 41.  The integer form is the definition.
+ * Linear (bilinear over two axes, trilinear over three), per axis, all in f32, every operation rounded on its own (no FMA):
+ *   align_corners == 0:  s = (float)in / (float)out;                                  src = max(s * (o + 0.5f) - 0.5f, 0)
+ *   align_corners != 0:  s = out == 1 ? 0 : (float)(in - 1) / (float)(out - 1);       src = s * o
+ *   i0 = min((int)floorf(src), in - 1);  i1 = min(i0 + 1, in - 1);  l1 = src - (float)i0;  l0 = 1 - l1
+ *   An output is l0 * a + l1 * b - two products and one sum - applied along the innermost axis first, then outward:
+ *   top = l0w * x00 + l1w * x01, bot = l0w * x10 + l1w * x11, y = l0h * top + l1h * bot, and the depth pair after that.  An axis
+ *   that is not there (nd < 3) contributes no operation.  A non-finite input propagates as these operations propagate it.
+ *   Downsampling is not antialiased (torch's default).
+ * bwd:  dx[i] += total(i), one add.  total(i) is the f32 sum, from 0, of w * g[o] over the outputs o of the element's own (n, c)
+ *   plane in ascending row-major order and, within an output, over its 2^nd corners in row-major corner order, counting the corners
+ *   that land on i (a clamped edge with i0 == i1 gives both).  The weight of a corner is built innermost first: w = l_w; w = l_h * w;
+ *   w = l_d * w.  Nearest has one corner of weight 1 and multiplies nothing.  Input elements that no output reads get 0 (or += 0).
+ *   The forward and the backward take (i0, i1, l0, l1) from one device function, so their weights agree to the bit.
+ * No atomics: the backward is a gather - a thread owns input elements and walks, per axis, a range of candidate outputs that surely
+ * holds every reader (nearest: the exact range ceil(i * out / in) .. ceil((i + 1) * out / in) - 1).  The order of every sum is a
+ * function of the geometry alone: every result repeats bit for bit, whatever the class.  Nothing here synchronises, allocates or
+ * uses the workspace, and no block waits on another: every call can be captured into a graph.
+ * Kernel classes, chosen inside each call from (mode, in, out) and the pointers' 16-byte alignment; all give the same bits:
+ *   nearest x2  nearest with out_W == 2 in_W, in_W % 4 == 0 and both pointers 16-byte aligned, any ratio on the outer axes: a lane
+ *               loads 16 bytes of x and stores two 16-byte groups per output row it feeds; backward, a lane owns 16 bytes of dx and
+ *               reads g in 16-byte loads.
+ *   vector      forward: out_W % 4 == 0 and y aligned - a lane makes four adjacent outputs and stores 16 bytes; backward:
+ *               in_W % 4 == 0 and dx aligned - a lane owns 16 bytes of dx.
+ *   generic     scalar, any shape, any alignment.
+ * The `_assign` twin writes what `+=` would leave in an all-zero dx, without reading it. */
+enum { NK_UPSAMPLE_NEAREST = 0, NK_UPSAMPLE_LINEAR = 1 };
+int nk_upsample_out_size(int nd, const int* x_shape, const double* scale, int* out_size);
+int nk_upsample_fwd(nk_device* dev, int nd, int mode, int align_corners, const float* x, const int* x_shape, float* y,
+                    const int* out_size);
+int nk_upsample_bwd(nk_device* dev, int nd, int mode, int align_corners, float* dx, const int* x_shape, const float* g,
+                    const int* out_size);
+int nk_upsample_bwd_assign(nk_device* dev, int nd, int mode, int align_corners, float* dx, const int* x_shape, const float* g,
+                           const int* out_size);
+
 /* ------------------------------------------------------------------ fused attention core ---
  * The composed multi-head attention's per-(sample, head) chain in one kernel per direction (SURVEY.md 8a note; the
  * composition is MatrixMatrixMulT node/matrix_matrix_mul_t/mod.rs:31-41, Multiplication node/multiplication/mod.rs:39-50,

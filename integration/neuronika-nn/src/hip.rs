@@ -177,6 +177,44 @@ pool_layer!(AvgPool1d, 1usize, true, "Average pooling of `(N, C, L)` inputs (`co
 pool_layer!(AvgPool2d, 2usize, true, "Average pooling of `(N, C, H, W)` inputs (`count_include_pad` is a public field, `true` after `new`).");
 pool_layer!(AvgPool3d, 3usize, true, "Average pooling of `(N, C, D, H, W)` inputs (`count_include_pad` is a public field, `true` after `new`).");
 
+/// torch's `nn.Upsample` (the reference has none; semantics in `include/neuronika_hip.h`): either `size` (one entry per spatial axis)
+/// or `scale_factor` (one value, or one per axis; `out_i = floor(in_i * scale_i)` in f64, after which the index arithmetic sees `in_i`
+/// and `out_i` alone), never both.  `mode` is "nearest", or "linear" / "bilinear" / "trilinear" for 1 / 2 / 3 spatial axes, checked
+/// against the input's rank at `forward`.  No parameters.
+pub struct Upsample {
+    pub size: Vec<usize>,
+    pub scale_factor: Vec<f64>,
+    pub mode: String,
+    pub align_corners: bool,
+}
+
+impl Upsample {
+    pub fn new(size: &[usize], scale_factor: &[f64], mode: &str, align_corners: bool) -> Self {
+        assert!(size.is_empty() != scale_factor.is_empty(), "Upsample: give either size or scale_factor, not both and not neither");
+        assert!(["nearest", "linear", "bilinear", "trilinear"].contains(&mode), "Upsample: unknown mode {:?}", mode);
+        assert!(mode != "nearest" || !align_corners, "Upsample: align_corners has no meaning for the nearest mode");
+        assert!(scale_factor.iter().all(|s| s.is_finite() && *s > 0.0), "Upsample: scale_factor entries must be finite and positive");
+        Self { size: size.to_vec(), scale_factor: scale_factor.to_vec(), mode: mode.to_string(), align_corners }
+    }
+
+    /// The output extents for an input of this shape (what `nk_upsample_out_size` computes).
+    pub fn output_size(&self, input_shape: &[usize]) -> Vec<usize> {
+        let nd = input_shape.len().saturating_sub(2);
+        if !self.size.is_empty() {
+            assert!(self.size.len() == nd, "Upsample: size takes {} entries", nd);
+            return self.size.clone();
+        }
+        assert!(self.scale_factor.len() == 1 || self.scale_factor.len() == nd, "Upsample: scale_factor takes one entry, or {}", nd);
+        (0..nd).map(|i| (input_shape[2 + i] as f64 * self.scale_factor[if self.scale_factor.len() == 1 { 0 } else { i }]).floor() as usize).collect()
+    }
+
+    /// ONE forward node and ONE backward entry (`nk_upsample_fwd` / `nk_upsample_bwd`).
+    pub fn forward<D: Dimension + 'static>(&self, input: HipVarDiff<D>) -> HipVarDiff<D> {
+        let out = self.output_size(&input.shape());
+        input.upsample(&out, &self.mode, self.align_corners)
+    }
+}
+
 /// Layer normalisation over the trailing dimensions `normalized_shape` of the input (the reference has no normalisation layer;
 /// semantics in `include/neuronika_hip.h`): `y = (x - mean) / sqrt(var + eps) * weight + bias` per row, biased variance.
 /// `weight` starts as ones, `bias` as zeros, both of `normalized_shape` (dimension `E`).

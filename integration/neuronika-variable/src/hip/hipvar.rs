@@ -26,6 +26,7 @@ use super::{
         decode_chunk, decode_paged_workspace, decode_window_workspace, decode_workspace, PackedDecodeAttention, PagedDecodeAttention,
         RepeatKv, RepeatKvBackward, RepeatKvGeometry, rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
         sample_stage_limit, Sample, SampleParams,
+        Upsample, UpsampleBackward, UpsampleGeometry, UpsampleMode,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
         ReLUBackward, ReluMask, Softmax, SoftmaxBackward,
         SquaredError, SquaredErrorBackward, Sum, SumBackward, Transpose, TransposeBackward,
@@ -59,6 +60,26 @@ fn pool_setup<D: Dimension>(dim: &D, kernel: &[usize], stride: &[usize], padding
         *o = y as usize;
     }
     (out, k, s, p)
+}
+
+/// Host side of the upsampling geometry (`nk_upsample_fwd` holds the rules): the mode by its torch name, checked against the number of
+/// spatial axes, and the output dimension `(N, C, out...)`.
+fn upsample_setup<D: Dimension>(dim: &D, out_size: &[usize], mode: &str, align_corners: bool) -> (D, UpsampleGeometry) {
+    let nd = dim.ndim().saturating_sub(2);
+    assert!((1..=3).contains(&nd), "upsample: the input must be (N, C, spatial...) with 1 to 3 spatial axes");
+    assert!(out_size.len() == nd, "upsample: out_size takes {} entries", nd);
+    let mode = match (mode, nd) {
+        ("nearest", _) => UpsampleMode::Nearest,
+        ("linear", 1) | ("bilinear", 2) | ("trilinear", 3) => UpsampleMode::Linear,
+        _ => panic!("upsample: mode {:?} does not fit {} spatial axes (nearest, linear, bilinear, trilinear)", mode, nd),
+    };
+    assert!(mode == UpsampleMode::Linear || !align_corners, "upsample: align_corners has no meaning for the nearest mode");
+    assert!(out_size.iter().all(|&e| e >= 1), "upsample: output extents must be >= 1");
+    let mut out = dim.clone();
+    for (o, &e) in out.slice_mut()[2..].iter_mut().zip(out_size) {
+        *o = e;
+    }
+    (out, UpsampleGeometry { out_size: out_size.iter().map(|&e| e as i32).collect(), mode, align_corners })
 }
 
 fn shared<D: Dimension>(dim: D, device: &Device) -> Shared<HipArray<D>> {
@@ -367,6 +388,15 @@ where
         let (dim, k, s, p) = pool_setup(&self.data.borrow().dimension(), kernel, stride, padding);
         let data = shared(dim, &self.device());
         let op = AvgPool::new(self.data, data.clone(), k, s, p, count_include_pad);
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
+    /// Nearest or linear resampling of the spatial axes to `out_size` (ours, the reference has none; semantics in
+    /// `include/neuronika_hip.h`): `mode` is "nearest", or "linear" / "bilinear" / "trilinear" for 1 / 2 / 3 spatial axes.
+    pub fn upsample(self, out_size: &[usize], mode: &str, align_corners: bool) -> HipVar<D> {
+        let (dim, geometry) = upsample_setup(&self.data.borrow().dimension(), out_size, mode, align_corners);
+        let data = shared(dim, &self.device());
+        let op = Upsample::new(self.data, data.clone(), geometry);
         HipVar::node(data, Rc::new(op), self.history)
     }
 
@@ -1240,6 +1270,15 @@ where
         let grad = self.new_grad(dim);
         let var = self.var.avg_pool(kernel, stride, padding, count_include_pad);
         let op = AvgPoolBackward::new(self.grad.clone(), grad.clone(), k, s, p, count_include_pad);
+        HipVarDiff::node(var, grad.clone(), (Rc::new(op), grad), self.history)
+    }
+
+    /// Upsampling: the backward node gathers, per input element, from the outputs that read it (`nk_upsample_bwd`).
+    pub fn upsample(self, out_size: &[usize], mode: &str, align_corners: bool) -> HipVarDiff<D> {
+        let (dim, geometry) = upsample_setup(&self.var.data.borrow().dimension(), out_size, mode, align_corners);
+        let grad = self.new_grad(dim);
+        let var = self.var.upsample(out_size, mode, align_corners);
+        let op = UpsampleBackward::new(self.grad.clone(), grad.clone(), geometry);
         HipVarDiff::node(var, grad.clone(), (Rc::new(op), grad), self.history)
     }
 

@@ -3,7 +3,7 @@
 //! reference's ndarray nodes (`node/*/mod.rs`), so graph construction code is unchanged.  Written here: the nodes of
 //! the BASELINE configurations (MatMul / MatMulT, Convolution, broadcast binaries, ReLU, Softmax, Dropout, Sum,
 //! SquaredError, the fused attention core of the composed MHA) and their glue (LogSoftmax, Mean, Pad in all four modes, Chunk,
-//! MultiConcatenate, Transpose, the SGD / Adam steps) and the layer, batch and group normalisation and the max / average pooling the reference lacks.  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
+//! MultiConcatenate, Transpose, the SGD / Adam steps) and the layer, batch and group normalisation and the max / average pooling and the upsampling the reference lacks.  Every node is constructed by a `HipVar` / `HipVarDiff` method (`hipvar.rs`).
 mod activation;
 mod attention;
 mod binary_op;
@@ -25,6 +25,7 @@ mod repeat_kv;
 mod rms_norm;
 mod rope;
 mod sample;
+mod upsample;
 
 pub(crate) use activation::*;
 pub(crate) use attention::*;
@@ -47,6 +48,7 @@ pub(crate) use repeat_kv::*;
 pub(crate) use rms_norm::*;
 pub(crate) use rope::*;
 pub(crate) use sample::*;
+pub(crate) use upsample::*;
 
 use std::rc::Rc;
 

@@ -203,6 +203,10 @@ _SIGS = {
     "nk_avg_pool_fwd": [VP, C.c_int, VP, c_intp, VP, c_intp, c_intp, c_intp, C.c_int],
     "nk_avg_pool_bwd": [VP, C.c_int, VP, c_intp, VP, c_intp, c_intp, c_intp, C.c_int],
     "nk_avg_pool_bwd_assign": [VP, C.c_int, VP, c_intp, VP, c_intp, c_intp, c_intp, C.c_int],
+    "nk_upsample_out_size": [C.c_int, c_intp, C.POINTER(C.c_double), c_intp],
+    "nk_upsample_fwd": [VP, C.c_int, C.c_int, C.c_int, VP, c_intp, VP, c_intp],
+    "nk_upsample_bwd": [VP, C.c_int, C.c_int, C.c_int, VP, c_intp, VP, c_intp],
+    "nk_upsample_bwd_assign": [VP, C.c_int, C.c_int, C.c_int, VP, c_intp, VP, c_intp],
     "nk_attention_supported": [C.c_int, C.c_int, C.c_double, C.c_int],
     "nk_attention_fwd": [VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_attention_bwd": [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double,
@@ -997,6 +1001,35 @@ def avg_pool_fwd(dev, x, x_shape, y, kernel, stride, padding, count_include_pad=
 def avg_pool_bwd(dev, dx, x_shape, g, kernel, stride, padding, count_include_pad=True, assign=False):
     check((lib.nk_avg_pool_bwd_assign if assign else lib.nk_avg_pool_bwd)(dev.h, len(x_shape) - 2, _p(dx), ints(x_shape), _p(g), ints(kernel), ints(stride),
                                                                           ints(padding), int(bool(count_include_pad))))
+
+
+UPSAMPLE_NEAREST, UPSAMPLE_LINEAR = 0, 1
+_UPSAMPLE_MODES = {"nearest": UPSAMPLE_NEAREST, "linear": UPSAMPLE_LINEAR, "bilinear": UPSAMPLE_LINEAR, "trilinear": UPSAMPLE_LINEAR}
+
+
+def _upsample_mode(mode):
+    return _UPSAMPLE_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def upsample_out_size(x_shape, scale):
+    """nk_upsample_out_size: out_i = floor(in_i * scale_i) in f64, `scale` one value or one per spatial axis; raises
+    NeuronikaHipError for a scale or a geometry outside the header's contract.  Needs no device."""
+    nd = len(x_shape) - 2
+    sc = [float(scale)] * max(nd, 0) if not hasattr(scale, "__len__") else [float(v) for v in scale]
+    out = (C.c_int * max(1, nd))()
+    check(lib.nk_upsample_out_size(nd, ints(x_shape), (C.c_double * max(1, len(sc)))(*sc), out))
+    return tuple(out[i] for i in range(nd))
+
+
+def upsample_fwd(dev, x, x_shape, y, out_size, mode="nearest", align_corners=False):
+    """`x_shape` = (N, C, in...) and `out_size` = (out...) give the geometry (`x`, `y` may be flat or offset views); `mode`: a name
+    ("nearest", "linear", "bilinear", "trilinear") or the header's integer"""
+    check(lib.nk_upsample_fwd(dev.h, len(x_shape) - 2, _upsample_mode(mode), int(align_corners), _p(x), ints(x_shape), _p(y), ints(out_size)))
+
+
+def upsample_bwd(dev, dx, x_shape, g, out_size, mode="nearest", align_corners=False, assign=False):
+    check((lib.nk_upsample_bwd_assign if assign else lib.nk_upsample_bwd)(dev.h, len(x_shape) - 2, _upsample_mode(mode), int(align_corners), _p(dx),
+                                                                          ints(x_shape), _p(g), ints(out_size)))
 
 
 def embedding_fwd(dev, weight, idx, out, n, V, D):

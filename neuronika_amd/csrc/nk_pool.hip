@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 
 namespace {
 
@@ -605,3 +606,6 @@ int nk_avg_pool_bwd_assign(nk_device* dev, int nd, float* dx, const int* x_shape
 }
 
 }  // extern "C"
+
+// nn::Upsample: its kernels, host code and entry points (this unit's pool_al16 / pool_grid serve it)
+#include "nk_upsample.h"
