@@ -20,6 +20,12 @@ K and V per token instead of the causal forward over the whole prefix.
                                                       # however long the generation runs (here past three times the ring); without
                                                       # --rolling the caches are linear, long enough for the whole run, and the ids
                                                       # are the same
+    python examples/generate.py [new_tokens] --quant 8 [--group 32]    # weight-only quantised decoding: every step's projections read
+                                                      # int8 (or --quant 4: int4) weights with per-group f32 scales (--group 32 / 64 /
+                                                      # 128, default one scale per row) - `mha.quantize` for q / k / v / o,
+                                                      # `nn.QuantLinear` for the MLP and the head; a twin model with the same seeds
+                                                      # keeps its f32 weights, runs the same ids, and the largest difference of any
+                                                      # step's logits between the two is printed (information, not a check)
 
 The weights are random (fixed seeds): the text means nothing, the mechanics are the point.  The last lines compare every step's
 logits with those of the full causal forward over the same prefix."""
@@ -46,13 +52,20 @@ class Block:
         self.mha.window = window                                         # 0: every position attends to its whole prefix
         self.up, self.down = nk.nn.Linear(dev, D_MODEL, 4 * D_MODEL, seed + 20), nk.nn.Linear(dev, 4 * D_MODEL, D_MODEL, seed + 22)
         self.act = nk.nn.GELU()
+        self.qup = self.qdown = None
 
-    def mlp(self, h):
-        return self.down.forward(self.act.forward(self.up.forward(self.ln2.forward(h)))) + h
+    def quantize(self, nk, bits, group):
+        """the step's weights as int8 / int4 images; `full` keeps reading the f32 ones"""
+        self.mha.quantize(bits, group)
+        self.qup, self.qdown = nk.nn.QuantLinear(self.up, bits, group), nk.nn.QuantLinear(self.down, bits, group)
+
+    def mlp(self, h, up=None, down=None):
+        up, down = up or self.up, down or self.down
+        return down.forward(self.act.forward(up.forward(self.ln2.forward(h)))) + h
 
     def step(self, h, batch, cache):
         """the new positions only; `cache` holds this layer's keys and values"""
-        return self.mlp(self.mha.forward_step(self.ln1.forward(h), batch, cache) + h)
+        return self.mlp(self.mha.forward_step(self.ln1.forward(h), batch, cache) + h, self.qup, self.qdown)
 
     def full(self, h, batch):
         """every position at once: the causal forward"""
@@ -69,6 +82,12 @@ class Decoder:
         self.rope = nk.nn.RotaryEmbedding(dev, D_MODEL // HEADS, context) if rope else None
         self.blocks = [Block(nk, dev, 100 * (i + 1), self.rope, norm, kv_heads, window) for i in range(LAYERS)]
         self.ln, self.head = norm(dev, [D_MODEL]), nk.nn.Linear(dev, D_MODEL, VOCAB, 7)
+        self.qhead = None
+
+    def quantize(self, bits, group):
+        for block in self.blocks:
+            block.quantize(self.nk, bits, group)
+        self.qhead = self.nk.nn.QuantLinear(self.head, bits, group)
 
     def embed(self, ids, first, shape=None):
         """ids (batch, T) at positions first .. first + T - 1 -> (batch * T, d_model); a device Var of batch * T ids comes with its
@@ -87,7 +106,7 @@ class Decoder:
         h = self.embed(ids, first, shape)
         for block, cache in zip(self.blocks, caches):
             h = block.step(h, batch, cache)
-        out = self.head.forward(self.ln.forward(h))
+        out = (self.qhead or self.head).forward(self.ln.forward(h))
         out.forward()
         return out
 
@@ -123,7 +142,7 @@ def generate_on_device(nk, dev, model, prompt, new_tokens, caches, temperature, 
 
 
 def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=0, top_p=1.0, seed=0, rmsnorm=False, kv_heads=HEADS, window=0,
-         rolling=False):
+         rolling=False, quant=0, group=0):
     import neuronika_amd
     nk = neuronika_amd.tape
     dev = nk.Device(0)
@@ -135,16 +154,26 @@ def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=
     model = Decoder(nk, dev, rope, rmsnorm, kv_heads, window, context)
     # a linear cache holds every position of the run; a rolling one the window and the prompt's rows, whatever the length
     slots, ring = (window + n - 1, dict(rolling=True)) if rolling else (context, dict())
-    caches = [nk.nn.KvCache(dev, batch, kv_heads, D_MODEL // HEADS, slots, **ring) for _ in range(LAYERS)]   # kv_heads heads per layer
+    new_caches = lambda: [nk.nn.KvCache(dev, batch, kv_heads, D_MODEL // HEADS, slots, **ring) for _ in range(LAYERS)]   # kv_heads heads per layer
+    caches = new_caches()
+    twin, apart = None, 0.0
+    if quant:
+        assert not device_sample, "--quant compares every step with an f32 twin on the host path"
+        model.quantize(quant, group)
+        twin, twin_caches = Decoder(nk, dev, rope, rmsnorm, kv_heads, window, context), new_caches()   # same seeds, f32 weights
     if device_sample:
         ids, worst = generate_on_device(nk, dev, model, prompt, new_tokens, caches, temperature, top_k, top_p, seed)
     else:
         logits = model.logits_step(prompt, 0, caches)                    # prefill: every prompt position in one step
+        if twin:
+            apart = float(np.abs(logits - twin.logits_step(prompt, 0, twin_caches)).max())
         ids, worst = prompt, 0.0
         for _ in range(new_tokens):
             nxt = logits[:, -1].argmax(axis=1).reshape(batch, 1)
             ids = np.concatenate([ids, nxt], axis=1)
             logits = model.logits_step(nxt, ids.shape[1] - 1, caches)    # one token through the layers, K and V from the caches
+            if twin:
+                apart = max(apart, float(np.abs(logits - twin.logits_step(nxt, ids.shape[1] - 1, twin_caches)).max()))
             worst = max(worst, float(np.abs(logits[:, -1] - model.logits_full(ids)[:, -1]).max()))
     assert caches[0].lens() == [n + new_tokens] * batch
     if rolling:
@@ -152,6 +181,9 @@ def main(new_tokens=16, rope=False, device_sample=False, temperature=0.0, top_k=
     print("prompt   ", prompt[0].tolist())
     print("generated", ids[0, n:].tolist())
     print("largest difference between a step's logits and the full causal forward's: %.3g" % worst)
+    if twin:
+        print("int%d weights (group %s): largest difference of a step's logits from the f32 model's on the same ids: %.3g"
+              % (quant, group or "row", apart))
     return ids, worst
 
 
@@ -168,6 +200,8 @@ if __name__ == "__main__":
     ap.add_argument("--top-k", type=int, default=0, help="with --device-sample: 0 = off")
     ap.add_argument("--top-p", type=float, default=1.0, help="with --device-sample: 1 = off")
     ap.add_argument("--seed", type=int, default=0, help="with --device-sample: the Philox key of the draws")
+    ap.add_argument("--quant", type=int, default=0, choices=[0, 8, 4], help="weight-only quantised decoding: int8 or int4 weights in every step (0 = off)")
+    ap.add_argument("--group", type=int, default=0, choices=[0, 32, 64, 128], help="with --quant: weights per f32 scale (0 = one scale per row)")
     a = ap.parse_args()
     main(a.new_tokens, rope=a.rope, device_sample=a.device_sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed, rmsnorm=a.rmsnorm,
-         kv_heads=a.kv_heads, window=a.window, rolling=a.rolling)
+         kv_heads=a.kv_heads, window=a.window, rolling=a.rolling, quant=a.quant, group=a.group)

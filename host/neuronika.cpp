@@ -1003,6 +1003,7 @@ struct DecodeStepFwd : Forward {
     int window = 0;             // > 0: every step the core does not take runs nk_attention_decode_window_fwd
     bool ring = false;          // a rolling cache: position p at slot p % cap
     Shared<HipArray> x, w[3], b[3], wo, bo;  // packed: w[0] / b[0] are the (d + 2 dkv, d) / (d + 2 dkv) storage, the others null
+    nn::QuantImage qw[3], qwo;               // MultiheadAttention::quantize: the images of w[i] / wo the projections read instead; null without
     Shared<HipArray> qkv, q, k, v, ctx, out;
     Shared<HipArray> kc, vc, ws, start;
     Shared<HipArray> qf, kf, vf;  // grouped prefill on the core: K and V repeated to (n, d); qf: Q out of the packed buffer, contiguous
@@ -1013,17 +1014,23 @@ struct DecodeStepFwd : Forward {
     // page > 0: kc / vc are the pools of a PagedKvCache, cap is unused.  `start` then holds, in one upload, the B starts, the
     // (B, max_pages) table rows and the ncopy (src | dst) page ids of the copies reserve() asked for
     int page = 0, max_pages = 0, num_pages = 0, ncopy = 0;
+    // y (n, out) = in (n, k) . W^T + bias: the f32 weight, or its quantised image when the node was built with one
+    static void project(nk_device* dev, const Shared<HipArray>& in, const Shared<HipArray>& wt, const nn::QuantImage& img,
+                        const Shared<HipArray>& bias, const Shared<HipArray>& y, int n, int k, int out) {
+        if (img) check(nk_quant_linear_fwd(dev, in->ptr(), k, img.qweight->ptr(), img.scales->ptr(), bias->ptr(), y->ptr(), out, n, out, k, img.bits, img.group));
+        else check(nk_linear_fwd(dev, in->ptr(), wt->ptr(), bias->ptr(), y->ptr(), n, k, out));
+    }
     void forward() const override {
         nk_device* dev = D(x);
         const int n = B * T, d = H * dh, dkv = Hkv * dh;
         const float *Q, *K, *V;
         int ld, ldkv;
         if (qkv) {
-            check(nk_linear_fwd(dev, x->ptr(), w[0]->ptr(), b[0]->ptr(), qkv->ptr(), n, d, d + 2 * dkv));
+            project(dev, x, w[0], qw[0], b[0], qkv, n, d, d + 2 * dkv);
             Q = qkv->ptr(); K = Q + d; V = Q + d + dkv; ld = ldkv = d + 2 * dkv;
         } else {
             Shared<HipArray> y[3] = {q, k, v};
-            for (int i = 0; i < 3; ++i) check(nk_linear_fwd(dev, x->ptr(), w[i]->ptr(), b[i]->ptr(), y[i]->ptr(), n, d, i == 0 ? d : dkv));
+            for (int i = 0; i < 3; ++i) project(dev, x, w[i], qw[i], b[i], y[i], n, d, i == 0 ? d : dkv);
             Q = q->ptr(); K = k->ptr(); V = v->ptr(); ld = d; ldkv = dkv;
         }
         const int* st = reinterpret_cast<const int*>(start->ptr());
@@ -1061,7 +1068,19 @@ struct DecodeStepFwd : Forward {
             check(nk_attention_decode_gqa_fwd(dev, Q, ld, kc->ptr(), vc->ptr(), st, ctx->ptr(), ws->ptr(), B, T, H, Hkv, dh, cap, scale));
         else
             check(nk_attention_decode_fwd(dev, Q, ld, kc->ptr(), vc->ptr(), st, ctx->ptr(), ws->ptr(), B, T, H, dh, cap, scale));
-        check(nk_linear_fwd(dev, ctx->ptr(), wo->ptr(), bo->ptr(), out->ptr(), n, d, d));
+        project(dev, ctx, wo, qwo, bo, out, n, d, d);
+    }
+};
+
+// nn::QuantLinear::forward (ours; semantics at nk_quant_linear_fwd in neuronika_hip.h): (rows, in) -> (rows, out) on the packed integer
+// weights.  No backward node: the layer is inference-only.
+struct QuantLinearFwd : Forward {
+    Shared<HipArray> x, bias, y;
+    nn::QuantImage img;
+    int rows = 0, in = 0, out = 0;
+    void forward() const override {
+        check(nk_quant_linear_fwd(D(x), x->ptr(), in, img.qweight->ptr(), img.scales->ptr(), bias ? bias->ptr() : nullptr, y->ptr(), out, rows, out, in,
+                                  img.bits, img.group));
     }
 };
 
@@ -3585,6 +3604,66 @@ Sampler::Sampler(DevicePtr dev_, float temperature_, int top_k_, float top_p_, u
 Var Sampler::forward(const Var& logits, int batch) const { return logits.sample(*this, batch); }
 Var Sampler::forward(const VarDiff& logits, int batch) const { return logits.var.sample(*this, batch); }
 
+// The image of a (N, K) weight, packed on the device (nk_quant_linear_pack)
+static QuantImage quant_image(const char* who, const Shared<HipArray>& w, int N, int K, int bits, int group) {
+    const size_t words = nk_quant_linear_words(N, K, bits), ns = nk_quant_linear_scales(N, K, group);
+    if (words == 0 || ns == 0)
+        panic(std::string(who) + ": bits must be 8 or 4, group 32, 64, 128 or 0, and the input extent (" + std::to_string(K) +
+              ") a multiple of 32 and of the group; got bits = " + std::to_string(bits) + ", group = " + std::to_string(group));
+    QuantImage img;
+    img.bits = bits; img.group = group;
+    img.qweight = std::make_shared<HipArray>(w->device(), Shape{(int)words}, HipArray::Uninit{});
+    img.scales = std::make_shared<HipArray>(w->device(), Shape{N, (int)(ns / (size_t)N)}, HipArray::Uninit{});
+    check(nk_quant_linear_pack(D(w), w->ptr(), K, img.qweight->ptr(), img.scales->ptr(), N, K, bits, group));
+    return img;
+}
+QuantLinear::QuantLinear(const Linear& lin, int bits_, int group_) : bits(bits_), group(group_) {
+    const Shape& ws = lin.weight.shape();
+    if (ws.size() != 2 || lin.bias.shape() != Shape{ws[0]}) panic("QuantLinear: the Linear must hold an (out, in) weight and an (out) bias");
+    out_features = ws[0]; in_features = ws[1];
+    const QuantImage img = quant_image("QuantLinear", lin.weight.var.data, out_features, in_features, bits, group);
+    qweight = img.qweight; scales = img.scales;
+    bias = lin.bias.var.data;
+}
+Var QuantLinear::forward(const Var& x) const {
+    const Shape& s = x.shape();
+    if (s.size() != 2 || s[1] != in_features) panic("QuantLinear: the input must be (rows, " + std::to_string(in_features) + ")");
+    if (x.device().get() != qweight->device().get()) panic("QuantLinear: the input lives on another device");
+    auto n = std::make_shared<QuantLinearFwd>();
+    n->x = x.data; n->bias = bias;
+    n->img.qweight = qweight; n->img.scales = scales; n->img.bits = bits; n->img.group = group;
+    n->rows = s[0]; n->in = in_features; n->out = out_features;
+    n->y = zeros_like(x.data, Shape{s[0], out_features});
+    auto y = n->y;
+    return Var::node(y, n, x.history);
+}
+Var QuantLinear::forward(const VarDiff& x) const { return forward(x.var); }
+Var QuantLinear::dequantize() const {
+    auto w = std::make_shared<HipArray>(qweight->device(), Shape{out_features, in_features});
+    check(nk_quant_linear_unpack(D(w), qweight->ptr(), scales->ptr(), w->ptr(), in_features, out_features, in_features, bits, group));
+    return Var::leaf(w);
+}
+void MultiheadAttention::quantize(int bits, int group) {
+    const int dkv = d_model / heads * kv_heads;
+    const bool packed = packed_qkv && still_packed();
+    QuantImage img[3];
+    if (packed) img[0] = quant_image("MultiheadAttention::quantize", wqkv_, d_model + 2 * dkv, d_model, bits, group);
+    else {
+        const Linear* ls[3] = {&q, &k, &v};
+        for (int i = 0; i < 3; ++i) {
+            const int out = i == 0 ? d_model : dkv;
+            if (ls[i]->weight.shape() != Shape{out, d_model})
+                panic("MultiheadAttention::quantize: the projections must be (d_model, d_model) - k and v (kv_heads*head_dim, d_model)");
+            img[i] = quant_image("MultiheadAttention::quantize", ls[i]->weight.var.data, out, d_model, bits, group);
+        }
+    }
+    if (o.weight.shape() != Shape{d_model, d_model}) panic("MultiheadAttention::quantize: the output projection must be (d_model, d_model)");
+    const QuantImage io = quant_image("MultiheadAttention::quantize", o.weight.var.data, d_model, d_model, bits, group);
+    for (int i = 0; i < 3; ++i) qimg_[i] = img[i];   // nothing changes when a panic fired above
+    qo_ = io;
+    qpacked_ = packed;
+}
+
 Segments::Segments(DevicePtr dev, int batch_, int S_, const std::vector<std::vector<int>>& doc_lens) : batch(batch_), S(S_), max_len(0) {
     if (!dev) panic("Segments: null device");
     check(nk_graph_refuse_capture(dev->raw(), "nn::Segments (its arrays are uploaded with a synchronising copy)"));  // before anything touches the stream
@@ -3682,8 +3761,10 @@ void KvCache::truncate(const std::vector<int>& lens) {
     lens_ = lens;
 }
 
+struct StepImages { const QuantImage* qkv; const QuantImage* o; bool packed; };  // MultiheadAttention::quantize's images; o null: none
 static std::shared_ptr<DecodeStepFwd> decode_step_node(const MultiheadAttention& m, const Var& x, int batch, int T, bool fresh, bool packed,
-                                                       const Shared<HipArray>& wqkv, const Shared<HipArray>& bqkv, History<ForwardEntry>& hf);
+                                                       const Shared<HipArray>& wqkv, const Shared<HipArray>& bqkv, History<ForwardEntry>& hf,
+                                                       const StepImages& qi);
 
 // What both forward_step overloads refuse before they look at their cache's contents, in the order they fire: the layer's mode,
 // the input's shape, the cache's own geometry and device (`cache_fits(dh)`, worded by each overload), rope's head size, the
@@ -3733,7 +3814,7 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
         fresh = fresh && cache.lens()[b] == 0;
     }
     History<ForwardEntry> hf = x.history;
-    auto fw = decode_step_node(*this, x, batch, T, fresh, packed_qkv && still_packed(), wqkv_, bqkv_, hf);
+    auto fw = decode_step_node(*this, x, batch, T, fresh, packed_qkv && still_packed(), wqkv_, bqkv_, hf, StepImages{qimg_, qo_ ? &qo_ : nullptr, qpacked_});
     fw->cap = cache.capacity;
     fw->ring = cache.rolling;
     fw->kc = cache.k; fw->vc = cache.v;
@@ -3754,7 +3835,8 @@ Var MultiheadAttention::forward_step(const Var& x, int batch, KvCache& cache) co
 // The part of the step's node both forward_step overloads build the same way: the projections, the temporaries, rope and the
 // decision for the causal core.  The caller adds the cache, the scratch and the start positions.
 static std::shared_ptr<DecodeStepFwd> decode_step_node(const MultiheadAttention& m, const Var& x, int batch, int T, bool fresh, bool packed,
-                                                const Shared<HipArray>& wqkv, const Shared<HipArray>& bqkv, History<ForwardEntry>& hf) {
+                                                const Shared<HipArray>& wqkv, const Shared<HipArray>& bqkv, History<ForwardEntry>& hf,
+                                                const StepImages& qi) {
     const int d_model = m.d_model, heads = m.heads, kv_heads = m.kv_heads, window = m.window, dh = d_model / heads;
     const Linear &q = m.q, &k = m.k, &v = m.v, &o = m.o;
     const Shared<RotaryEmbedding>& rope = m.rope;
@@ -3780,6 +3862,13 @@ static std::shared_ptr<DecodeStepFwd> decode_step_node(const MultiheadAttention&
     if (o.weight.shape() != Shape{d_model, d_model} || o.bias.shape() != Shape{d_model})
         panic("MultiheadAttention::forward_step: the output projection must be (d_model, d_model) with a (d_model) bias");
     fw->wo = o.weight.var.data; fw->bo = o.bias.var.data;
+    if (qi.o) {  // quantize() was called: the node projects through the images, which must be of the form this step takes
+        if (qi.packed != packed)
+            panic("MultiheadAttention::forward_step: quantize() built the images of the " + std::string(qi.packed ? "packed" : "three separate") +
+                  " projections, this step takes the " + (packed ? "packed" : "three separate") + " ones: call quantize() again");
+        for (int i = 0; i < (packed ? 1 : 3); ++i) fw->qw[i] = qi.qkv[i];
+        fw->qwo = *qi.o;
+    }
     fw->ctx = zeros_like(x.data, Shape{n, d_model});
     fw->out = zeros_like(x.data, Shape{n, d_model});
     if (rope) {
@@ -3833,7 +3922,7 @@ Var MultiheadAttention::forward_step(const Var& x, const std::vector<int>& seqs,
     // the node and the scratch first (their panics: projection shapes, a scratch past 31 bits), then reserve(), which panics before
     // it changes anything (out of pages, max_pages exceeded, duplicate ids); after it nothing panics
     History<ForwardEntry> hf = x.history;
-    auto fw = decode_step_node(*this, x, batch, T, fresh, packed_qkv && still_packed(), wqkv_, bqkv_, hf);
+    auto fw = decode_step_node(*this, x, batch, T, fresh, packed_qkv && still_packed(), wqkv_, bqkv_, hf, StepImages{qimg_, qo_ ? &qo_ : nullptr, qpacked_});
     if (!fw->core) fw->ws = cache.workspace(batch, T, heads, window);  // one partial per QUERY head
     const std::vector<std::pair<int, int>> copies = cache.reserve(seqs, T);
     fw->cap = 0;

@@ -639,6 +639,29 @@ struct LinearOrigin {
     Shared<Gradient> input_grad;
     History<BackwardEntry> input_history;
 };
+// The weight-only quantised image of one (out, in) weight (ours; format at nk_quant_linear_* in neuronika_hip.h): packed int8 / int4
+// rows and their per-group f32 scales, both ordinary device arrays of opaque words.  Null arrays: no image.
+struct QuantImage {
+    Shared<HipArray> qweight, scales;
+    int bits = 0, group = 0;
+    explicit operator bool() const { return (bool)qweight; }
+};
+// Weight-only quantised Linear for inference (ours; the reference has no such layer): W8A32 / W4A32.  The constructor packs the
+// weight of `lin` on the device and shares its bias array; the Linear is left as it is, and later updates of its weight do not reach
+// the image.  forward(x): (rows, in_features) -> (rows, out_features) as ONE forward node on nk_quant_linear_fwd, without a
+// gradient: a differentiable input enters through its data and forward tape.  dequantize(): the (out, in) values float(q) * s the
+// node multiplies by.  It holds no parameters: the optimizers, dp::GradientSync and serde do not see it (serde of quantised layers is
+// out of scope; keep the Linear, or the packer's output, to rebuild one).
+// Panics: bits not 8 / 4, group not 32 / 64 / 128 / 0, in_features not a multiple of 32 and of the group, an input of another shape
+// or device.
+struct QuantLinear {
+    Shared<HipArray> qweight, scales, bias;
+    int in_features, out_features, bits, group;
+    QuantLinear(const Linear& lin, int bits, int group = 0);
+    Var forward(const Var& input) const;
+    Var forward(const VarDiff& input) const;
+    Var dequantize() const;
+};
 // Graph-build peephole `forward(x).relu()` -> the Linear+ReLU node (on by default, per thread; off: the ReLU node over the
 // Linear's output, as the tests that pit the two graphs against each other bit for bit need it).  Returns the old setting.
 bool set_relu_peephole(bool on);
@@ -1183,8 +1206,18 @@ struct MultiheadAttention {
     // head size; a sequence with behind > 0 stepped by a layer with window == 0, or whose window would reach below behind;
     // lens + T beyond rope's table.
     Var forward_step(const Var& x, const std::vector<int>& seqs, PagedKvCache& cache) const;
+    // Weight-only quantised decoding (nn::QuantLinear's format): builds int8 / int4 images of the projections forward_step uses and
+    // of `o` - ONE image of the packed [Wq; Wk; Wv] storage while the module is still packed and packed_qkv is on, three otherwise.
+    // From then on both forward_step overloads project through nk_quant_linear_fwd; forward() for training is untouched and keeps
+    // reading the f32 weights, which stay allocated.  The images are a snapshot: after an optimizer step, an assignment to q / k /
+    // v / o or a change of packed_qkv, call quantize() again (forward_step panics when the form it needs has no image).  Never
+    // called: null images, every launch and bit as before.  Panics: what QuantLinear refuses; d_model not a multiple of 32.
+    void quantize(int bits, int group = 0);
+    bool quantized() const { return (bool)qo_; }
 
    private:
+    QuantImage qimg_[3], qo_;   // [0] alone: the packed storage's image; all three: q, k, v
+    bool qpacked_ = false;
     VarDiff forward_impl(const VarDiff& x, int batch, const Segments* seg) const;
     bool still_packed() const;
     Shared<HipArray> wqkv_, bqkv_, gwqkv_, gbqkv_;  // packed storage (null when the layers were handed in)

@@ -326,6 +326,19 @@ PYBIND11_MODULE(_tape, m) {
         .def("forward", py::overload_cast<const VarDiff&>(&nn::Linear::forward, py::const_))
         .def("forward_relu", py::overload_cast<const Var&>(&nn::Linear::forward_relu, py::const_))
         .def("forward_relu", py::overload_cast<const VarDiff&>(&nn::Linear::forward_relu, py::const_));
+    py::class_<nn::QuantLinear>(nn, "QuantLinear")
+        .def(py::init<const nn::Linear&, int, int>(), py::arg("linear"), py::arg("bits"), py::arg("group") = 0,
+             "Weight-only quantised Linear for inference: packs the Linear's weight to int8 / int4 with per-group f32 scales (group 32, 64, "
+             "128, or 0 for one per row) on the device and shares its bias. The Linear is left as it is. No parameters, no gradient, no serde.")
+        .def_readonly("in_features", &nn::QuantLinear::in_features)
+        .def_readonly("out_features", &nn::QuantLinear::out_features)
+        .def_readonly("bits", &nn::QuantLinear::bits)
+        .def_readonly("group", &nn::QuantLinear::group)
+        .def("forward", py::overload_cast<const Var&>(&nn::QuantLinear::forward, py::const_), py::arg("input"),
+             "(rows, in_features) -> (rows, out_features), one forward node on nk_quant_linear_fwd, no gradient.")
+        // a differentiable input (what the layers return) enters through its data and forward tape
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::QuantLinear::forward, py::const_), py::arg("input"))
+        .def("dequantize", &nn::QuantLinear::dequantize, "The (out_features, in_features) values float(q) * scale the layer multiplies by.");
     py::class_<nn::LayerNorm>(nn, "LayerNorm")
         .def(py::init<DevicePtr, Shape, double, bool>(), py::arg("dev"), py::arg("normalized_shape"), py::arg("eps") = 1e-5,
              py::arg("elementwise_affine") = true)
@@ -702,7 +715,12 @@ PYBIND11_MODULE(_tape, m) {
              "The same step over a paged cache: the batch is len(seqs), any subset of the cache's sequences in any order. Pages are "
              "reserved when the node is built; forward() runs the page copies, the append and the attention.")
         .def("forward_step", [](const nn::MultiheadAttention& m, const VarDiff& x, const std::vector<int>& seqs, nn::PagedKvCache& cache) {
-                 return m.forward_step(x.var, seqs, cache); }, py::arg("x"), py::arg("seqs"), py::arg("cache"));
+                 return m.forward_step(x.var, seqs, cache); }, py::arg("x"), py::arg("seqs"), py::arg("cache"))
+        .def("quantize", &nn::MultiheadAttention::quantize, py::arg("bits"), py::arg("group") = 0,
+             "Build int8 / int4 images of the projections forward_step uses (the packed [Wq; Wk; Wv] storage while the module is still "
+             "packed, three images otherwise) and of o; both forward_step overloads then project through nk_quant_linear_fwd. forward() "
+             "is untouched. A snapshot: call it again after the weights change.")
+        .def_property_readonly("quantized", &nn::MultiheadAttention::quantized);
 
     py::module_ optim = m.def_submodule("optim");
     {

@@ -104,10 +104,12 @@ const char* nk_version(void);
  *                          takes the guarded instantiations of the same layout, tile and epilogue (64-bit base per k-tile, 32-bit
  *                          element offsets inside it, one k-tile of look-ahead); both give the same bits.  k-pair blocks are decided
  *                          first and are not affected.  A small W lets a test reach that route with small matrices.
+ *   NK_TUNE_QUANT_ROWS     values[0] = -1 rule / 0 nk_quant_linear_fwd never takes its rows kernels (always unpack + GEMM) / L > 0 the
+ *                          rows kernels for M <= L, in ceil(M / 8) passes.  Rule: L = nk_quant_linear_rows_rule(bits)
  * For schedule sweeps (benchmarks/ab_*.py) and the tests that pit one schedule against another bit for bit; results never
  * depend on them beyond summation order (split-K, chain length, algorithm). */
 enum { NK_TUNE_GEMM_FORCE = 0, NK_TUNE_GEMM_KPAIR = 1, NK_TUNE_ATTENTION_OCC = 2, NK_TUNE_GEMM_PAIR = 3, NK_TUNE_CONV_NARROW = 4,
-       NK_TUNE_CONV_WINOGRAD = 5, NK_TUNE_GEMM_CHAIN = 6, NK_TUNE_CONV_S2DX = 7, NK_TUNE_GEMM_WINDOW = 8 };
+       NK_TUNE_CONV_WINOGRAD = 5, NK_TUNE_GEMM_CHAIN = 6, NK_TUNE_CONV_S2DX = 7, NK_TUNE_GEMM_WINDOW = 8, NK_TUNE_QUANT_ROWS = 9 };
 int nk_dev_tune(nk_device* dev, int knob, const int* values, int n);
 /* How many GEMM launches on this handle took the buffer-addressed kernels so far (NK_TUNE_GEMM_WINDOW decides per launch; a launch
  * sent to the guarded instantiations instead does not count). */
@@ -1234,6 +1236,50 @@ int nk_rope_bwd_assign(nk_device* dev, float* dx, int lddx, const float* g, int 
 int nk_sample_fwd(nk_device* dev, const float* logits, long long ld, int rows, int V, float* ids, float temperature, int top_k, float top_p,
                   uint64_t seed, uint64_t offset);
 int nk_sample_stage_limit(void);
+/* ------------------------------------------------------------------ weight-only quantised Linear --
+ * Ours (the reference has no such layer): W8A32 / W4A32 - integer weights with per-group f32 scales, f32 activations and
+ * accumulation - for the projections of incremental decoding, where M = 1 .. 8 rows of x meet the whole weight matrix and the
+ * step is as fast as the weights can be read.  Inference only.
+ * Format, for a Linear weight W of shape (N = out, K = in), row-major, so that an external packer can produce it:
+ *   bits    8 or 4; qmax = 127 / 7.
+ *   group   32, 64 or 128 consecutive k of one row, or 0 for one group per row.  K % 32 == 0, and K % group == 0 when group > 0.
+ *   scale   per row n and group g, symmetric: s = fl32(absmax / qmax), one IEEE f32 division.
+ *   q       clamp(rint(fl32(w / s)), -qmax, qmax), round-half-even; s == 0 gives q = 0.
+ *   value   w^ = fl32(float(q) * s), one rounding.
+ *   qw      rows contiguous, K * bits / 8 bytes each: int8 as two's-complement bytes; int4 as the unsigned nibble q + 8, element k in
+ *           byte k / 2, even k in the low nibble.  nk_quant_linear_words(N, K, bits) floats hold it; the allocation is an ordinary
+ *           float* of opaque words (as mask_bits are), 16-byte aligned.
+ *   scales  (N, K / group) f32, or (N, 1) for group 0: nk_quant_linear_scales(N, K, group) floats.
+ *   Non-finite weights give unspecified values; the calls stay memory-safe.
+ * Both size functions return 0 for a geometry the calls refuse.
+ * nk_quant_linear_pack: W (row stride ldw) -> qw, scales, on the device.  nk_quant_linear_unpack: w^ into W (row stride ldw; nothing
+ *   beyond a row's K columns is written).
+ * nk_quant_linear_fwd: y[m][n] = bias[n] + sum_k x[m][k] * w^[n][k] for M rows; x row m at x + m*ldx, y row m at y + m*ldy (a column
+ *   block of a wider buffer either way); bias may be NULL.  Two paths, chosen from (M, bits) alone:
+ *   rows  M <= L(bits) = nk_quant_linear_rows_rule(bits) (measured; NK_TUNE_QUANT_ROWS overrides): up to 8 rows of x per pass over the
+ *         weights, ceil(M / 8) passes.  The weights go from memory to registers in 16-byte loads and are never written back as f32.
+ *         The scale is applied per UNIT of 16 consecutive k (a unit lies inside one group):
+ *             p   = fma(x[k+15], float(q[k+15]), ... fma(x[k], float(q[k]), 0))
+ *             acc = fma(s, p, acc)
+ *         i.e. acc += s * sum_unit(x * float(q)), not a sum of x * w^.  A 16-byte chunk of a weight row (16 int8 / 32 int4 elements)
+ *         belongs to lane (chunk % 64) of the row's wave, a lane adds its units in ascending k, the 64 lane sums meet in an xor
+ *         butterfly (offsets 32 .. 1), then the bias is added: a compile-time function of (bits, K).  No split of K, no workspace, no
+ *         atomics, nothing allocated - the path can sit in a captured region.
+ *         Bit contract: the bits of y[m][n] depend on x[m, :], row n of qw and scales, bias[n] and (bits, group, K) only - not on M,
+ *         N, the other rows, ldx / ldy, pointer alignment of x, or the pass a row falls in.  A sequence decoded alone gets the bits it
+ *         gets in a batch, as with the decode attention kernels.
+ *   many  M > L: unpack into a scratch region of the device handle (N*K floats; its growth refuses stream capture like the
+ *         workspace's), then the f32 GEMM.  With a bias and ldx == K, ldy == N the bits are exactly nk_linear_fwd's over the unpacked
+ *         weights; otherwise nk_sgemm's with the bias added afterwards.
+ * NK_ERR_INVALID, nothing written: bits not 8 / 4, group not 32 / 64 / 128 / 0, K % 32 != 0, K % group != 0, non-positive N or K,
+ * M < 0 (M == 0 is an empty success), a null pointer other than bias, ldx < K, ldy < N, ldw < K, qw not 16-byte aligned. */
+size_t nk_quant_linear_words(int N, int K, int bits);
+size_t nk_quant_linear_scales(int N, int K, int group);
+int nk_quant_linear_rows_rule(int bits);
+int nk_quant_linear_pack(nk_device* dev, const float* W, int ldw, float* qw, float* scales, int N, int K, int bits, int group);
+int nk_quant_linear_unpack(nk_device* dev, const float* qw, const float* scales, float* W, int ldw, int N, int K, int bits, int group);
+int nk_quant_linear_fwd(nk_device* dev, const float* x, int ldx, const float* qw, const float* scales, const float* bias, float* y, int ldy,
+                        int M, int N, int K, int bits, int group);
 /* ------------------------------------------------------------------ dropout ------------ */
 /* Dropout::forward node/dropout/mod.rs:53-79.  train && 0<p<1: noise ~ Bernoulli(1-p) in
  * {0,1} is (re)drawn from Philox4x32-10(seed, offset) and written to `noise` (f32, like the

@@ -26,6 +26,7 @@ use super::{
         decode_chunk, decode_paged_workspace, decode_window_workspace, decode_workspace, PackedDecodeAttention, PagedDecodeAttention,
         RepeatKv, RepeatKvBackward, RepeatKvGeometry, rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
         sample_stage_limit, Sample, SampleParams,
+        quant_linear_rows_rule, QuantLinear, QuantWeight,
         Upsample, UpsampleBackward, UpsampleGeometry, UpsampleMode,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
         ReLUBackward, ReluMask, Softmax, SoftmaxBackward,
@@ -800,7 +801,55 @@ impl SamplerState {
     }
 }
 
+/// A weight-only quantised `(out, in)` weight with its optional bias (ours; format at `nk_quant_linear_*` in
+/// `include/neuronika_hip.h`): what `HipVar::quant_linear` multiplies by.  Built from an f32 weight on the device; the f32 weight
+/// is left as it is.  Inference only: no gradient, no parameters for an optimizer, no serde.
+#[derive(Clone)]
+pub struct QuantLinearState {
+    weight: QuantWeight,
+    bias: Option<Shared<HipArray<Ix1>>>,
+}
+
+impl QuantLinearState {
+    /// `bits` 8 or 4; `group` 32, 64, 128 or 0 (one scale per row); `in` a multiple of 32 and of the group.
+    pub fn new(weight: &HipVar<Ix2>, bias: Option<&HipVar<Ix1>>, bits: usize, group: usize) -> Self {
+        let dim = weight.data.borrow().dimension();
+        let (words, scales) = QuantWeight::sizes(dim[0], dim[1], bits as i32, group as i32)
+            .expect("QuantLinearState: bits must be 8 or 4, group 32, 64, 128 or 0, and the input extent a multiple of 32 and of the group");
+        let device = weight.device();
+        let q = QuantWeight { qweight: shared(ndarray::Dim([words]), &device), scales: shared(ndarray::Dim([scales]), &device),
+                              out_features: dim[0], in_features: dim[1], bits: bits as i32, group: group as i32 };
+        q.pack(&weight.data.borrow());
+        if let Some(b) = bias {
+            assert!(b.data.borrow().dimension()[0] == dim[0], "QuantLinearState: the bias must have one entry per output");
+        }
+        Self { weight: q, bias: bias.map(|b| b.data.clone()) }
+    }
+
+    /// The `(out, in)` values `float(q) * scale` as a leaf.
+    pub fn dequantize(&self) -> HipVar<Ix2> {
+        let device = self.weight.qweight.borrow().device().clone();
+        let data = shared(ndarray::Dim([self.weight.out_features, self.weight.in_features]), &device);
+        self.weight.unpack(&mut data.borrow_mut());
+        HipVar { data, history: History::default() }
+    }
+
+    /// Rows of `x` up to which the forward takes the rows kernels by rule.
+    pub fn rows_rule(&self) -> usize {
+        quant_linear_rows_rule(self.weight.bits)
+    }
+}
+
 impl HipVar<Ix2> {
+    /// `(rows, in) -> (rows, out)` on the packed integer weights of `layer`: ONE node (`nk_quant_linear_fwd`), no gradient.
+    pub fn quant_linear(self, layer: &QuantLinearState) -> HipVar<Ix2> {
+        let dim = self.data.borrow().dimension();
+        assert!(dim[1] == layer.weight.in_features, "quant_linear: the input must be (rows, {})", layer.weight.in_features);
+        let data = shared(ndarray::Dim([dim[0], layer.weight.out_features]), &self.device());
+        let op = QuantLinear::new(layer.weight.clone(), layer.bias.clone(), dim[0], self.data, data.clone());
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
     /// The next token of every sample of `(batch * rows, vocab)` logits: the `(batch,)` ids, as f32, drawn from the LAST row of each
     /// sample - what `embedding` takes.  ONE node (`nk_sample_fwd`), no gradient.
     pub fn sample(self, sampler: &SamplerState, batch: usize) -> HipVar<Ix1> {

@@ -24,6 +24,7 @@ mod reduction;
 mod repeat_kv;
 mod rms_norm;
 mod rope;
+mod quant_linear;
 mod sample;
 mod upsample;
 
@@ -47,6 +48,7 @@ pub(crate) use reduction::*;
 pub(crate) use repeat_kv::*;
 pub(crate) use rms_norm::*;
 pub(crate) use rope::*;
+pub(crate) use quant_linear::*;
 pub(crate) use sample::*;
 pub(crate) use upsample::*;
 

@@ -51,7 +51,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIBDIR, exist_ok=True)
     srcs = _sources()
-    with cf.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
+    # one worker per unit, at most 16: with 8 the row unit (nk_norm.hip, one of the two longest) waited for a free worker and ended the build
+    with cf.ThreadPoolExecutor(max_workers=min(16, len(srcs))) as ex:
         results = list(ex.map(lambda s: _compile(s, force), srcs))
     objs = [o for o, _ in results]
     rebuilt = any(r for _, r in results)

@@ -260,6 +260,12 @@ _SIGS = {
     "nk_rope_bwd_assign": [VP, VP, C.c_int, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_sample_fwd": [VP, VP, C.c_longlong, C.c_int, C.c_int, VP, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_uint64],
     "nk_sample_stage_limit": [],
+    "nk_quant_linear_words": [C.c_int, C.c_int, C.c_int],
+    "nk_quant_linear_scales": [C.c_int, C.c_int, C.c_int],
+    "nk_quant_linear_rows_rule": [C.c_int],
+    "nk_quant_linear_pack": [VP, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_quant_linear_unpack": [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_quant_linear_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_scale_softmax_dropout_fwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_scale_softmax_dropout_bwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_dropout_fwd": [VP, VP, VP, VP, C.c_size_t, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
@@ -300,7 +306,7 @@ _SIGS = {
 }
 _RESTYPES = {"nk_last_error": C.c_char_p, "nk_version": C.c_char_p, "nk_stream_compute": VP, "nk_stream_comm": VP,
              "nk_attention_decode_workspace": C.c_size_t, "nk_attention_decode_window_workspace": C.c_size_t,
-             "nk_attention_decode_paged_workspace": C.c_size_t,
+             "nk_attention_decode_paged_workspace": C.c_size_t, "nk_quant_linear_words": C.c_size_t, "nk_quant_linear_scales": C.c_size_t,
              "nk_gemm_buffer_records": C.c_longlong, "nk_attention_band_scratch": C.c_size_t, "nk_attention_band_mask_words": C.c_size_t}
 EXPORTED = tuple(_SIGS)
 
@@ -363,6 +369,7 @@ class Event:
 
 TUNE_GEMM_FORCE, TUNE_GEMM_KPAIR, TUNE_ATTENTION_OCC, TUNE_GEMM_PAIR, TUNE_CONV_NARROW, TUNE_CONV_WINOGRAD, TUNE_GEMM_CHAIN, TUNE_CONV_S2DX = 0, 1, 2, 3, 4, 5, 6, 7   # include/neuronika_hip.h: nk_dev_tune knobs
 TUNE_GEMM_WINDOW = 8
+TUNE_QUANT_ROWS = 9
 
 
 class Device:
@@ -421,6 +428,11 @@ class Device:
         """NK_TUNE_GEMM_WINDOW: None / 0 the rule (2^31 - 1), W > 0: aligned 128 x 128 GEMM launches take the buffer-addressed
         kernels only while a tile's window in each operand is at most W bytes (above it: the guarded instantiations, same bits)"""
         self.tune(TUNE_GEMM_WINDOW, nbytes)
+
+    def quant_rows(self, limit=None):
+        """NK_TUNE_QUANT_ROWS: None / -1 the rule (nk_quant_linear_rows_rule(bits)), 0 nk_quant_linear_fwd never takes its rows kernels,
+        L > 0 the rows kernels for M <= L"""
+        self.tune(TUNE_QUANT_ROWS, limit)
 
     def gemm_buffer_launches(self) -> int:
         """nk_gemm_buffer_launches: GEMM launches on this handle that took the buffer-addressed kernels so far (not those sent to the
@@ -1196,6 +1208,37 @@ def sample_fwd(dev, logits, ld, rows, V, ids, temperature=1.0, top_k=0, top_p=1.
 def sample_stage_limit() -> int:
     """The largest V whose row the sampling kernel keeps in LDS: a constant of the library."""
     return int(lib.nk_sample_stage_limit())
+
+
+def quant_linear_words(N, K, bits) -> int:
+    """Floats that hold the packed (N, K) weight at `bits` per element; 0 for a geometry the entry points refuse."""
+    return int(lib.nk_quant_linear_words(int(N), int(K), int(bits)))
+
+
+def quant_linear_scales(N, K, group) -> int:
+    """Floats of the (N, K / group) scales ((N, 1) for group 0); 0 for a geometry the entry points refuse."""
+    return int(lib.nk_quant_linear_scales(int(N), int(K), int(group)))
+
+
+def quant_linear_rows_rule(bits) -> int:
+    """L(bits): nk_quant_linear_fwd takes its rows kernels for M <= L by rule."""
+    return int(lib.nk_quant_linear_rows_rule(int(bits)))
+
+
+def quant_linear_pack(dev, W, ldw, qw, scales, N, K, bits, group=0):
+    """W (N rows of K floats, row stride ldw) -> packed integers `qw` and f32 `scales`, on the device."""
+    check(lib.nk_quant_linear_pack(dev.h, _p(W), int(ldw), _p(qw), _p(scales), int(N), int(K), int(bits), int(group)))
+
+
+def quant_linear_unpack(dev, qw, scales, W, ldw, N, K, bits, group=0):
+    """The dequantised weights float(q) * s into W (row stride ldw); nothing beyond a row's K columns is written."""
+    check(lib.nk_quant_linear_unpack(dev.h, _p(qw), _p(scales), _p(W), int(ldw), int(N), int(K), int(bits), int(group)))
+
+
+def quant_linear_fwd(dev, x, ldx, qw, scales, bias, y, ldy, M, N, K, bits, group=0):
+    """y[m][n] = bias[n] + sum_k x[m][k] * w^[n][k]; x rows at stride ldx, y rows at stride ldy, bias may be None."""
+    check(lib.nk_quant_linear_fwd(dev.h, _p(x), int(ldx), _p(qw), _p(scales), _p(bias), _p(y), int(ldy), int(M), int(N), int(K), int(bits),
+                                  int(group)))
 
 
 def attention_bwd(dev, dQ, dK, dV, dS, dropped, dO, out, scores, stats, mask_bits, Q, K, V, B, S, H, dh, scale, p, train=True,

@@ -52,6 +52,7 @@ struct nk_device {
     int tune_conv_winograd = -1;             // 3x3 s1 d1 g1 forward / input gradient: -1 rule, 0 never Winograd, 1 whenever the shape allows
     int tune_attn_occ = 0;                   // attention forward: 2 = size the register budget for two blocks per CU
     int tune_gemm_window = 0;                // buffer-addressed GEMM loads: largest operand window of a tile in bytes, 0 = the rule (2^31 - 1)
+    int tune_quant_rows = -1;                // nk_quant_linear_fwd: -1 rule, 0 never the rows kernels, L > 0 rows kernels up to L rows of x
     unsigned long long gemm_buf_launches = 0;  // GEMM launches that took the buffer-addressed kernels (nk_gemm_buffer_launches)
     // bench instrumentation (nk_profile_begin/end)
     bool prof_on = false;

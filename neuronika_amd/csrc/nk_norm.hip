@@ -310,6 +310,7 @@ int rms_norm_bwd_gamma(nk_device* dev, float* dgamma, const float* g, const floa
 }  // namespace
 
 #include "nk_group_norm.h"  // GroupNorm / InstanceNorm: its kernels and entry points, built on the helpers above
+#include "nk_quant_linear.h"  // weight-only int8 / int4 Linear: pack, unpack, the decode rows kernels and their entry points
 
 extern "C" {
 

@@ -232,6 +232,10 @@ int nk_dev_tune(nk_device* dev, int knob, const int* values, int n) {
             NK_CHECK(n <= 1 && (n == 0 || values[0] >= 0), "NK_TUNE_GEMM_WINDOW: 0 (rule) or a window limit in bytes");
             dev->tune_gemm_window = n ? values[0] : 0;
             return NK_OK;
+        case NK_TUNE_QUANT_ROWS:
+            NK_CHECK(n <= 1 && (n == 0 || values[0] >= -1), "NK_TUNE_QUANT_ROWS: -1 (rule), 0 (never the rows kernels) or a row count");
+            dev->tune_quant_rows = n ? values[0] : -1;
+            return NK_OK;
     }
     nk_set_error("unknown tuning knob %d", knob);
     return NK_ERR_INVALID;
