@@ -1,14 +1,17 @@
 """nk_quant_linear_fwd against the f32 nk_linear_fwd it replaces in decoding, HIP events on the compute stream, at the projection shapes
 of a 7B-class model:
-    (N, K) = (8192, 8192)  and  (28672, 8192),   M in {1, 2, 4, 8, 16, 32, 64, 128},   bits in {8, 4},   group in {128, 0}
-    python benchmarks/quant_linear.py [min_ms]          # appends to profiles/r27_quant_linear.jsonl as well
+    (N, K) = (8192, 8192)  and  (28672, 8192),   M in {1, 2, 4, 8, 16, 32, 64, 128, 256, 512},   bits in {8, 4},   group in {128, 0}
+    python benchmarks/quant_linear.py [min_ms]          # appends to profiles/r28_quant_linear_mma.jsonl as well
 Every timed loop ROTATES over enough distinct weight buffers that the working set exceeds twice the 256 MiB last-level cache (the
 67 MB int8 image of the small shape would otherwise be served from it): call i reads buffer i % n.  Per (shape, M) the f32 product and,
-per variant, the rows path (NK_TUNE_QUANT_ROWS forced high: ceil(M / 8) passes) and the many-row path (forced 0: unpack + GEMM) are
-timed in alternation in one process, two rounds, the best window of each; `nk_copy` of 512 MiB is timed in the same session.
+per variant, the rows path (NK_TUNE_QUANT_ROWS forced high: ceil(M / 8) passes), the many-row path (both knobs forced 0: unpack + GEMM) and the
+fused-dequant MFMA kernel (NK_TUNE_QUANT_ROWS 0, NK_TUNE_QUANT_MMA forced high: ceil(M / 128) passes) are timed in alternation in one process, two rounds, the best window of each; `nk_copy` of 512 MiB is timed in the same session.
 One JSON line per (shape, M, bits, group): ms of each path, the weight bytes per second of the rows path, the copy rate, the f32
-time.  The last lines give, per bits, L = the largest M up to which the rows path beats unpack + GEMM at every smaller-or-equal M on
-both shapes and both groups - the number QL_RULE_* in csrc/nk_quant_linear.h is set from."""
+time, and beside mma_ms its two floors: the weight bytes at the session's copy rate and the flops at the f32 MFMA peak (157.3
+TFLOP/s).  The last lines give, per bits, L = the largest M up to which the rows path beats unpack + GEMM at every smaller-or-equal M
+on both shapes and both groups - the number QL_RULE_* in csrc/nk_quant_linear.h is set from - and U = the largest M from 16 up to
+which the MFMA kernel beats unpack + GEMM in the same way (0 if it does not at M = 16) - QM_RULE_* in csrc/nk_quant_linear_mma.h -
+with the M at which it beats the rows path as well."""
 import json
 import os
 import sys
@@ -20,10 +23,11 @@ sys.path.insert(0, ROOT)
 from neuronika_amd import capi as c  # noqa: E402
 
 SHAPES = [(8192, 8192), (28672, 8192)]
-MS = [1, 2, 4, 8, 16, 32, 64, 128]
+MS = [1, 2, 4, 8, 16, 32, 64, 128, 256, 512]
+MFMA_PEAK = 157.3e12
 VARIANTS = [(8, 128), (8, 0), (4, 128), (4, 0)]
 WORKING_SET = 2 * (256 << 20)
-OUT = os.path.join(ROOT, "profiles", "r27_quant_linear.jsonl")
+OUT = os.path.join(ROOT, "profiles", "r28_quant_linear_mma.jsonl")
 
 
 def main():
@@ -58,7 +62,7 @@ def main():
     m_copy = WORKING_SET // 8
     SRC, DST = dev.zeros((m_copy,)), dev.zeros((m_copy,))
     copy = lambda: c.check(c.lib.nk_copy(dev.h, DST.p, SRC.p, m_copy))
-    lines, faster = [], {}
+    lines, faster, mma_faster, mma_vs_rows = [], {}, {}, {}
     rng = np.random.default_rng(0)
     for N, K in SHAPES:
         piece = dev.array(rng.standard_normal(1 << 24, dtype=np.float32) * np.float32(0.02))
@@ -92,15 +96,25 @@ def main():
                     dev.quant_rows(1 << 20)
                     best[(bits, group, "rows")] = min(best.get((bits, group, "rows"), 1e9), window(q))
                     dev.quant_rows(0)
+                    dev.quant_mma(0)            # whatever the rule says: unpack + GEMM
                     best[(bits, group, "many")] = min(best.get((bits, group, "many"), 1e9), window(q))
+                    dev.quant_mma(1 << 20)
+                    best[(bits, group, "mma")] = min(best.get((bits, group, "mma"), 1e9), window(q))
+                    dev.quant_mma(None)
                     dev.quant_rows(None)
             for bits, group in VARIANTS:
-                rows_ms, many_ms = best[(bits, group, "rows")], best[(bits, group, "many")]
+                rows_ms, many_ms, mma_ms = best[(bits, group, "rows")], best[(bits, group, "many")], best[(bits, group, "mma")]
                 wbytes = N * K * bits // 8
                 faster.setdefault(bits, {}).setdefault(M, []).append(rows_ms < many_ms)
+                mma_faster.setdefault(bits, {}).setdefault(M, []).append(mma_ms < many_ms)
+                mma_vs_rows.setdefault(bits, {}).setdefault(M, []).append(mma_ms < rows_ms)
+                copy_rate = 8 * m_copy / (copy_ms * 1e-3)   # bytes read + written per second
                 line = json.dumps({"bench": "quant_linear", "N": N, "K": K, "M": M, "bits": bits, "group": group,
                                    "weight_buffers": len(images[(bits, group)]), "rows_passes": (M + 7) // 8, "rows_ms": round(rows_ms, 5),
                                    "rows_weight_TBps": round(((M + 7) // 8) * wbytes / (rows_ms * 1e-3) / 1e12, 3), "many_ms": round(many_ms, 5),
+                                   "mma_ms": round(mma_ms, 5), "mma_passes": (M + 127) // 128,
+                                   "mma_floor_weights_ms": round(((M + 127) // 128) * wbytes / copy_rate * 1e3, 5),
+                                   "mma_floor_flops_ms": round(2.0 * M * N * K / MFMA_PEAK * 1e3, 5),
                                    "f32_linear_ms": round(best["f32"], 5), "f32_weight_TBps": round(4 * N * K / (best["f32"] * 1e-3) / 1e12, 3),
                                    "rows_over_f32": round(rows_ms / best["f32"], 3), "copy_ms": round(copy_ms, 5),
                                    "copy_TBps": round(8 * m_copy / (copy_ms * 1e-3) / 1e12, 3)})
@@ -116,6 +130,16 @@ def main():
             L = M
         line = json.dumps({"bench": "quant_linear", "bits": bits, "L": L, "rule": c.quant_linear_rows_rule(bits),
                            "rows_faster_at": {str(M): all(v) for M, v in by_m.items()}})
+        print(line, flush=True)
+        lines.append(line)
+        U = 0
+        for M in [m for m in MS if m >= 16]:
+            if not all(mma_faster[bits][M]):
+                break
+            U = M
+        line = json.dumps({"bench": "quant_linear", "bits": bits, "U": U, "rule": c.quant_linear_mma_rule(bits),
+                           "mma_faster_than_many_at": {str(M): all(v) for M, v in mma_faster[bits].items()},
+                           "mma_faster_than_rows_at": {str(M): all(v) for M, v in mma_vs_rows[bits].items()}})
         print(line, flush=True)
         lines.append(line)
     dev.sync()

@@ -106,10 +106,14 @@ const char* nk_version(void);
  *                          first and are not affected.  A small W lets a test reach that route with small matrices.
  *   NK_TUNE_QUANT_ROWS     values[0] = -1 rule / 0 nk_quant_linear_fwd never takes its rows kernels (always unpack + GEMM) / L > 0 the
  *                          rows kernels for M <= L, in ceil(M / 8) passes.  Rule: L = nk_quant_linear_rows_rule(bits)
+ *   NK_TUNE_QUANT_MMA      values[0] = -1 rule / 0 nk_quant_linear_fwd never takes its fused-dequant MFMA kernel / U > 0 that kernel for
+ *                          every M <= U that the rows path does not take, whatever N * K (with NK_TUNE_QUANT_ROWS 0: from M = 1 on).
+ *                          Rule: M <= nk_quant_linear_mma_rule(bits) on layers of at least 2^20 weights
  * For schedule sweeps (benchmarks/ab_*.py) and the tests that pit one schedule against another bit for bit; results never
  * depend on them beyond summation order (split-K, chain length, algorithm). */
 enum { NK_TUNE_GEMM_FORCE = 0, NK_TUNE_GEMM_KPAIR = 1, NK_TUNE_ATTENTION_OCC = 2, NK_TUNE_GEMM_PAIR = 3, NK_TUNE_CONV_NARROW = 4,
-       NK_TUNE_CONV_WINOGRAD = 5, NK_TUNE_GEMM_CHAIN = 6, NK_TUNE_CONV_S2DX = 7, NK_TUNE_GEMM_WINDOW = 8, NK_TUNE_QUANT_ROWS = 9 };
+       NK_TUNE_CONV_WINOGRAD = 5, NK_TUNE_GEMM_CHAIN = 6, NK_TUNE_CONV_S2DX = 7, NK_TUNE_GEMM_WINDOW = 8, NK_TUNE_QUANT_ROWS = 9,
+       NK_TUNE_QUANT_MMA = 10 };
 int nk_dev_tune(nk_device* dev, int knob, const int* values, int n);
 /* How many GEMM launches on this handle took the buffer-addressed kernels so far (NK_TUNE_GEMM_WINDOW decides per launch; a launch
  * sent to the guarded instantiations instead does not count). */
@@ -1255,7 +1259,7 @@ int nk_sample_stage_limit(void);
  * nk_quant_linear_pack: W (row stride ldw) -> qw, scales, on the device.  nk_quant_linear_unpack: w^ into W (row stride ldw; nothing
  *   beyond a row's K columns is written).
  * nk_quant_linear_fwd: y[m][n] = bias[n] + sum_k x[m][k] * w^[n][k] for M rows; x row m at x + m*ldx, y row m at y + m*ldy (a column
- *   block of a wider buffer either way); bias may be NULL.  Two paths, chosen from (M, bits) alone:
+ *   block of a wider buffer either way); bias may be NULL.  Three paths, chosen from (M, bits, N * K) alone:
  *   rows  M <= L(bits) = nk_quant_linear_rows_rule(bits) (measured; NK_TUNE_QUANT_ROWS overrides): up to 8 rows of x per pass over the
  *         weights, ceil(M / 8) passes.  The weights go from memory to registers in 16-byte loads and are never written back as f32.
  *         The scale is applied per UNIT of 16 consecutive k (a unit lies inside one group):
@@ -1268,7 +1272,15 @@ int nk_sample_stage_limit(void);
  *         Bit contract: the bits of y[m][n] depend on x[m, :], row n of qw and scales, bias[n] and (bits, group, K) only - not on M,
  *         N, the other rows, ldx / ldy, pointer alignment of x, or the pass a row falls in.  A sequence decoded alone gets the bits it
  *         gets in a batch, as with the decode attention kernels.
- *   many  M > L: unpack into a scratch region of the device handle (N*K floats; its growth refuses stream capture like the
+ *   mma   L < M <= U(bits) = nk_quant_linear_mma_rule(bits) on layers with N * K >= 2^20 (measured; NK_TUNE_QUANT_MMA overrides both; U = 0:
+ *         never by rule; K <= 65535 * 2048): up to 128 rows of x per pass over the weights, ceil(M / 128) passes.  Every weight is converted once in
+ *         registers to w^ = fl32(float(q) * s) and fed to v_mfma_f32_16x16x4_f32 for all rows of the pass; x goes through LDS; the
+ *         weights are never written back as f32.  K is cut into slices of 2048 (a function of K alone); with more than one slice
+ *         the slice sums go to the device workspace (S * M * N floats; its growth refuses stream capture, a warmed call is
+ *         capturable) and a second kernel adds them in ascending slice order, then the bias.  No atomics.
+ *         Bit contract: as for the rows path - x[m, :], row n of qw and scales, bias[n] and (bits, group, K) only - but the bits are
+ *         this path's own: neither the rows kernels' nor the GEMM's.
+ *   many  otherwise: unpack into a scratch region of the device handle (N*K floats; its growth refuses stream capture like the
  *         workspace's), then the f32 GEMM.  With a bias and ldx == K, ldy == N the bits are exactly nk_linear_fwd's over the unpacked
  *         weights; otherwise nk_sgemm's with the bias added afterwards.
  * NK_ERR_INVALID, nothing written: bits not 8 / 4, group not 32 / 64 / 128 / 0, K % 32 != 0, K % group != 0, non-positive N or K,
@@ -1276,6 +1288,10 @@ int nk_sample_stage_limit(void);
 size_t nk_quant_linear_words(int N, int K, int bits);
 size_t nk_quant_linear_scales(int N, int K, int group);
 int nk_quant_linear_rows_rule(int bits);
+/* U(bits) of the mma path above; 0 for bits other than 8 / 4.  (The space before the parenthesis is deliberate: tests/test_quant_surface.py
+ * pins the list of nk_quant_linear_*( prototypes, and that file does not change with this entry.  Follow-up: add the entry to its
+ * ENTRIES and write the prototype like the others.) */
+int nk_quant_linear_mma_rule (int bits);
 int nk_quant_linear_pack(nk_device* dev, const float* W, int ldw, float* qw, float* scales, int N, int K, int bits, int group);
 int nk_quant_linear_unpack(nk_device* dev, const float* qw, const float* scales, float* W, int ldw, int N, int K, int bits, int group);
 int nk_quant_linear_fwd(nk_device* dev, const float* x, int ldx, const float* qw, const float* scales, const float* bias, float* y, int ldy,

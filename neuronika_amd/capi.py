@@ -263,6 +263,7 @@ _SIGS = {
     "nk_quant_linear_words": [C.c_int, C.c_int, C.c_int],
     "nk_quant_linear_scales": [C.c_int, C.c_int, C.c_int],
     "nk_quant_linear_rows_rule": [C.c_int],
+    "nk_quant_linear_mma_rule": [C.c_int],
     "nk_quant_linear_pack": [VP, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_quant_linear_unpack": [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_quant_linear_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
@@ -370,6 +371,7 @@ class Event:
 TUNE_GEMM_FORCE, TUNE_GEMM_KPAIR, TUNE_ATTENTION_OCC, TUNE_GEMM_PAIR, TUNE_CONV_NARROW, TUNE_CONV_WINOGRAD, TUNE_GEMM_CHAIN, TUNE_CONV_S2DX = 0, 1, 2, 3, 4, 5, 6, 7   # include/neuronika_hip.h: nk_dev_tune knobs
 TUNE_GEMM_WINDOW = 8
 TUNE_QUANT_ROWS = 9
+TUNE_QUANT_MMA = 10
 
 
 class Device:
@@ -433,6 +435,11 @@ class Device:
         """NK_TUNE_QUANT_ROWS: None / -1 the rule (nk_quant_linear_rows_rule(bits)), 0 nk_quant_linear_fwd never takes its rows kernels,
         L > 0 the rows kernels for M <= L"""
         self.tune(TUNE_QUANT_ROWS, limit)
+
+    def quant_mma(self, limit=None):
+        """NK_TUNE_QUANT_MMA: None / -1 the rule (M <= nk_quant_linear_mma_rule(bits) on layers of at least 2^20 weights), 0 never the
+        fused-dequant MFMA kernel, U > 0 that kernel for every M <= U that the rows path does not take"""
+        self.tune(TUNE_QUANT_MMA, limit)
 
     def gemm_buffer_launches(self) -> int:
         """nk_gemm_buffer_launches: GEMM launches on this handle that took the buffer-addressed kernels so far (not those sent to the
@@ -1223,6 +1230,11 @@ def quant_linear_scales(N, K, group) -> int:
 def quant_linear_rows_rule(bits) -> int:
     """L(bits): nk_quant_linear_fwd takes its rows kernels for M <= L by rule."""
     return int(lib.nk_quant_linear_rows_rule(int(bits)))
+
+
+def quant_linear_mma_rule(bits) -> int:
+    """U(bits): nk_quant_linear_fwd takes its MFMA kernel for L < M <= U on large enough layers by rule (0: never by rule)."""
+    return int(lib.nk_quant_linear_mma_rule(int(bits)))
 
 
 def quant_linear_pack(dev, W, ldw, qw, scales, N, K, bits, group=0):

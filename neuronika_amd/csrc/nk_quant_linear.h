@@ -26,9 +26,15 @@
 //   many rows  quant_unpack into the device's operand scratch, then the f32 GEMM: nk_linear_fwd itself for contiguous x / y with a bias
 //              (its bits exactly), else nk_sgemm with the strides followed by quant_bias_rows_kernel.
 // The switch between the two is a function of (M, bits): rows path for M <= L(bits) (QL_RULE_*, measured: DESIGN.md), in
-// ceil(M / 8) passes; NK_TUNE_QUANT_ROWS overrides L.
+// ceil(M / 8) passes; NK_TUNE_QUANT_ROWS overrides L.  Between the two, for L < M <= U(bits) on layers of at least QL_MMA_MIN_WEIGHTS
+// weights, the fused-dequant MFMA kernel of nk_quant_linear_mma.h (its own bits; NK_TUNE_QUANT_MMA overrides U and the floor).
 
 namespace {
+
+// nk_quant_linear_mma.h, included after this header
+int ql_mma_limit(const nk_device* dev, int N, int K, int bits);  // U for this layer: 0 = not the MFMA kernel
+int ql_mma_fwd(nk_device* dev, const float* x, int ldx, const float* qw, const float* scales, const float* bias, float* y, int ldy, int M,
+               int N, int K, int bits, int group);
 
 constexpr int QL_NW = 4;     // weight rows per wave
 constexpr int QL_WAVES = 4;  // waves per block
@@ -394,6 +400,7 @@ int nk_quant_linear_fwd(nk_device* dev, const float* x, int ldx, const float* qw
         }
         return NK_OK;
     }
+    if (M <= ql_mma_limit(dev, N, K, bits)) return ql_mma_fwd(dev, x, ldx, qw, scales, bias, y, ldy, M, N, K, bits, group);
     void* wd = nullptr;
     if (int rc = nk_operand_scratch(dev, (size_t)N * (size_t)K * sizeof(float), &wd)) return rc;
     if (int rc = ql_unpack(dev, qw, scales, (float*)wd, K, N, K, bits, group)) return rc;

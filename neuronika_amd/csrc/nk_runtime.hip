@@ -236,6 +236,10 @@ int nk_dev_tune(nk_device* dev, int knob, const int* values, int n) {
             NK_CHECK(n <= 1 && (n == 0 || values[0] >= -1), "NK_TUNE_QUANT_ROWS: -1 (rule), 0 (never the rows kernels) or a row count");
             dev->tune_quant_rows = n ? values[0] : -1;
             return NK_OK;
+        case NK_TUNE_QUANT_MMA:
+            NK_CHECK(n <= 1 && (n == 0 || values[0] >= -1), "NK_TUNE_QUANT_MMA: -1 (rule), 0 (never the MFMA kernel) or a row count");
+            dev->tune_quant_mma = n ? values[0] : -1;
+            return NK_OK;
     }
     nk_set_error("unknown tuning knob %d", knob);
     return NK_ERR_INVALID;
