@@ -1077,10 +1077,11 @@ struct DecodeStepFwd : Forward {
 struct QuantLinearFwd : Forward {
     Shared<HipArray> x, bias, y;
     nn::QuantImage img;
-    int rows = 0, in = 0, out = 0;
+    int rows = 0, in = 0, out = 0, act_bits = 0;   // act_bits 8: int8 activations (nk_quant_a8_linear_fwd)
     void forward() const override {
-        check(nk_quant_linear_fwd(D(x), x->ptr(), in, img.qweight->ptr(), img.scales->ptr(), bias ? bias->ptr() : nullptr, y->ptr(), out, rows, out, in,
-                                  img.bits, img.group));
+        check((act_bits == 8 ? nk_quant_a8_linear_fwd : nk_quant_linear_fwd)(D(x), x->ptr(), in, img.qweight->ptr(), img.scales->ptr(),
+                                                                             bias ? bias->ptr() : nullptr, y->ptr(), out, rows, out, in,
+                                                                             img.bits, img.group));
     }
 };
 
@@ -3617,7 +3618,9 @@ static QuantImage quant_image(const char* who, const Shared<HipArray>& w, int N,
     check(nk_quant_linear_pack(D(w), w->ptr(), K, img.qweight->ptr(), img.scales->ptr(), N, K, bits, group));
     return img;
 }
-QuantLinear::QuantLinear(const Linear& lin, int bits_, int group_) : bits(bits_), group(group_) {
+QuantLinear::QuantLinear(const Linear& lin, int bits_, int group_, int act_bits_) : bits(bits_), group(group_), act_bits(act_bits_) {
+    if (act_bits != 0 && act_bits != 8) panic("QuantLinear: act_bits must be 0 (f32 activations) or 8; got " + std::to_string(act_bits));
+    if (act_bits == 8 && group == 32) panic("QuantLinear: act_bits = 8 takes group 64, 128 or 0 (a 64-k instruction would straddle two scales of group 32)");
     const Shape& ws = lin.weight.shape();
     if (ws.size() != 2 || lin.bias.shape() != Shape{ws[0]}) panic("QuantLinear: the Linear must hold an (out, in) weight and an (out) bias");
     out_features = ws[0]; in_features = ws[1];
@@ -3632,7 +3635,7 @@ Var QuantLinear::forward(const Var& x) const {
     auto n = std::make_shared<QuantLinearFwd>();
     n->x = x.data; n->bias = bias;
     n->img.qweight = qweight; n->img.scales = scales; n->img.bits = bits; n->img.group = group;
-    n->rows = s[0]; n->in = in_features; n->out = out_features;
+    n->rows = s[0]; n->in = in_features; n->out = out_features; n->act_bits = act_bits;
     n->y = zeros_like(x.data, Shape{s[0], out_features});
     auto y = n->y;
     return Var::node(y, n, x.history);

@@ -652,12 +652,15 @@ struct QuantImage {
 // gradient: a differentiable input enters through its data and forward tape.  dequantize(): the (out, in) values float(q) * s the
 // node multiplies by.  It holds no parameters: the optimizers, dp::GradientSync and serde do not see it (serde of quantised layers is
 // out of scope; keep the Linear, or the packer's output, to rebuild one).
-// Panics: bits not 8 / 4, group not 32 / 64 / 128 / 0, in_features not a multiple of 32 and of the group, an input of another shape
-// or device.
+// act_bits = 8 (W8A8 / W4A8): the same single node on nk_quant_a8_linear_fwd - the rows of x are quantised to int8 per row on the
+// fly and summed as integers on the int8 matrix instruction (lossy in x, so opt-in; groups 64, 128 and 0).  act_bits = 0: the layer
+// as it always was, bit for bit.
+// Panics: bits not 8 / 4, group not 32 / 64 / 128 / 0, in_features not a multiple of 32 and of the group, act_bits not 0 / 8,
+// act_bits = 8 with group 32, an input of another shape or device.
 struct QuantLinear {
     Shared<HipArray> qweight, scales, bias;
-    int in_features, out_features, bits, group;
-    QuantLinear(const Linear& lin, int bits, int group = 0);
+    int in_features, out_features, bits, group, act_bits;
+    QuantLinear(const Linear& lin, int bits, int group = 0, int act_bits = 0);
     Var forward(const Var& input) const;
     Var forward(const VarDiff& input) const;
     Var dequantize() const;

@@ -327,13 +327,15 @@ PYBIND11_MODULE(_tape, m) {
         .def("forward_relu", py::overload_cast<const Var&>(&nn::Linear::forward_relu, py::const_))
         .def("forward_relu", py::overload_cast<const VarDiff&>(&nn::Linear::forward_relu, py::const_));
     py::class_<nn::QuantLinear>(nn, "QuantLinear")
-        .def(py::init<const nn::Linear&, int, int>(), py::arg("linear"), py::arg("bits"), py::arg("group") = 0,
+        .def(py::init<const nn::Linear&, int, int, int>(), py::arg("linear"), py::arg("bits"), py::arg("group") = 0, py::arg("act_bits") = 0,
              "Weight-only quantised Linear for inference: packs the Linear's weight to int8 / int4 with per-group f32 scales (group 32, 64, "
-             "128, or 0 for one per row) on the device and shares its bias. The Linear is left as it is. No parameters, no gradient, no serde.")
+             "128, or 0 for one per row) on the device and shares its bias. The Linear is left as it is. No parameters, no gradient, no serde. "
+             "act_bits = 8: int8 activations, quantised per row on the fly, on the int8 matrix instruction (groups 64, 128, 0).")
         .def_readonly("in_features", &nn::QuantLinear::in_features)
         .def_readonly("out_features", &nn::QuantLinear::out_features)
         .def_readonly("bits", &nn::QuantLinear::bits)
         .def_readonly("group", &nn::QuantLinear::group)
+        .def_readonly("act_bits", &nn::QuantLinear::act_bits)
         .def("forward", py::overload_cast<const Var&>(&nn::QuantLinear::forward, py::const_), py::arg("input"),
              "(rows, in_features) -> (rows, out_features), one forward node on nk_quant_linear_fwd, no gradient.")
         // a differentiable input (what the layers return) enters through its data and forward tape

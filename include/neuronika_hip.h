@@ -195,8 +195,9 @@ int nk_graph_refuse_capture(nk_device* dev, const char* what);
  * MFMA kernels is bracketed by a HIP event pair on the compute stream.  nk_profile_end
  * synchronises and returns, for one kernel class, the number of launches, the sum of their
  * durations and the algorithmic flop they performed (2*M*N*K per GEMM; 2*N*Cout*L*K per conv
- * pass). */
-enum nk_kernel_class { NK_KERNEL_SGEMM = 0, NK_KERNEL_CONV = 1, NK_KERNEL_ATTENTION = 2 };
+ * pass; 2*M*N*K integer operations for the int8 GEMM kernel of nk_quant_a8_linear_fwd, whose
+ * row quantiser is not bracketed). */
+enum nk_kernel_class { NK_KERNEL_SGEMM = 0, NK_KERNEL_CONV = 1, NK_KERNEL_ATTENTION = 2, NK_KERNEL_QUANT_A8 = 3 };
 int nk_profile_begin(nk_device* dev);
 /* Suspends (paused != 0) / resumes the bracketing inside a window without dropping its records: an event pair costs the stream
  * ~10 us per launch, so a harness may instrument every n-th step of its timed region instead of all of them. */
@@ -1296,6 +1297,29 @@ int nk_quant_linear_pack(nk_device* dev, const float* W, int ldw, float* qw, flo
 int nk_quant_linear_unpack(nk_device* dev, const float* qw, const float* scales, float* W, int ldw, int N, int K, int bits, int group);
 int nk_quant_linear_fwd(nk_device* dev, const float* x, int ldx, const float* qw, const float* scales, const float* bias, float* y, int ldy,
                         int M, int N, int K, int bits, int group);
+/* ------------------------------------------------------------------ quantised Linear, int8 activations --
+ * Ours: W8A8 / W4A8.  The arguments are nk_quant_linear_fwd's (same weight format, same strides, bias may be NULL), but the rows of x are
+ * quantised to int8 on the fly, per row, and the products are summed as integers on v_mfma_i32_16x16x64_i8.  Activation rounding is
+ * lossy, so this is an entry of its own: nk_quant_linear_fwd never chooses it and keeps its bits.  Contract - every f32 operation
+ * rounded on its own, no fma:
+ *   activations, per row m (the weight format's rule with bits = 8, group = 0):
+ *             sx[m] = fl32(absmax / 127);  xq = clamp(rint(fl32(x / sx)), -127, 127), round-half-even;  sx == 0 gives xq = 0
+ *   span      `group` consecutive k for group 64 / 128; for group 0, F = 2048 consecutive k (the last span may be shorter)
+ *   sum       acc = +0, then over the spans j in ascending order
+ *             isum_j = sum_{k in span j} xq[m][k] * q[n][k]       exact in int32 (at most 2048 * 127^2 < 2^31)
+ *             p_j    = fl32(float(isum_j) * sw[n][j])             int -> f32 round-to-nearest-even (exact for groups 64 / 128);
+ *                                                                 group 0: sw[n][j] = sw[n]
+ *             acc    = fl32(acc + p_j)
+ *   result    y = fl32(acc * sx[m]), then y = fl32(y + bias[n]) with a bias
+ * Bit contract: the bits of y[m][n] depend on x[m, :], row n of qw and scales, bias[n] and (bits, group, K) only - not on M, N, the
+ * tile a row lands in, ldx / ldy or the alignment of x.  A NumPy restatement reproduces them exactly (tests/quant_a8_oracle.py).
+ * Error against the f64 product over w^: at most 0.5 * sx[m] * sum_k |w^[n][k]| from the activation rounding, plus f32 rounding.
+ * The int8 image of x and sx live in the device workspace (M * K bytes + M floats; its growth refuses stream capture, a warmed call is
+ * capturable); nothing else is allocated, no atomics.  Kernels: csrc/nk_quant_a8.h.
+ * NK_ERR_INVALID, nothing written: group 32 (one 64-k instruction would straddle two scales: use 64, 128 or 0), K > 2^30, and
+ * everything nk_quant_linear_fwd refuses.  M == 0 is an empty success. */
+int nk_quant_a8_linear_fwd(nk_device* dev, const float* x, int ldx, const float* qw, const float* scales, const float* bias, float* y, int ldy,
+                           int M, int N, int K, int bits, int group);
 /* ------------------------------------------------------------------ dropout ------------ */
 /* Dropout::forward node/dropout/mod.rs:53-79.  train && 0<p<1: noise ~ Bernoulli(1-p) in
  * {0,1} is (re)drawn from Philox4x32-10(seed, offset) and written to `noise` (f32, like the

@@ -808,6 +808,7 @@ impl SamplerState {
 pub struct QuantLinearState {
     weight: QuantWeight,
     bias: Option<Shared<HipArray<Ix1>>>,
+    act_bits: i32,
 }
 
 impl QuantLinearState {
@@ -823,7 +824,16 @@ impl QuantLinearState {
         if let Some(b) = bias {
             assert!(b.data.borrow().dimension()[0] == dim[0], "QuantLinearState: the bias must have one entry per output");
         }
-        Self { weight: q, bias: bias.map(|b| b.data.clone()) }
+        Self { weight: q, bias: bias.map(|b| b.data.clone()), act_bits: 0 }
+    }
+
+    /// `act_bits` 8: int8 activations, quantised per row on the fly (`nk_quant_a8_linear_fwd`; groups 64, 128 and 0).  0: f32
+    /// activations, the layer as built.
+    pub fn with_act_bits(mut self, act_bits: usize) -> Self {
+        assert!(act_bits == 0 || act_bits == 8, "QuantLinearState: act_bits must be 0 or 8");
+        assert!(act_bits == 0 || self.weight.group != 32, "QuantLinearState: act_bits = 8 takes group 64, 128 or 0");
+        self.act_bits = act_bits as i32;
+        self
     }
 
     /// The `(out, in)` values `float(q) * scale` as a leaf.
@@ -841,12 +851,13 @@ impl QuantLinearState {
 }
 
 impl HipVar<Ix2> {
-    /// `(rows, in) -> (rows, out)` on the packed integer weights of `layer`: ONE node (`nk_quant_linear_fwd`), no gradient.
+    /// `(rows, in) -> (rows, out)` on the packed integer weights of `layer`: ONE node (`nk_quant_linear_fwd`, or `nk_quant_a8_linear_fwd` for a layer
+    /// `with_act_bits(8)`), no gradient.
     pub fn quant_linear(self, layer: &QuantLinearState) -> HipVar<Ix2> {
         let dim = self.data.borrow().dimension();
         assert!(dim[1] == layer.weight.in_features, "quant_linear: the input must be (rows, {})", layer.weight.in_features);
         let data = shared(ndarray::Dim([dim[0], layer.weight.out_features]), &self.device());
-        let op = QuantLinear::new(layer.weight.clone(), layer.bias.clone(), dim[0], self.data, data.clone());
+        let op = QuantLinear::new(layer.weight.clone(), layer.bias.clone(), layer.act_bits, dim[0], self.data, data.clone());
         HipVar::node(data, Rc::new(op), self.history)
     }
 

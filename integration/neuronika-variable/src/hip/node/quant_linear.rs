@@ -53,19 +53,22 @@ impl QuantWeight {
 }
 
 /// Weight-only quantised Linear (ours: the reference has no such layer): `(rows, in) -> (rows, out)` on the packed integer weights,
-/// f32 activations and accumulation (`nk_quant_linear_fwd`).  Inference only: there is no backward node.
+/// f32 activations and accumulation (`nk_quant_linear_fwd`), or, with `act_bits == 8`, int8 activations quantised per row on the fly
+/// and integer sums on the int8 matrix instruction (`nk_quant_a8_linear_fwd`; groups 64, 128 and 0).  Inference only: there is no
+/// backward node.
 pub(crate) struct QuantLinear {
     weight: QuantWeight,
     bias: Option<Shared<HipArray<Ix1>>>,
+    act_bits: i32,
     rows: usize,
     input: Shared<HipArray<Ix2>>,
     data: Shared<HipArray<Ix2>>,
 }
 
 impl QuantLinear {
-    pub(crate) fn new(weight: QuantWeight, bias: Option<Shared<HipArray<Ix1>>>, rows: usize, input: Shared<HipArray<Ix2>>,
+    pub(crate) fn new(weight: QuantWeight, bias: Option<Shared<HipArray<Ix1>>>, act_bits: i32, rows: usize, input: Shared<HipArray<Ix2>>,
                       data: Shared<HipArray<Ix2>>) -> Self {
-        Self { weight, bias, rows, input, data }
+        Self { weight, bias, act_bits, rows, input, data }
     }
 }
 
@@ -76,9 +79,15 @@ impl Forward for QuantLinear {
         let (q, s) = (self.weight.qweight.borrow(), self.weight.scales.borrow());
         let bias = self.bias.as_ref().map(|b| b.borrow());
         let (n, k) = (self.weight.out_features as i32, self.weight.in_features as i32);
+        let b = bias.as_ref().map_or(std::ptr::null(), |b| b.as_ptr());
         ffi::check(unsafe {
-            ffi::nk_quant_linear_fwd(x.device().as_raw(), x.as_ptr(), k, q.as_ptr(), s.as_ptr(), bias.as_ref().map_or(std::ptr::null(), |b| b.as_ptr()),
-                                     y.as_mut_ptr(), n, self.rows as i32, n, k, self.weight.bits, self.weight.group)
+            if self.act_bits == 8 {
+                ffi::nk_quant_a8_linear_fwd(x.device().as_raw(), x.as_ptr(), k, q.as_ptr(), s.as_ptr(), b, y.as_mut_ptr(), n, self.rows as i32, n, k,
+                                            self.weight.bits, self.weight.group)
+            } else {
+                ffi::nk_quant_linear_fwd(x.device().as_raw(), x.as_ptr(), k, q.as_ptr(), s.as_ptr(), b, y.as_mut_ptr(), n, self.rows as i32, n, k,
+                                         self.weight.bits, self.weight.group)
+            }
         });
     }
 }

@@ -267,6 +267,7 @@ _SIGS = {
     "nk_quant_linear_pack": [VP, VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_quant_linear_unpack": [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_quant_linear_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_quant_a8_linear_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_scale_softmax_dropout_fwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_scale_softmax_dropout_bwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_dropout_fwd": [VP, VP, VP, VP, C.c_size_t, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
@@ -599,7 +600,7 @@ class HipIntArray(HipArray):
         return v
 
 
-KERNEL_SGEMM, KERNEL_CONV, KERNEL_ATTENTION = 0, 1, 2
+KERNEL_SGEMM, KERNEL_CONV, KERNEL_ATTENTION, KERNEL_QUANT_A8 = 0, 1, 2, 3
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1251,6 +1252,13 @@ def quant_linear_fwd(dev, x, ldx, qw, scales, bias, y, ldy, M, N, K, bits, group
     """y[m][n] = bias[n] + sum_k x[m][k] * w^[n][k]; x rows at stride ldx, y rows at stride ldy, bias may be None."""
     check(lib.nk_quant_linear_fwd(dev.h, _p(x), int(ldx), _p(qw), _p(scales), _p(bias), _p(y), int(ldy), int(M), int(N), int(K), int(bits),
                                   int(group)))
+
+
+def quant_a8_linear_fwd(dev, x, ldx, qw, scales, bias, y, ldy, M, N, K, bits, group=0):
+    """nk_quant_linear_fwd's arguments with int8 activations (W8A8 / W4A8): rows of x quantised per row on the fly, integer sums on the
+    int8 matrix instruction, one f32 conversion per span of `group` (2048 for group 0) k.  Groups 64, 128 and 0."""
+    check(lib.nk_quant_a8_linear_fwd(dev.h, _p(x), int(ldx), _p(qw), _p(scales), _p(bias), _p(y), int(ldy), int(M), int(N), int(K), int(bits),
+                                     int(group)))
 
 
 def attention_bwd(dev, dQ, dK, dV, dS, dropped, dO, out, scores, stats, mask_bits, Q, K, V, B, S, H, dh, scale, p, train=True,
