@@ -1085,6 +1085,16 @@ struct QuantLinearFwd : Forward {
     }
 };
 
+// nn::MxLinear::forward (ours; semantics at nk_quant_mx_linear_fwd in neuronika_hip.h): (rows, in) -> (rows, out) on the MXFP4
+// weights.  No backward node: the layer is inference-only.
+struct MxLinearFwd : Forward {
+    Shared<HipArray> x, qweight, scales, bias, y;
+    int rows = 0, in = 0, out = 0;
+    void forward() const override {
+        check(nk_quant_mx_linear_fwd(D(x), x->ptr(), in, qweight->ptr(), scales->ptr(), bias ? bias->ptr() : nullptr, y->ptr(), out, rows, out, in));
+    }
+};
+
 // Scalar criteria: node/{absolute_error,bce,bce_with_logits,kldiv,nll}/mod.rs.  kind -1 = NLL.
 struct LossFwd : Forward {
     int kind;
@@ -3644,6 +3654,35 @@ Var QuantLinear::forward(const VarDiff& x) const { return forward(x.var); }
 Var QuantLinear::dequantize() const {
     auto w = std::make_shared<HipArray>(qweight->device(), Shape{out_features, in_features});
     check(nk_quant_linear_unpack(D(w), qweight->ptr(), scales->ptr(), w->ptr(), in_features, out_features, in_features, bits, group));
+    return Var::leaf(w);
+}
+MxLinear::MxLinear(const Linear& lin) {
+    const Shape& ws = lin.weight.shape();
+    if (ws.size() != 2 || lin.bias.shape() != Shape{ws[0]}) panic("MxLinear: the Linear must hold an (out, in) weight and an (out) bias");
+    out_features = ws[0]; in_features = ws[1];
+    const size_t words = nk_quant_mx_words(out_features, in_features), ns = nk_quant_mx_scales(out_features, in_features);
+    if (words == 0 || ns == 0) panic("MxLinear: the input extent (" + std::to_string(in_features) + ") must be a multiple of the MX block, 32");
+    const Shared<HipArray>& w = lin.weight.var.data;
+    qweight = std::make_shared<HipArray>(w->device(), Shape{(int)words}, HipArray::Uninit{});
+    scales = std::make_shared<HipArray>(w->device(), Shape{(int)ns}, HipArray::Uninit{});
+    check(nk_quant_mx_pack(D(w), w->ptr(), in_features, qweight->ptr(), scales->ptr(), out_features, in_features));
+    bias = lin.bias.var.data;
+}
+Var MxLinear::forward(const Var& x) const {
+    const Shape& s = x.shape();
+    if (s.size() != 2 || s[1] != in_features) panic("MxLinear: the input must be (rows, " + std::to_string(in_features) + ")");
+    if (x.device().get() != qweight->device().get()) panic("MxLinear: the input lives on another device");
+    auto n = std::make_shared<MxLinearFwd>();
+    n->x = x.data; n->qweight = qweight; n->scales = scales; n->bias = bias;
+    n->rows = s[0]; n->in = in_features; n->out = out_features;
+    n->y = zeros_like(x.data, Shape{s[0], out_features});
+    auto y = n->y;
+    return Var::node(y, n, x.history);
+}
+Var MxLinear::forward(const VarDiff& x) const { return forward(x.var); }
+Var MxLinear::dequantize() const {
+    auto w = std::make_shared<HipArray>(qweight->device(), Shape{out_features, in_features});
+    check(nk_quant_mx_unpack(D(w), qweight->ptr(), scales->ptr(), w->ptr(), in_features, out_features, in_features));
     return Var::leaf(w);
 }
 void MultiheadAttention::quantize(int bits, int group) {

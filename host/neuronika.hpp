@@ -665,6 +665,20 @@ struct QuantLinear {
     Var forward(const VarDiff& input) const;
     Var dequantize() const;
 };
+// Microscaling Linear for inference (ours; format and contract at nk_quant_mx_* in neuronika_hip.h): the weight of `lin` packed on
+// the device to MXFP4 (E2M1 elements, one E8M0 scale per 32 consecutive inputs of a row), its bias shared; the Linear is left as
+// it is.  forward(x): (rows, in_features) -> (rows, out_features) as ONE forward node on nk_quant_mx_linear_fwd, without a gradient -
+// the rows of x are quantised to MXFP8 on the fly and multiplied on the block-scaled matrix instruction.  dequantize(): the
+// (out, in) values element * 2^(e - 127) the node multiplies by.  No parameters, no serde.
+// Panics: in_features not a multiple of 32, an input of another shape or device.
+struct MxLinear {
+    Shared<HipArray> qweight, scales, bias;
+    int in_features, out_features;
+    explicit MxLinear(const Linear& lin);
+    Var forward(const Var& input) const;
+    Var forward(const VarDiff& input) const;
+    Var dequantize() const;
+};
 // Graph-build peephole `forward(x).relu()` -> the Linear+ReLU node (on by default, per thread; off: the ReLU node over the
 // Linear's output, as the tests that pit the two graphs against each other bit for bit need it).  Returns the old setting.
 bool set_relu_peephole(bool on);

@@ -341,6 +341,17 @@ PYBIND11_MODULE(_tape, m) {
         // a differentiable input (what the layers return) enters through its data and forward tape
         .def("forward", py::overload_cast<const VarDiff&>(&nn::QuantLinear::forward, py::const_), py::arg("input"))
         .def("dequantize", &nn::QuantLinear::dequantize, "The (out_features, in_features) values float(q) * scale the layer multiplies by.");
+    py::class_<nn::MxLinear>(nn, "MxLinear")
+        .def(py::init<const nn::Linear&>(), py::arg("linear"),
+             "Microscaling Linear for inference: packs the Linear's weight to MXFP4 (E2M1 elements, one E8M0 scale per 32 inputs of a row) "
+             "on the device and shares its bias; in_features must be a multiple of 32. The Linear is left as it is. No parameters, no "
+             "gradient, no serde.")
+        .def_readonly("in_features", &nn::MxLinear::in_features)
+        .def_readonly("out_features", &nn::MxLinear::out_features)
+        .def("forward", py::overload_cast<const Var&>(&nn::MxLinear::forward, py::const_), py::arg("input"),
+             "(rows, in_features) -> (rows, out_features), one forward node on nk_quant_mx_linear_fwd (rows of x to MXFP8 on the fly), no gradient.")
+        .def("forward", py::overload_cast<const VarDiff&>(&nn::MxLinear::forward, py::const_), py::arg("input"))
+        .def("dequantize", &nn::MxLinear::dequantize, "The (out_features, in_features) values element * 2^(e - 127) the layer multiplies by.");
     py::class_<nn::LayerNorm>(nn, "LayerNorm")
         .def(py::init<DevicePtr, Shape, double, bool>(), py::arg("dev"), py::arg("normalized_shape"), py::arg("eps") = 1e-5,
              py::arg("elementwise_affine") = true)

@@ -196,8 +196,8 @@ int nk_graph_refuse_capture(nk_device* dev, const char* what);
  * synchronises and returns, for one kernel class, the number of launches, the sum of their
  * durations and the algorithmic flop they performed (2*M*N*K per GEMM; 2*N*Cout*L*K per conv
  * pass; 2*M*N*K integer operations for the int8 GEMM kernel of nk_quant_a8_linear_fwd, whose
- * row quantiser is not bracketed). */
-enum nk_kernel_class { NK_KERNEL_SGEMM = 0, NK_KERNEL_CONV = 1, NK_KERNEL_ATTENTION = 2, NK_KERNEL_QUANT_A8 = 3 };
+ * row quantiser is not bracketed; likewise 2*M*N*K for the GEMM kernel of nk_quant_mx_linear_fwd). */
+enum nk_kernel_class { NK_KERNEL_SGEMM = 0, NK_KERNEL_CONV = 1, NK_KERNEL_ATTENTION = 2, NK_KERNEL_QUANT_A8 = 3, NK_KERNEL_QUANT_MX = 4 };
 int nk_profile_begin(nk_device* dev);
 /* Suspends (paused != 0) / resumes the bracketing inside a window without dropping its records: an event pair costs the stream
  * ~10 us per launch, so a harness may instrument every n-th step of its timed region instead of all of them. */
@@ -1320,6 +1320,47 @@ int nk_quant_linear_fwd(nk_device* dev, const float* x, int ldx, const float* qw
  * everything nk_quant_linear_fwd refuses.  M == 0 is an empty success. */
 int nk_quant_a8_linear_fwd(nk_device* dev, const float* x, int ldx, const float* qw, const float* scales, const float* bias, float* y, int ldy,
                            int M, int N, int K, int bits, int group);
+/* ------------------------------------------------------------------ microscaling Linear (MXFP4 x MXFP8) --
+ * Ours: an inference layer of its own beside the quantised Linear above, on gfx950's block-scaled matrix instruction
+ * v_mfma_scale_f32_16x16x128_f8f6f4.  Everything is OCP Microscaling (MX) v1.0: blocks of 32 consecutive k of one row share a
+ * power-of-two scale, an E8M0 byte e of value 2^(e - 127).  Format, so that an external packer can produce it; K % 32 == 0:
+ *   scale    per row and block: absmax == 0 gives e = 127 and elements 0; otherwise, with E the exponent field of the f32 absmax
+ *            (E - 127 = floor(log2(absmax)) for a normal number, E = 0 for a subnormal one),
+ *                e = clamp(E - emax, 0, 254),   emax = 2 for the weights (E2M1), 8 for the rows of x (E4M3).
+ *            Byte 255 (NaN) is never produced.
+ *   element  v = |w| * 2^(127 - e), exact; rounded to the nearest value of the element format, ties to the even mantissa, then
+ *            saturated (6 / 448).  As ONE rounding: with B the binade of v (not below the lowest normal one, 0 / -6) and m the
+ *            mantissa bits (1 / 3), rint(v * 2^(m - B)) * 2^(B - m).  The sign is w's; a zero element carries none.
+ *   weights  MXFP4.  qw: rows of K / 2 bytes of E2M1 codes - sign, then the magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 - element k in byte
+ *            k / 2, even k in the low nibble: nk_quant_mx_words(N, K) floats of opaque words, 16-byte aligned.  sw: the (N, K / 32)
+ *            scale bytes, dense: nk_quant_mx_scales(N, K) floats hold them.  Both return 0 for a geometry the calls refuse.
+ *   rows     MXFP8.  E4M3 codes (bias 7, subnormals, no infinities; 0x7f / 0xff, the NaNs, are never produced), one byte per
+ *            element, made per call from the rows of x, with (M, K / 32) scale bytes.
+ *   value    w^ = element * 2^(e - 127), x^ likewise: exact in f32 (subnormal results included).
+ *   Non-finite inputs give unspecified values; the calls stay memory-safe.
+ * nk_quant_mx_pack: W (row stride ldw) -> qw, sw, on the device.  nk_quant_mx_unpack: w^ into W (row stride ldw; nothing beyond a
+ *   row's K columns is written).  nk_quant_mx_rows: the activation quantiser as an entry of its own - M rows of K bytes into xq
+ *   (16-byte aligned), M rows of K / 32 scale bytes into sx; the forward runs the same kernel into the device workspace.
+ * nk_quant_mx_linear_fwd: y[m][n] = bias[n] + sum_k x^[m][k] * w^[n][k] for M rows; x row m at x + m*ldx, y row m at y + m*ldy, as
+ *   in nk_quant_a8_linear_fwd; bias may be NULL.  The products are exact and are summed in f32 inside the matrix instruction, 128 k
+ *   an instruction, both scales applied by the instruction.  Two kernel classes, chosen from M alone:
+ *   skinny  M <= 16: eight waves of a block take interleaved 128-k slabs of K (wave w: slabs w, w + 8, ...), each chaining its own
+ *           accumulator; the eight sums are added in ascending wave order, then the bias.
+ *   wide    M > 16: one accumulator per output, chained from the first slab of K to the last, then the bias.
+ *   Bit contract: within one class the bits of y[m][n] depend on x[m, :], row n of qw and sw, bias[n] and K only - not on M, N,
+ *   the tile a row lands in, ldx / ldy or the alignment of x.  The two classes may differ from each other in the last bits.
+ *   Error against the f64 product of x^ and w^: at most 2 (K + 2) * 2^-24 * (sum_k |x^ w^| + |bias|).
+ * The image of x lives in the device workspace (M * K bytes + M * roundup(K / 32, 16) scale bytes; its growth refuses stream
+ * capture, a warmed call is capturable); nothing else is allocated, no atomics.  Kernels: csrc/nk_quant_mx.h.
+ * NK_ERR_INVALID, nothing written: K % 32 != 0, non-positive N or K (nk_quant_mx_rows: M), K > 2^30, M < 0 (M == 0 is an empty
+ * success), a null pointer other than bias, ldx < K, ldy < N, ldw < K, qw or xq not 16-byte aligned. */
+size_t nk_quant_mx_words(int N, int K);
+size_t nk_quant_mx_scales(int N, int K);
+int nk_quant_mx_pack(nk_device* dev, const float* W, int ldw, float* qw, float* sw, int N, int K);
+int nk_quant_mx_unpack(nk_device* dev, const float* qw, const float* sw, float* W, int ldw, int N, int K);
+int nk_quant_mx_rows(nk_device* dev, const float* x, int ldx, float* xq, float* sx, int M, int K);
+int nk_quant_mx_linear_fwd(nk_device* dev, const float* x, int ldx, const float* qw, const float* sw, const float* bias, float* y, int ldy,
+                           int M, int N, int K);
 /* ------------------------------------------------------------------ dropout ------------ */
 /* Dropout::forward node/dropout/mod.rs:53-79.  train && 0<p<1: noise ~ Bernoulli(1-p) in
  * {0,1} is (re)drawn from Philox4x32-10(seed, offset) and written to `noise` (f32, like the

@@ -27,6 +27,7 @@ use super::{
         RepeatKv, RepeatKvBackward, RepeatKvGeometry, rope_table, Rope, RopeBackward, RopeGeometry, RopeInPlace, RopeInPlaceBackward,
         sample_stage_limit, Sample, SampleParams,
         quant_linear_rows_rule, QuantLinear, QuantWeight,
+        MxLinear, MxWeight,
         Upsample, UpsampleBackward, UpsampleGeometry, UpsampleMode,
         MultiConcatenate, MultiConcatenateBackward, PackedHeadsAttention, PackedHeadsAttentionBackward, Pad, PadBackward, PadMode, Pair, ReLU,
         ReLUBackward, ReluMask, Softmax, SoftmaxBackward,
@@ -850,7 +851,49 @@ impl QuantLinearState {
     }
 }
 
+/// An `(out, in)` weight in MXFP4 with its optional bias (ours; format at `nk_quant_mx_*` in `include/neuronika_hip.h`): what
+/// `HipVar::mx_linear` multiplies by.  Built from an f32 weight on the device, which is left as it is; `in` a multiple of 32.
+/// Inference only: no gradient, no parameters for an optimizer, no serde.
+#[derive(Clone)]
+pub struct MxLinearState {
+    weight: MxWeight,
+    bias: Option<Shared<HipArray<Ix1>>>,
+}
+
+impl MxLinearState {
+    pub fn new(weight: &HipVar<Ix2>, bias: Option<&HipVar<Ix1>>) -> Self {
+        let dim = weight.data.borrow().dimension();
+        let (words, scales) = MxWeight::sizes(dim[0], dim[1]).expect("MxLinearState: the input extent must be a multiple of the MX block, 32");
+        let device = weight.device();
+        let q = MxWeight { qweight: shared(ndarray::Dim([words]), &device), scales: shared(ndarray::Dim([scales]), &device),
+                           out_features: dim[0], in_features: dim[1] };
+        q.pack(&weight.data.borrow());
+        if let Some(b) = bias {
+            assert!(b.data.borrow().dimension()[0] == dim[0], "MxLinearState: the bias must have one entry per output");
+        }
+        Self { weight: q, bias: bias.map(|b| b.data.clone()) }
+    }
+
+    /// The `(out, in)` values `element * 2^(e - 127)` as a leaf.
+    pub fn dequantize(&self) -> HipVar<Ix2> {
+        let device = self.weight.qweight.borrow().device().clone();
+        let data = shared(ndarray::Dim([self.weight.out_features, self.weight.in_features]), &device);
+        self.weight.unpack(&mut data.borrow_mut());
+        HipVar { data, history: History::default() }
+    }
+}
+
 impl HipVar<Ix2> {
+    /// `(rows, in) -> (rows, out)` on the MXFP4 weights of `layer`, the rows quantised to MXFP8 on the fly: ONE node
+    /// (`nk_quant_mx_linear_fwd`), no gradient.
+    pub fn mx_linear(self, layer: &MxLinearState) -> HipVar<Ix2> {
+        let dim = self.data.borrow().dimension();
+        assert!(dim[1] == layer.weight.in_features, "mx_linear: the input must be (rows, {})", layer.weight.in_features);
+        let data = shared(ndarray::Dim([dim[0], layer.weight.out_features]), &self.device());
+        let op = MxLinear::new(layer.weight.clone(), layer.bias.clone(), dim[0], self.data, data.clone());
+        HipVar::node(data, Rc::new(op), self.history)
+    }
+
     /// `(rows, in) -> (rows, out)` on the packed integer weights of `layer`: ONE node (`nk_quant_linear_fwd`, or `nk_quant_a8_linear_fwd` for a layer
     /// `with_act_bits(8)`), no gradient.
     pub fn quant_linear(self, layer: &QuantLinearState) -> HipVar<Ix2> {

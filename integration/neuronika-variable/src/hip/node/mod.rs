@@ -16,6 +16,7 @@ mod layout;
 mod linear;
 mod matrix_matrix_mul;
 mod matrix_matrix_mul_t;
+mod mx_linear;
 mod normalization;
 mod optim;
 mod pointwise;
@@ -40,6 +41,7 @@ pub(crate) use layout::*;
 pub(crate) use linear::*;
 pub(crate) use matrix_matrix_mul::*;
 pub(crate) use matrix_matrix_mul_t::*;
+pub(crate) use mx_linear::*;
 pub(crate) use normalization::*;
 pub(crate) use optim::*;
 pub(crate) use pointwise::*;

@@ -268,6 +268,12 @@ _SIGS = {
     "nk_quant_linear_unpack": [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_quant_linear_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_quant_a8_linear_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "nk_quant_mx_words": [C.c_int, C.c_int],
+    "nk_quant_mx_scales": [C.c_int, C.c_int],
+    "nk_quant_mx_pack": [VP, VP, C.c_int, VP, VP, C.c_int, C.c_int],
+    "nk_quant_mx_unpack": [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int],
+    "nk_quant_mx_rows": [VP, VP, C.c_int, VP, VP, C.c_int, C.c_int],
+    "nk_quant_mx_linear_fwd": [VP, VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int],
     "nk_scale_softmax_dropout_fwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_scale_softmax_dropout_bwd": [VP, VP, VP, VP, VP, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
     "nk_dropout_fwd": [VP, VP, VP, VP, C.c_size_t, C.c_double, C.c_int, C.c_uint64, C.c_uint64],
@@ -309,6 +315,7 @@ _SIGS = {
 _RESTYPES = {"nk_last_error": C.c_char_p, "nk_version": C.c_char_p, "nk_stream_compute": VP, "nk_stream_comm": VP,
              "nk_attention_decode_workspace": C.c_size_t, "nk_attention_decode_window_workspace": C.c_size_t,
              "nk_attention_decode_paged_workspace": C.c_size_t, "nk_quant_linear_words": C.c_size_t, "nk_quant_linear_scales": C.c_size_t,
+             "nk_quant_mx_words": C.c_size_t, "nk_quant_mx_scales": C.c_size_t,
              "nk_gemm_buffer_records": C.c_longlong, "nk_attention_band_scratch": C.c_size_t, "nk_attention_band_mask_words": C.c_size_t}
 EXPORTED = tuple(_SIGS)
 
@@ -600,7 +607,7 @@ class HipIntArray(HipArray):
         return v
 
 
-KERNEL_SGEMM, KERNEL_CONV, KERNEL_ATTENTION, KERNEL_QUANT_A8 = 0, 1, 2, 3
+KERNEL_SGEMM, KERNEL_CONV, KERNEL_ATTENTION, KERNEL_QUANT_A8, KERNEL_QUANT_MX = 0, 1, 2, 3, 4
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1259,6 +1266,37 @@ def quant_a8_linear_fwd(dev, x, ldx, qw, scales, bias, y, ldy, M, N, K, bits, gr
     int8 matrix instruction, one f32 conversion per span of `group` (2048 for group 0) k.  Groups 64, 128 and 0."""
     check(lib.nk_quant_a8_linear_fwd(dev.h, _p(x), int(ldx), _p(qw), _p(scales), _p(bias), _p(y), int(ldy), int(M), int(N), int(K), int(bits),
                                      int(group)))
+
+
+def quant_mx_words(N, K) -> int:
+    """Floats that hold the MXFP4 codes of an (N, K) weight; 0 for a geometry the entry points refuse."""
+    return int(lib.nk_quant_mx_words(int(N), int(K)))
+
+
+def quant_mx_scales(N, K) -> int:
+    """Floats that hold the (N, K / 32) E8M0 scale bytes; 0 for a geometry the entry points refuse."""
+    return int(lib.nk_quant_mx_scales(int(N), int(K)))
+
+
+def quant_mx_pack(dev, W, ldw, qw, sw, N, K):
+    """W (N rows of K floats, row stride ldw) -> MXFP4 codes `qw` and E8M0 scale bytes `sw`, on the device."""
+    check(lib.nk_quant_mx_pack(dev.h, _p(W), int(ldw), _p(qw), _p(sw), int(N), int(K)))
+
+
+def quant_mx_unpack(dev, qw, sw, W, ldw, N, K):
+    """The values element * 2^(e - 127) into W (row stride ldw); nothing beyond a row's K columns is written."""
+    check(lib.nk_quant_mx_unpack(dev.h, _p(qw), _p(sw), _p(W), int(ldw), int(N), int(K)))
+
+
+def quant_mx_rows(dev, x, ldx, xq, sx, M, K):
+    """The MXFP8 (E4M3) image of M rows of x: M * K code bytes into `xq`, M * K / 32 scale bytes into `sx`."""
+    check(lib.nk_quant_mx_rows(dev.h, _p(x), int(ldx), _p(xq), _p(sx), int(M), int(K)))
+
+
+def quant_mx_linear_fwd(dev, x, ldx, qw, sw, bias, y, ldy, M, N, K):
+    """y[m][n] = bias[n] + sum_k x^[m][k] * w^[n][k] on the block-scaled matrix instruction: MXFP4 weights, rows of x quantised to
+    MXFP8 on the fly; x rows at stride ldx, y rows at stride ldy, bias may be None."""
+    check(lib.nk_quant_mx_linear_fwd(dev.h, _p(x), int(ldx), _p(qw), _p(sw), _p(bias), _p(y), int(ldy), int(M), int(N), int(K)))
 
 
 def attention_bwd(dev, dQ, dK, dV, dS, dropped, dO, out, scores, stats, mask_bits, Q, K, V, B, S, H, dh, scale, p, train=True,

@@ -313,6 +313,7 @@ int rms_norm_bwd_gamma(nk_device* dev, float* dgamma, const float* g, const floa
 #include "nk_quant_linear.h"  // weight-only int8 / int4 Linear: pack, unpack, the decode rows kernels and their entry points
 #include "nk_quant_linear_mma.h"  // ... and its fused-dequant MFMA kernel for more rows than those
 #include "nk_quant_a8.h"  // int8 activations: the row quantiser and the int8 MFMA kernel of nk_quant_a8_linear_fwd
+#include "nk_quant_mx.h"  // microscaling Linear: MXFP4 weights x MXFP8 rows on the block-scaled MFMA (nk_quant_mx_*)
 
 extern "C" {
 
